@@ -141,6 +141,27 @@ def build_instance(dev, T, N, cano_idx, seed, use_flow=True, n_iter=15000, use_g
     return eng, seq, model
 
 
+def dump_outputs(eng, out_dir, steps):
+    """What a caller of the timed loop holds after its last iteration, written as out_dir/<name>.npy (float32; the part labels
+    as float64): that iteration's losses and forward output, the optimised parameters, and the loss rows of the timed steps.
+    Under 2 MB at the default size; the inputs are seeded, so two builds run with the same arguments compare file by file."""
+    it, log = eng.loss_log()
+    arrays = {
+        "losses": eng.last_losses(),                 # [4] recon, lambda * flow, total, tau
+        "loss_log": log[-min(steps, log.shape[0]):] if steps > 0 else log[:0],   # [min(steps, ring), 4], oldest first
+        "pc_trans": eng.pc_trans,                    # [T-1, N, 3] in the caller's point order
+        "seg_part": eng.seg_part.double(),           # [N] arg-max part of the noise-free logits
+        "trans_list": eng.trans_list,                # [T-1, P, 4, 4] per-part transforms
+        "iterations": torch.tensor([it], dtype=torch.float64),   # iterations done, warm-up included
+    }
+    for name, p in zip(("seg_w1", "seg_b1", "seg_w2", "proposal_6d", "proposal_t"), eng.params):
+        arrays[name] = p
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a if a.dtype == np.float64 else a.astype(np.float32))
+
+
 def cpu_baseline(seq, T, N, cano_idx, budget_s=20.0):
     """The oracle's iteration (C, OpenMP) on the host cores: a bounded sample of the same workload."""
     import oracle
@@ -885,7 +906,11 @@ def main():
                     help="(default, as in run_robot.py) assignment-bound configs: tied optima settled canonically")
     ap.add_argument("--no-deterministic", dest="deterministic", action="store_false")
     ap.add_argument("--one-mode", action="store_true", help="nao_projection: do not repeat the bounded sample in the other mode")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="relax: after the timed steps write what the last one computed (rank 0, first instance) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.dump_outputs and args.config != "relax":
+        raise SystemExit("--dump-outputs: only the relax config (the headline loop) dumps its outputs")
     # an explicit --steps N always means N (1500 used to be a sentinel for "the whole run" of the nao configs)
     args.full = args.steps is None
     from reart_amd.utils import lap as _lap
@@ -1006,6 +1031,8 @@ def main():
     except Exception:
         prof = None
     replays, eager = eng.graph_replays, eng.eager_steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, args.dump_outputs, args.steps)     # before anything below steps the engine again (step_timed)
     el_local = el                                   # this rank's own clock around the timed region (the line's `value` uses the max)
     if distributed:
         tt = torch.tensor([el], dtype=torch.float64, device=dev)

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -33,6 +34,24 @@ def test_headline_line_contract(dev):
     assert r["traffic"] is None or isinstance(r["traffic"], (int, float))        # a number of bytes (or null), as the contract says
     # the launch chain with its arithmetic removed, measured in the run: below the step, the small kernels' share below the whole
     assert 0 < r["step_floor_small_kernels_us"] < r["step_floor_us"] < 1e3 * d["ms_per_step"] and 0 < r["step_floor_frac"] < 1
+
+
+def test_dump_outputs(dev, tmp_path):
+    """--dump-outputs DIR: what the last timed iteration computed, as float32 / float64 .npy files under 64 MB, consistent with the
+    line; --steps sets the timed iterations (one loss row each) and the warm-up comes on top."""
+    d = _run("--gpus", "1", "--steps", "7", "--warmup", "3", "--no-cpu-baseline", "--no-secondary", "--no-tail", "--sweep-instances", "0",
+             "--profile-steps", "0", "--dump-outputs", str(tmp_path))
+    a = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert set(a) == {"losses", "loss_log", "pc_trans", "seg_part", "trans_list", "iterations",
+                      "seg_w1", "seg_b1", "seg_w2", "proposal_6d", "proposal_t"}
+    assert all(v.dtype in (np.float32, np.float64) and np.isfinite(v).all() for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert d["steps"] == 7 and a["loss_log"].shape == (7, 4) and a["iterations"].tolist() == [10.0]
+    np.testing.assert_array_equal(a["loss_log"][-1], a["losses"])
+    np.testing.assert_allclose(a["losses"][:2], [d["final_losses"]["recon"], d["final_losses"]["flow"]], rtol=1e-4)
+    assert a["pc_trans"].shape == (19, 4096, 3) and a["trans_list"].shape == (19, 20, 4, 4)
+    seg = a["seg_part"]
+    assert seg.shape == (4096,) and (seg == np.round(seg)).all() and 0 <= seg.min() and seg.max() < 20
 
 
 def _strings(x, path=""):
