@@ -32,12 +32,15 @@ extern "C" {
 typedef enum {
     REART_OK = 0,
     REART_ERR_INVALID_ARG = -1,   /* null pointer, negative size, bad enum      */
-    REART_ERR_UNSUPPORTED = -2,   /* e.g. D != 3, K > REART_MAX_K                */
+    REART_ERR_UNSUPPORTED = -2,   /* e.g. D != 3, K > REART_MAX_K_LIST           */
     REART_ERR_LAUNCH = -3,        /* hipGetLastError() after a launch            */
     REART_ERR_NO_DEVICE = -4      /* no HIP device visible                       */
 } reart_status;
 
 #define REART_MAX_K 16            /* neighbours kept in registers per query      */
+#define REART_MAX_K_LIST 1024     /* K-NN searches with K > REART_MAX_K keep a    */
+                                  /* sorted key list per query in LDS (one wave   */
+                                  /* per query); above this they are unsupported  */
 
 /* Library / device probes (host side, no device work). */
 int reart_version(void);                       /* 100*major + minor              */
@@ -54,8 +57,10 @@ const char *reart_status_string(int status);
  *   dists [N,P1,K] f32 squared L2, idx [N,P1,K] i64 into p2, ascending by
  *   (distance, index); rows >= lengths1[n] and slots >= lengths2[n] are zero.
  * Distance contract: ((dx*dx)+(dy*dy))+(dz*dz) in fp32, no FMA, ties -> lowest j.
+ * 1 <= K <= REART_MAX_K_LIST; K <= REART_MAX_K runs the register-list kernels, larger K
+ * the LDS-list kernel (same result contract).
  * workspace (SoA target image + per-slice partial results):
- *   reart_knn_points_workspace_bytes(N,P1,P2,K) bytes. */
+ *   reart_knn_points_workspace_bytes(N,P1,P2,K) bytes (0 when K is out of range). */
 size_t reart_knn_points_workspace_bytes(int N, int P1, int P2, int K);
 int reart_knn_points_idx(const float *p1, const float *p2,
                          const int64_t *lengths1, const int64_t *lengths2,
@@ -89,6 +94,7 @@ int reart_chamfer_bidir(const float *x, const float *y, int N, int P,
  * (run_robot.py:65-66,122; shape contract utils/model_utils.py:42):
  *   ref [B,nr,3], query [B,nq,3] -> dist [B,nq,k] ascending, idx [B,nq,k] i64.
  * euclidean != 0: dist = sqrt(squared distance) (upstream KNN_CUDA 0.2).
+ * 1 <= k <= min(nr, REART_MAX_K_LIST).
  * workspace: reart_knn_points_workspace_bytes(B, nq, nr, k). */
 int reart_knn_cuda(const float *ref, const float *query, int B, int nr, int nq,
                    int D, int k, int euclidean, float *dist, int64_t *idx,
@@ -344,9 +350,22 @@ int reart_relax_profile(const reart_relax_config *cfg, void *workspace, size_t w
  *   the CPU fallback draws it from torch's RNG: inject it);  cuda_mode = 0: arg-max = first
  *   maximum (torch.max), 1: the CUDA kernel's block-tree tie rule.  No `temp` buffer is
  *   needed: the running minimum distances live in registers.
- *   idx32 [B,npoint] i32 and/or idx64 [B,npoint] i64 (either may be NULL).  N <= 12288. */
+ *   idx32 [B,npoint] i32 and/or idx64 [B,npoint] i64 (either may be NULL).
+ *   N <= REART_FPS_MAX_N_LDS (the cloud is staged in LDS); larger clouds: reart_fps_temp. */
+#define REART_FPS_MAX_N_LDS 12288         /* reart_fps: 12 B of LDS per point              */
+#define REART_FPS_MAX_N (1 << 21)         /* reart_fps_temp: 21-bit index in the tie key   */
 int reart_fps(const float *xyz, int B, int N, int npoint, const int32_t *start, int cuda_mode,
               int32_t *idx32, int64_t *idx64, void *stream);
+
+/* The same sampling, same arguments and both tie rules, for 1 <= N <= REART_FPS_MAX_N, with the
+ * reference wrapper's caller-allocated distance buffer (sampling.cpp:38-49 temp_tensor).
+ *   temp: f32 [B,N] (B * N * sizeof(float) bytes), scratch only: the kernel initialises the
+ *   entries it uses and the caller's contents are never read.  For N <= REART_FPS_MAX_N_LDS the
+ *   call is reart_fps and `temp` is not touched; above it one 1024-thread workgroup per cloud
+ *   keeps 16 384 running minima in registers and the rest in `temp`.
+ *   N > REART_FPS_MAX_N: REART_ERR_UNSUPPORTED. */
+int reart_fps_temp(const float *xyz, int B, int N, int npoint, const int32_t *start, int cuda_mode,
+                   float *temp, int32_t *idx32, int64_t *idx64, void *stream);
 
 /* Replaces ball_query_wrapper(b,n,m,radius,nsample,new_xyz,xyz,idx)
  * (networks/pointnet_lib/src/ball_query.cpp:15-26 -> ball_query_gpu.cu:9-45) and the CPU

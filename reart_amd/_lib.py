@@ -16,6 +16,12 @@ LIB_PATH = os.environ.get("REART_LIB") or os.path.join(_HERE, "csrc", "libreart_
 c_int, c_float, c_size_t, c_void_p = ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_void_p
 P = c_void_p  # every device pointer
 
+# size limits of include/reart_hip.h, checked before a call so that they surface as NotImplementedError
+MAX_K = 16               # REART_MAX_K: K-NN list in registers
+MAX_K_LIST = 1024        # REART_MAX_K_LIST: K-NN list in LDS, the largest K of any search
+FPS_MAX_N_LDS = 12288    # REART_FPS_MAX_N_LDS: reart_fps, cloud staged in LDS
+FPS_MAX_N = 1 << 21      # REART_FPS_MAX_N: reart_fps_temp, 21-bit index in the tie key
+
 # name -> (restype, argtypes); mirrors include/reart_hip.h one to one
 PROTOTYPES = {
     "reart_version": (c_int, []),
@@ -47,6 +53,7 @@ PROTOTYPES = {
     "reart_adam_step": (c_int, [P, P, P, P, c_int, c_int, c_float, c_float, c_float, c_float, P]),
     "reart_adam_step_multi": (c_int, [c_int, P, P, P, P, P, P, c_int, c_float, c_float, c_float, P]),
     "reart_fps": (c_int, [P, c_int, c_int, c_int, P, c_int, P, P, P]),
+    "reart_fps_temp": (c_int, [P, c_int, c_int, c_int, P, c_int, P, P, P, P]),
     "reart_ball_query": (c_int, [P, P, c_int, c_int, c_int, ctypes.c_double, c_int, c_int, P, P, P]),
     "reart_pn2_gather_points": (c_int, [P, P, c_int, c_int, c_int, c_int, P, P]),
     "reart_pn2_gather_points_grad": (c_int, [P, P, c_int, c_int, c_int, c_int, P, P]),

@@ -19,13 +19,18 @@ def _as_len(lengths, n, full, device):
 
 
 def knn_points_idx(p1, p2, lengths1, lengths2, K, version=-1):
-    """-> (idx int64 [N,P1,K], dists float32 [N,P1,K] squared L2), cf. utils/chamfer.py:174."""
+    """-> (idx int64 [N,P1,K], dists float32 [N,P1,K] squared L2), cf. utils/chamfer.py:174.
+
+    1 <= K <= 1024: K <= 16 keeps each query's list in registers, larger K in LDS (same result, bit for bit);
+    K > 1024 raises NotImplementedError."""
     _lib.require_gpu(p1, p2, lengths1, lengths2)
     if p1.dtype != torch.float32 or p2.dtype != torch.float32:
         raise TypeError("knn_points_idx expects float32 point clouds")
     p1, p2 = p1.contiguous(), p2.contiguous()
     N, P1, D = p1.shape
     P2 = p2.shape[1]
+    if K > _lib.MAX_K_LIST:
+        raise NotImplementedError(f"knn_points_idx: K = {K} > {_lib.MAX_K_LIST} (REART_MAX_K_LIST)")
     l1 = _as_len(lengths1, N, P1, p1.device)
     l2 = _as_len(lengths2, N, P2, p1.device)
     dists = torch.empty((N, P1, K), dtype=torch.float32, device=p1.device)

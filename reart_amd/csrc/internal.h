@@ -147,6 +147,12 @@ struct KnnArgs {
 int reart_knn_launch_slices(const KnnArgs &a, int KK, hipStream_t st);
 int reart_soa_launch(const SoaArgs &sa, int maxPpad, int N, int njobs, hipStream_t st);
 int reart_knn_pick_split(long waves, int P2, int K);
+
+// ---- K-NN for REART_MAX_K < K <= REART_MAX_K_LIST (knn_list.hip) ---------------------------
+size_t reart_knn_list_workspace_bytes(int N, int P1, int P2, int K);
+int reart_knn_list_run(const float *q, const float *t, const int64_t *lenq, const int64_t *lent, int N, int P1,
+                       int P2, int K, int euclidean, float *dists, int64_t *idx, void *workspace,
+                       size_t workspace_bytes, hipStream_t st);
 #ifndef NN_BOX
 #define NN_BOX 16   // targets per bounding box of the block-skip test (16, 32 or 64; measured 4545 / 4438 / 4321 it/s)
 #endif

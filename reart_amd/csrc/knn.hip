@@ -445,6 +445,7 @@ int reart_knn_run(int njobs, const float *const *q, const float *const *t,
 }
 
 extern "C" size_t reart_knn_points_workspace_bytes(int N, int P1, int P2, int K) {
+    if (K > REART_MAX_K) return reart_knn_list_workspace_bytes(N, P1, P2, K);
     KnnPlan pl;
     if (N <= 0 || P1 <= 0 || P2 <= 0 || knn_plan(1, N, &P1, &P2, K, &pl) != REART_OK) return 0;
     return pl.total;
@@ -462,7 +463,7 @@ extern "C" int reart_knn_points_idx(const float *p1, const float *p2, const int6
                                     float *dists, int64_t *idx, void *workspace,
                                     size_t workspace_bytes, void *stream) {
     if (N < 0 || P1 < 0 || P2 < 0 || K < 1) return REART_ERR_INVALID_ARG;
-    if (D != 3 || K > REART_MAX_K) return REART_ERR_UNSUPPORTED;
+    if (D != 3 || K > REART_MAX_K_LIST) return REART_ERR_UNSUPPORTED;
     if (N == 0 || P1 == 0) return REART_OK;
     if (!dists || !idx) return REART_ERR_INVALID_ARG;
     hipStream_t st = (hipStream_t)stream;
@@ -473,6 +474,8 @@ extern "C" int reart_knn_points_idx(const float *p1, const float *p2, const int6
         return REART_OK;
     }
     if (!p1 || !p2) return REART_ERR_INVALID_ARG;
+    if (K > REART_MAX_K)
+        return reart_knn_list_run(p1, p2, lengths1, lengths2, N, P1, P2, K, 0, dists, idx, workspace, workspace_bytes, st);
     const int64_t *lq[1] = {lengths1}, *lt[1] = {lengths2};
     return reart_knn_run(1, &p1, &p2, lq, lt, N, &P1, &P2, K, 0, &dists, &idx, workspace, workspace_bytes, st);
 }
@@ -495,10 +498,13 @@ extern "C" int reart_knn_cuda(const float *ref, const float *query, int B, int n
                               int k, int euclidean, float *dist, int64_t *idx, void *workspace,
                               size_t workspace_bytes, void *stream) {
     if (B < 0 || nr < 0 || nq < 0 || k < 1) return REART_ERR_INVALID_ARG;
-    if (D != 3 || k > REART_MAX_K) return REART_ERR_UNSUPPORTED;
+    if (D != 3 || k > REART_MAX_K_LIST) return REART_ERR_UNSUPPORTED;
     if (k > nr) return REART_ERR_INVALID_ARG;  // knn_cuda asserts k <= number of references
     if (B == 0 || nq == 0) return REART_OK;
     if (!ref || !query || !dist || !idx) return REART_ERR_INVALID_ARG;
+    if (k > REART_MAX_K)
+        return reart_knn_list_run(query, ref, nullptr, nullptr, B, nq, nr, k, euclidean ? 1 : 0, dist, idx, workspace,
+                                  workspace_bytes, (hipStream_t)stream);
     return reart_knn_run(1, &query, &ref, nullptr, nullptr, B, &nq, &nr, k, euclidean ? 1 : 0, &dist, &idx,
                    workspace, workspace_bytes, (hipStream_t)stream);
 }

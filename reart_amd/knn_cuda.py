@@ -6,7 +6,8 @@ Call sites and shape contract: ``run_robot.py:65-66,122,138``, ``utils/model_uti
 ``utils/flow_utils.py:127`` (``transpose_mode=False``: [b,dim,n] -> [b,k,nq]).
 Distances are Euclidean (sqrt of the squared distance) like upstream KNN_CUDA 0.2; pass
 ``squared=True`` to get squared distances (the reference is silent on this).
-No gradient flows through it.
+No gradient flows through it.  ``k`` may be at most 1024 (REART_MAX_K_LIST; larger raises
+NotImplementedError) and at most the number of reference points.
 """
 import torch
 
@@ -29,6 +30,8 @@ class KNN(torch.nn.Module):
         ref, query = ref.contiguous().float(), query.contiguous().float()
         B, nr, D = ref.shape
         nq = query.shape[1]
+        if self.k > _lib.MAX_K_LIST:
+            raise NotImplementedError(f"KNN: k = {self.k} > {_lib.MAX_K_LIST} (REART_MAX_K_LIST)")
         dist = torch.empty((B, nq, self.k), dtype=torch.float32, device=ref.device)
         idx = torch.empty((B, nq, self.k), dtype=torch.int64, device=ref.device)
         L = _lib.lib()

@@ -35,18 +35,29 @@ def farthest_point_sample(xyz, npoint, start=None, cuda_mode=None):
 
     ``start`` [B]: first index of every cloud.  The reference's CPU fallback draws it with
     ``torch.randint`` from the global generator (:90) -- reproduced here when ``start`` is None and
-    ``cuda_mode`` is False; its CUDA kernel always starts at 0 (sampling_gpu.cu:113)."""
+    ``cuda_mode`` is False; its CUDA kernel always starts at 0 (sampling_gpu.cu:113).
+
+    N <= 12 288 runs ``reart_fps`` (cloud in LDS), larger clouds up to 2^21 points ``reart_fps_temp`` with a
+    [B,N] distance buffer allocated here; N > 2^21 raises NotImplementedError."""
     _lib.require_gpu(xyz)
     cuda_mode = _rules(cuda_mode)
     xyz = xyz.contiguous().float()
     B, N, _ = xyz.shape
+    if N > _lib.FPS_MAX_N:
+        raise NotImplementedError(f"farthest_point_sample: N = {N} > {_lib.FPS_MAX_N} points (REART_FPS_MAX_N)")
     if start is None and not cuda_mode:
         start = torch.randint(0, N, (B,), dtype=torch.long, device=xyz.device)
     st = None if start is None else start.to(device=xyz.device, dtype=torch.int32).contiguous()
     idx = torch.empty((B, npoint), dtype=torch.int64, device=xyz.device)
-    rc = _lib.lib().reart_fps(_lib.ptr(xyz), B, N, npoint, _lib.ptr(st), int(bool(cuda_mode)), None, _lib.ptr(idx),
-                              _lib.stream())
-    _lib.check(rc, "reart_fps")
+    if N <= _lib.FPS_MAX_N_LDS:
+        rc = _lib.lib().reart_fps(_lib.ptr(xyz), B, N, npoint, _lib.ptr(st), int(bool(cuda_mode)), None, _lib.ptr(idx),
+                                  _lib.stream())
+        _lib.check(rc, "reart_fps")
+        return idx
+    temp = torch.empty((B, N), dtype=torch.float32, device=xyz.device)   # running minima beyond the registers
+    rc = _lib.lib().reart_fps_temp(_lib.ptr(xyz), B, N, npoint, _lib.ptr(st), int(bool(cuda_mode)), _lib.ptr(temp),
+                                   None, _lib.ptr(idx), _lib.stream())
+    _lib.check(rc, "reart_fps_temp")
     return idx
 
 

@@ -3,19 +3,36 @@ ten wrappers, same argument order, caller-allocated outputs.  The reference itse
 (``furthest_point_sampling_wrapper`` from ``pointnet_lib/pointnet2_utils.py:29``, ``ball_query_wrapper`` from ``:263``); the other
 eight are reachable only from ``pointnet2_modules.py``, which nothing in the reference imports -- they are here so
 that the module is whole: ``three_nn_wrapper`` / ``knn_wrapper`` on the K-nearest search that exists (direct-difference squared
-distance, ascending scan, ties keep the lower index: ``reart_knn_points_idx``, K <= 16), the channel-major gather / group /
+distance, ascending scan, ties keep the lower index: ``reart_knn_points_idx``; ``knn_wrapper`` keeps k <= 16 while
+``knn_points`` / ``KNN`` reach k = 1024), the channel-major gather / group /
 interpolate operators and their backward forms on ``reart_pn2_*`` (csrc/pointnet.hip).  Their parity is against
 restatements of the CUDA kernels in ``oracle/`` (the reference's kernels cannot run here and hold no golden vectors: parity
-unpinned for these eight).
+unpinned for these eight).  ``furthest_point_sampling_wrapper`` samples clouds of up to 2^21 points: the
+LDS-resident kernel up to 12 288, above that the kernel that keeps running minima in the caller's ``temp_tensor``.
 """
+import torch
+
 from . import _lib
 
 
 def furthest_point_sampling_wrapper(b, n, m, points_tensor, temp_tensor, idx_tensor):
-    """points f32 [B,N,3], temp f32 [B,N] (unused: distances live in registers), idx i32 [B,M]."""
-    _lib.require_gpu(points_tensor, idx_tensor)
-    rc = _lib.lib().reart_fps(_lib.ptr(points_tensor), b, n, m, None, 1, _lib.ptr(idx_tensor), None, _lib.stream())
-    _lib.check(rc, "reart_fps")
+    """points f32 [B,N,3], temp f32 [B,N], idx i32 [B,M].  N <= 12 288: ``reart_fps`` (cloud in LDS, ``temp`` unused);
+    up to 2^21 points: ``reart_fps_temp``, which keeps running minima in ``temp`` (initialised by the kernel, the caller's
+    contents are never read); above that NotImplementedError."""
+    if n > _lib.FPS_MAX_N:
+        raise NotImplementedError(f"furthest_point_sampling_wrapper: n = {n} > {_lib.FPS_MAX_N} points (REART_FPS_MAX_N)")
+    if n <= _lib.FPS_MAX_N_LDS:
+        _lib.require_gpu(points_tensor, idx_tensor)
+        rc = _lib.lib().reart_fps(_lib.ptr(points_tensor), b, n, m, None, 1, _lib.ptr(idx_tensor), None, _lib.stream())
+        _lib.check(rc, "reart_fps")
+        return 1
+    _lib.require_gpu(points_tensor, temp_tensor, idx_tensor)
+    _contig(points_tensor, temp_tensor, idx_tensor)
+    if temp_tensor.dtype != torch.float32 or temp_tensor.numel() < b * n:
+        raise RuntimeError("temp_tensor must be float32 [B,N]")
+    rc = _lib.lib().reart_fps_temp(_lib.ptr(points_tensor), b, n, m, None, 1, _lib.ptr(temp_tensor),
+                                   _lib.ptr(idx_tensor), None, _lib.stream())
+    _lib.check(rc, "reart_fps_temp")
     return 1
 
 
@@ -46,7 +63,8 @@ def three_nn_wrapper(b, n, m, unknown_tensor, known_tensor, dist2_tensor, idx_te
 def knn_wrapper(b, n, m, k, unknown_tensor, known_tensor, dist2_tensor, idx_tensor):
     """interpolate.cpp:27-37 / interpolate_gpu.cu:9-58: unknown f32 [B,N,3], known f32 [B,M,3] -> dist2 f32 [B,N,k], idx i32
     [B,N,k], the k nearest by the same squared distance, insertion-sorted ascending with strict `<` (ties keep the lower
-    index).  k <= 16 here (the kernel's register list; the reference's bound is its 200-entry local array)."""
+    index).  k <= 16 here (the kernel's register list; the reference's bound is its 200-entry local array); the same
+    search for k up to 1024 is ``chamferdist_C.knn_points_idx`` / ``utils.chamfer.knn_points`` / ``knn_cuda.KNN``."""
     from .chamferdist_C import knn_points_idx
 
     if k > 16:
