@@ -32,7 +32,7 @@ extern "C" {
 typedef enum {
     REART_OK = 0,
     REART_ERR_INVALID_ARG = -1,   /* null pointer, negative size, bad enum      */
-    REART_ERR_UNSUPPORTED = -2,   /* e.g. D != 3, K > REART_MAX_K_LIST           */
+    REART_ERR_UNSUPPORTED = -2,   /* e.g. D > REART_MAX_D, K > REART_MAX_K_LIST  */
     REART_ERR_LAUNCH = -3,        /* hipGetLastError() after a launch            */
     REART_ERR_NO_DEVICE = -4      /* no HIP device visible                       */
 } reart_status;
@@ -41,6 +41,8 @@ typedef enum {
 #define REART_MAX_K_LIST 1024     /* K-NN searches with K > REART_MAX_K keep a    */
                                   /* sorted key list per query in LDS (one wave   */
                                   /* per query); above this they are unsupported  */
+#define REART_MAX_D 256           /* point dimension of the K-NN searches and     */
+                                  /* their backward: 1 <= D <= REART_MAX_D        */
 
 /* Library / device probes (host side, no device work). */
 int reart_version(void);                       /* 100*major + minor              */
@@ -53,15 +55,19 @@ const char *reart_status_string(int status);
 
 /* Replaces chamferdist._C.knn_points_idx(p1,p2,lengths1,lengths2,K,version)
  * (utils/chamfer.py:174; contract in the docstring :145-171).
- *   p1 [N,P1,3], p2 [N,P2,3] f32 contiguous; lengths1/2 [N] i64 or NULL (= full);
+ *   p1 [N,P1,D], p2 [N,P2,D] f32 contiguous, 1 <= D <= REART_MAX_D (D = 0: invalid
+ *   argument, D > REART_MAX_D: unsupported); lengths1/2 [N] i64 or NULL (= full);
  *   dists [N,P1,K] f32 squared L2, idx [N,P1,K] i64 into p2, ascending by
  *   (distance, index); rows >= lengths1[n] and slots >= lengths2[n] are zero.
- * Distance contract: ((dx*dx)+(dy*dy))+(dz*dz) in fp32, no FMA, ties -> lowest j.
- * 1 <= K <= REART_MAX_K_LIST; K <= REART_MAX_K runs the register-list kernels, larger K
- * the LDS-list kernel (same result contract).
- * workspace (SoA target image + per-slice partial results):
- *   reart_knn_points_workspace_bytes(N,P1,P2,K) bytes (0 when K is out of range). */
+ * Distance contract: ((d0*d0)+(d1*d1))+(d2*d2)+... with dc = p1[c]-p2[c], summed in
+ * ascending c, fp32, no FMA; ties -> lowest j.
+ * 1 <= K <= REART_MAX_K_LIST.  D = 3: K <= REART_MAX_K runs the register-list kernels,
+ * larger K the LDS-list kernel; D != 3: the any-D LDS-list kernel (same result contract).
+ * workspace (SoA target image + per-slice partial results; D != 3 also a query image):
+ *   reart_knn_points_workspace_bytes_d(N,P1,P2,D,K) bytes (0 when D or K is out of range);
+ *   reart_knn_points_workspace_bytes(N,P1,P2,K) is the D = 3 size. */
 size_t reart_knn_points_workspace_bytes(int N, int P1, int P2, int K);
+size_t reart_knn_points_workspace_bytes_d(int N, int P1, int P2, int D, int K);
 int reart_knn_points_idx(const float *p1, const float *p2,
                          const int64_t *lengths1, const int64_t *lengths2,
                          int N, int P1, int P2, int D, int K,
@@ -69,10 +75,12 @@ int reart_knn_points_idx(const float *p1, const float *p2,
                          void *workspace, size_t workspace_bytes, void *stream);
 
 /* Replaces chamferdist._C.knn_points_backward(p1,p2,lengths1,lengths2,idx,grad_dists)
- * (utils/chamfer.py:206-208).  grad_p1 [N,P1,3], grad_p2 [N,P2,3] are fully
- * written (zero where nothing contributes).  Deterministic: the scatter into
- * grad_p2 is a per-target gather over a counting sort of idx, summed in
- * ascending (i,k) order -- no float atomics.
+ * (utils/chamfer.py:206-208).  p1 [N,P1,D], p2 [N,P2,D], 1 <= D <= REART_MAX_D;
+ * grad_p1 [N,P1,D], grad_p2 [N,P2,D] are fully written (zero where nothing
+ * contributes).  Deterministic: the scatter into grad_p2 is a per-target gather
+ * over a counting sort of idx, summed in ascending (i,k) order with
+ * v = (2g)*diff, g1 += v, g2 -= v -- no float atomics.  The workspace does not
+ * depend on D.
  *   workspace: reart_knn_points_backward_workspace_bytes(N,P1,P2,K) bytes. */
 size_t reart_knn_points_backward_workspace_bytes(int N, int P1, int P2, int K);
 int reart_knn_points_backward(const float *p1, const float *p2,
@@ -92,10 +100,11 @@ int reart_chamfer_bidir(const float *x, const float *y, int N, int P,
 
 /* Replaces knn_cuda.KNN(k, transpose_mode=True).forward(ref, query)
  * (run_robot.py:65-66,122; shape contract utils/model_utils.py:42):
- *   ref [B,nr,3], query [B,nq,3] -> dist [B,nq,k] ascending, idx [B,nq,k] i64.
+ *   ref [B,nr,D], query [B,nq,D] -> dist [B,nq,k] ascending, idx [B,nq,k] i64,
+ *   1 <= D <= REART_MAX_D (distance contract of reart_knn_points_idx).
  * euclidean != 0: dist = sqrt(squared distance) (upstream KNN_CUDA 0.2).
  * 1 <= k <= min(nr, REART_MAX_K_LIST).
- * workspace: reart_knn_points_workspace_bytes(B, nq, nr, k). */
+ * workspace: reart_knn_points_workspace_bytes_d(B, nq, nr, D, k). */
 int reart_knn_cuda(const float *ref, const float *query, int B, int nr, int nq,
                    int D, int k, int euclidean, float *dist, int64_t *idx,
                    void *workspace, size_t workspace_bytes, void *stream);

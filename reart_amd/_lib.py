@@ -19,6 +19,7 @@ P = c_void_p  # every device pointer
 # size limits of include/reart_hip.h, checked before a call so that they surface as NotImplementedError
 MAX_K = 16               # REART_MAX_K: K-NN list in registers
 MAX_K_LIST = 1024        # REART_MAX_K_LIST: K-NN list in LDS, the largest K of any search
+MAX_D = 256              # REART_MAX_D: point dimension of the K-NN searches and their backward
 FPS_MAX_N_LDS = 12288    # REART_FPS_MAX_N_LDS: reart_fps, cloud staged in LDS
 FPS_MAX_N = 1 << 21      # REART_FPS_MAX_N: reart_fps_temp, 21-bit index in the tie key
 
@@ -28,6 +29,7 @@ PROTOTYPES = {
     "reart_device_count": (c_int, []),
     "reart_status_string": (ctypes.c_char_p, [c_int]),
     "reart_knn_points_workspace_bytes": (c_size_t, [c_int] * 4),
+    "reart_knn_points_workspace_bytes_d": (c_size_t, [c_int] * 5),
     "reart_knn_points_idx": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, c_size_t, P]),
     "reart_knn_points_backward_workspace_bytes": (c_size_t, [c_int] * 4),
     "reart_knn_points_backward": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, c_size_t, P]),

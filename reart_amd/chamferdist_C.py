@@ -18,11 +18,17 @@ def _as_len(lengths, n, full, device):
     return lengths.contiguous()
 
 
+def _check_dim(what, D):
+    if D > _lib.MAX_D:
+        raise NotImplementedError(f"{what}: D = {D} > {_lib.MAX_D} (REART_MAX_D)")
+
+
 def knn_points_idx(p1, p2, lengths1, lengths2, K, version=-1):
     """-> (idx int64 [N,P1,K], dists float32 [N,P1,K] squared L2), cf. utils/chamfer.py:174.
 
-    1 <= K <= 1024: K <= 16 keeps each query's list in registers, larger K in LDS (same result, bit for bit);
-    K > 1024 raises NotImplementedError."""
+    p1 [N,P1,D], p2 [N,P2,D] with 1 <= D <= 256 (REART_MAX_D); D > 256 raises NotImplementedError.
+    1 <= K <= 1024: at D = 3, K <= 16 keeps each query's list in registers, larger K in LDS; other D keep it in
+    LDS (same result, bit for bit); K > 1024 raises NotImplementedError."""
     _lib.require_gpu(p1, p2, lengths1, lengths2)
     if p1.dtype != torch.float32 or p2.dtype != torch.float32:
         raise TypeError("knn_points_idx expects float32 point clouds")
@@ -31,12 +37,13 @@ def knn_points_idx(p1, p2, lengths1, lengths2, K, version=-1):
     P2 = p2.shape[1]
     if K > _lib.MAX_K_LIST:
         raise NotImplementedError(f"knn_points_idx: K = {K} > {_lib.MAX_K_LIST} (REART_MAX_K_LIST)")
+    _check_dim("knn_points_idx", D)
     l1 = _as_len(lengths1, N, P1, p1.device)
     l2 = _as_len(lengths2, N, P2, p1.device)
     dists = torch.empty((N, P1, K), dtype=torch.float32, device=p1.device)
     idx = torch.empty((N, P1, K), dtype=torch.int64, device=p1.device)
     L = _lib.lib()
-    nbytes = L.reart_knn_points_workspace_bytes(N, P1, P2, K)
+    nbytes = L.reart_knn_points_workspace_bytes_d(N, P1, P2, D, K)
     ws = _lib.workspace(nbytes, p1.device)
     rc = L.reart_knn_points_idx(_lib.ptr(p1), _lib.ptr(p2), _lib.ptr(l1), _lib.ptr(l2), N, P1, P2, D, K,
                                 _lib.ptr(dists), _lib.ptr(idx), _lib.ptr(ws), ws.numel(), _lib.stream())
@@ -45,11 +52,12 @@ def knn_points_idx(p1, p2, lengths1, lengths2, K, version=-1):
 
 
 def knn_points_backward(p1, p2, lengths1, lengths2, idx, grad_dists):
-    """-> (grad_p1, grad_p2), cf. utils/chamfer.py:206-208."""
+    """-> (grad_p1 [N,P1,D], grad_p2 [N,P2,D]), cf. utils/chamfer.py:206-208; 1 <= D <= 256 (REART_MAX_D)."""
     _lib.require_gpu(p1, p2, idx, grad_dists)
     p1, p2 = p1.contiguous(), p2.contiguous()
     idx, grad_dists = idx.contiguous(), grad_dists.contiguous()
     N, P1, D = p1.shape
+    _check_dim("knn_points_backward", D)
     P2 = p2.shape[1]
     K = idx.shape[2]
     l1 = _as_len(lengths1, N, P1, p1.device)

@@ -2,6 +2,7 @@
 //
 // Replaces chamferdist._C.knn_points_idx / knn_points_backward (reference
 // utils/chamfer.py:174,206-208) and knn_cuda.KNN.forward (run_robot.py:65-66).
+// These kernels serve D = 3; the entry points send other D to knn_dim.hip.
 //
 // Design (DESIGN.md section "K-NN"):
 //   * The kernel is fp32-VALU bound (8 flop per pair against 24 B per point), so the
@@ -462,8 +463,8 @@ extern "C" int reart_knn_points_idx(const float *p1, const float *p2, const int6
                                     const int64_t *lengths2, int N, int P1, int P2, int D, int K,
                                     float *dists, int64_t *idx, void *workspace,
                                     size_t workspace_bytes, void *stream) {
-    if (N < 0 || P1 < 0 || P2 < 0 || K < 1) return REART_ERR_INVALID_ARG;
-    if (D != 3 || K > REART_MAX_K_LIST) return REART_ERR_UNSUPPORTED;
+    if (N < 0 || P1 < 0 || P2 < 0 || K < 1 || D < 1) return REART_ERR_INVALID_ARG;
+    if (D > REART_MAX_D || K > REART_MAX_K_LIST) return REART_ERR_UNSUPPORTED;
     if (N == 0 || P1 == 0) return REART_OK;
     if (!dists || !idx) return REART_ERR_INVALID_ARG;
     hipStream_t st = (hipStream_t)stream;
@@ -474,6 +475,8 @@ extern "C" int reart_knn_points_idx(const float *p1, const float *p2, const int6
         return REART_OK;
     }
     if (!p1 || !p2) return REART_ERR_INVALID_ARG;
+    if (D != 3)
+        return reart_knn_dim_run(p1, p2, lengths1, lengths2, N, P1, P2, D, K, 0, dists, idx, workspace, workspace_bytes, st);
     if (K > REART_MAX_K)
         return reart_knn_list_run(p1, p2, lengths1, lengths2, N, P1, P2, K, 0, dists, idx, workspace, workspace_bytes, st);
     const int64_t *lq[1] = {lengths1}, *lt[1] = {lengths2};
@@ -497,11 +500,14 @@ extern "C" int reart_chamfer_bidir(const float *x, const float *y, int N, int P,
 extern "C" int reart_knn_cuda(const float *ref, const float *query, int B, int nr, int nq, int D,
                               int k, int euclidean, float *dist, int64_t *idx, void *workspace,
                               size_t workspace_bytes, void *stream) {
-    if (B < 0 || nr < 0 || nq < 0 || k < 1) return REART_ERR_INVALID_ARG;
-    if (D != 3 || k > REART_MAX_K_LIST) return REART_ERR_UNSUPPORTED;
+    if (B < 0 || nr < 0 || nq < 0 || k < 1 || D < 1) return REART_ERR_INVALID_ARG;
+    if (D > REART_MAX_D || k > REART_MAX_K_LIST) return REART_ERR_UNSUPPORTED;
     if (k > nr) return REART_ERR_INVALID_ARG;  // knn_cuda asserts k <= number of references
     if (B == 0 || nq == 0) return REART_OK;
     if (!ref || !query || !dist || !idx) return REART_ERR_INVALID_ARG;
+    if (D != 3)
+        return reart_knn_dim_run(query, ref, nullptr, nullptr, B, nq, nr, D, k, euclidean ? 1 : 0, dist, idx, workspace,
+                                 workspace_bytes, (hipStream_t)stream);
     if (k > REART_MAX_K)
         return reart_knn_list_run(query, ref, nullptr, nullptr, B, nq, nr, k, euclidean ? 1 : 0, dist, idx, workspace,
                                   workspace_bytes, (hipStream_t)stream);
@@ -596,14 +602,14 @@ extern "C" int reart_knn_points_backward(const float *p1, const float *p2, const
                                          const float *grad_dists, int N, int P1, int P2, int D,
                                          int K, float *grad_p1, float *grad_p2, void *workspace,
                                          size_t workspace_bytes, void *stream) {
-    if (N < 0 || P1 < 0 || P2 < 0 || K < 1) return REART_ERR_INVALID_ARG;
-    if (D != 3) return REART_ERR_UNSUPPORTED;
+    if (N < 0 || P1 < 0 || P2 < 0 || K < 1 || D < 1) return REART_ERR_INVALID_ARG;
+    if (D > REART_MAX_D) return REART_ERR_UNSUPPORTED;
     if (N == 0) return REART_OK;
     hipStream_t st = (hipStream_t)stream;
     if (P1 == 0 || P2 == 0) {
-        if (P1 && hipMemsetAsync(grad_p1, 0, sizeof(float) * (size_t)N * P1 * 3, st) != hipSuccess)
+        if (P1 && hipMemsetAsync(grad_p1, 0, sizeof(float) * (size_t)N * P1 * D, st) != hipSuccess)
             return REART_ERR_LAUNCH;
-        if (P2 && hipMemsetAsync(grad_p2, 0, sizeof(float) * (size_t)N * P2 * 3, st) != hipSuccess)
+        if (P2 && hipMemsetAsync(grad_p2, 0, sizeof(float) * (size_t)N * P2 * D, st) != hipSuccess)
             return REART_ERR_LAUNCH;
         return REART_OK;
     }
@@ -611,6 +617,9 @@ extern "C" int reart_knn_points_backward(const float *p1, const float *p2, const
         return REART_ERR_INVALID_ARG;
     if (workspace_bytes < reart_knn_points_backward_workspace_bytes(N, P1, P2, K))
         return REART_ERR_INVALID_ARG;
+    if (D != 3)
+        return reart_knn_dim_backward_launch(p1, p2, lengths1, lengths2, idx, grad_dists, N, P1, P2, D, K, grad_p1,
+                                             grad_p2, (int *)workspace, st);
     hipLaunchKernelGGL(knn_bwd_kernel, dim3(N), dim3(BWD_BS), 0, st, p1, p2, lengths1, lengths2, idx,
                        grad_dists, P1, P2, K, reart_bits_for(P2), grad_p1, grad_p2, (int *)workspace);
     REART_CHECK_LAUNCH();

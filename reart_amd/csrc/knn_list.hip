@@ -5,24 +5,20 @@
 //
 // Design:
 //   * One wave per query, four queries per workgroup.  The query's K best targets so far are a sorted
-//     list of K 64-bit keys in LDS, key = (bits of the fp32 distance) << 32 | j.  Distances are >= +0, so
-//     integer order is (distance, index) order and every key is distinct.
+//     list of K 64-bit keys in LDS, key = (bits of the fp32 distance) << 32 | j (knn_keys.h).
 //   * Targets stream 64 per step in ascending j from the SoA image soa_kernel builds (one coalesced load
 //     per coordinate).  A lane's target is a candidate when its key is below the list's K-th key, which
 //     every lane reads from the same LDS word.  A step without candidates costs one ballot; otherwise the
-//     wave sorts its <= 64 candidates (bitonic, across lanes) and merges them into the list: every
-//     candidate and every list entry finds its new slot by counting the other side's smaller keys
-//     (binary searches), and entries pushed past K fall off.
+//     wave sorts its <= 64 candidates (bitonic, across lanes) and merges them into the list (kl_merge).
 //   * Rounding contract as knn.hip: d = ((dx*dx)+(dy*dy))+(dz*dz), fp32, no FMA (-ffp-contract=off).
 //     The result is the list order, so it does not depend on scheduling: no atomics, no cross-wave state.
 #include "common.h"
 #include "internal.h"
+#include "knn_keys.h"
 #include <math.h>
 
 #define KL_BS 256                     // four waves, four queries per workgroup
 #define KL_WAVES (KL_BS / 64)
-
-typedef unsigned long long u64;
 
 struct KnnListArgs {
     const float *q;                   // [N,P1,3] queries
@@ -32,42 +28,6 @@ struct KnnListArgs {
     float *dists;                     // [N,P1,K]
     int64_t *idx;                     // [N,P1,K]
 };
-
-// the wave's LDS accesses before this point are complete, and the compiler moves none across it
-__device__ __forceinline__ void kl_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ u64 kl_shfl_xor(u64 v, int m) {
-    const int lo = __shfl_xor((int)(unsigned)v, m, 64), hi = __shfl_xor((int)(unsigned)(v >> 32), m, 64);
-    return ((u64)(unsigned)hi << 32) | (unsigned)lo;
-}
-
-// ascending across the 64 lanes (bitonic network)
-__device__ __forceinline__ u64 kl_sort64(u64 v, int lane) {
-#pragma unroll
-    for (int k = 2; k <= 64; k <<= 1) {
-#pragma unroll
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            const u64 o = kl_shfl_xor(v, j);
-            const bool keep_min = ((lane & j) == 0) == ((lane & k) == 0);
-            v = keep_min ? (o < v ? o : v) : (o > v ? o : v);
-        }
-    }
-    return v;
-}
-
-// number of entries of the ascending array a[0..n) below v
-__device__ __forceinline__ int kl_count_below(const u64 *a, int n, u64 v) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (a[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
 
 // NE = list entries per lane (K <= 64 * NE)
 template <int NE>
@@ -107,23 +67,7 @@ __global__ __launch_bounds__(KL_BS) void knn_list_kernel(KnnListArgs a) {
         if (!m) continue;
         const int c = __popcll(m);
         const u64 v = kl_sort64(acc ? key : ~0ull, lane);   // candidates in lanes [0, c)
-        cand[lane] = v;
-        u64 old[NE];
-#pragma unroll
-        for (int u = 0; u < NE; ++u) old[u] = (lane + 64 * u < K) ? lst[lane + 64 * u] : ~0ull;
-        kl_wave_sync();
-        // new slots: a candidate moves up by the list entries below it, an entry by the candidates below it
-        const int cpos = lane < c ? lane + kl_count_below(lst, K, v) : K;
-        int npos[NE];
-#pragma unroll
-        for (int u = 0; u < NE; ++u) npos[u] = lane + 64 * u + kl_count_below(cand, c, old[u]);
-        kl_wave_sync();
-#pragma unroll
-        for (int u = 0; u < NE; ++u)
-            if (lane + 64 * u < K && npos[u] < K) lst[npos[u]] = old[u];
-        if (cpos < K) lst[cpos] = v;
-        kl_wave_sync();
-        thr = lst[K - 1];
+        thr = kl_merge<NE>(lst, cand, K, v, c, lane);
     }
 
     const int valid = K < n2 ? K : n2;

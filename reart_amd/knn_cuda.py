@@ -7,7 +7,8 @@ Call sites and shape contract: ``run_robot.py:65-66,122,138``, ``utils/model_uti
 Distances are Euclidean (sqrt of the squared distance) like upstream KNN_CUDA 0.2; pass
 ``squared=True`` to get squared distances (the reference is silent on this).
 No gradient flows through it.  ``k`` may be at most 1024 (REART_MAX_K_LIST; larger raises
-NotImplementedError) and at most the number of reference points.
+NotImplementedError) and at most the number of reference points.  ``dim`` may be anything from 1 to 256
+(REART_MAX_D; larger raises NotImplementedError), e.g. the 64-D descriptors of ``utils/flow_utils.py:127``.
 """
 import torch
 
@@ -32,10 +33,12 @@ class KNN(torch.nn.Module):
         nq = query.shape[1]
         if self.k > _lib.MAX_K_LIST:
             raise NotImplementedError(f"KNN: k = {self.k} > {_lib.MAX_K_LIST} (REART_MAX_K_LIST)")
+        if D > _lib.MAX_D:
+            raise NotImplementedError(f"KNN: dim = {D} > {_lib.MAX_D} (REART_MAX_D)")
         dist = torch.empty((B, nq, self.k), dtype=torch.float32, device=ref.device)
         idx = torch.empty((B, nq, self.k), dtype=torch.int64, device=ref.device)
         L = _lib.lib()
-        ws = _lib.workspace(L.reart_knn_points_workspace_bytes(B, nq, nr, self.k), ref.device)
+        ws = _lib.workspace(L.reart_knn_points_workspace_bytes_d(B, nq, nr, D, self.k), ref.device)
         rc = L.reart_knn_cuda(_lib.ptr(ref), _lib.ptr(query), B, nr, nq, D, self.k, 0 if self._squared else 1,
                               _lib.ptr(dist), _lib.ptr(idx), _lib.ptr(ws), ws.numel(), _lib.stream())
         _lib.check(rc, "reart_knn_cuda")

@@ -43,6 +43,7 @@ class _knn_points(Function):
 def knn_points(p1, p2, lengths1=None, lengths2=None, K=1, version=-1, return_nn=False, return_sorted=True):
     """K nearest neighbours of every p1 point in p2 (utils/chamfer.py:212-286).
 
+    p1 [N,P1,D], p2 [N,P2,D] with 1 <= D <= 256 and 1 <= K <= 1024 (above: NotImplementedError).
     Returns the namedtuple ``(dists [N,P1,K] squared, idx [N,P1,K] int64, knn or None)``.
     """
     if p1.shape[0] != p2.shape[0]:
@@ -77,7 +78,7 @@ def knn_gather(x, idx, lengths=None):
 
 
 class ChamferDistance(torch.nn.Module):
-    """Per-point (un-reduced) Chamfer distance, cf. utils/chamfer.py:19-132.
+    """Per-point (un-reduced) Chamfer distance, cf. utils/chamfer.py:19-132, for clouds of any dimension D <= 256.
 
     ``reduction`` is validated and then ignored, exactly like the reference (its reduction
     block is commented out, utils/chamfer.py:104-117): the result has shape [B, P].
