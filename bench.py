@@ -11,6 +11,10 @@ forward with fresh Gumbel noise, bidirectional Chamfer, 19 k=3 flow blends + flo
 Adam -- nothing skipped, inputs resident in HBM, replayed from a captured graph.  Multi-GPU is the
 reference's natural sharding: independent (sequence, cano_idx) instances, one per rank, no
 data-path collective; only the final energies are gathered (RCCL all_gather).  Prints ONE JSON line.
+
+A plain run does only what that line's headline needs: set-up, warm-up, the timed steps, --dump-outputs.  `--full` adds
+everything else the line can carry, each measured in runs of its own after the timed steps: the sweep of concurrent
+instances, per-phase times, the launch-chain floor, the CPU baselines, the end-of-run figures and the `secondary` legs.
 """
 import argparse
 import json
@@ -889,30 +893,35 @@ def main():
                          "host interaction, so several iterations replay as one graph)")
     ap.add_argument("--no-overlap", action="store_true", help="only affects the non-default search paths (brute force / grid): run their flow branch serially instead of on a second stream")
     ap.add_argument("--grid", action="store_true", help="exact grid search for the static targets (same results; slower at this size)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the kinematic / extractor figures appended to the default line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baselines (relax: they run only with --full)")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the kinematic / extractor / nao figures appended to the line")
     ap.add_argument("--instances-per-gpu", type=int, default=1,
                     help="sweep mode: K independent instances share each GPU on separate streams (secondary figure; "
                          "the headline is K=1)")
-    ap.add_argument("--no-tail", action="store_true", help="skip the end-of-run structure / energy timing (secondary figure)")
+    ap.add_argument("--no-tail", action="store_true", help="--full: skip the end-of-run structure / energy timing (secondary figure)")
     ap.add_argument("--sweep-mode", choices=("batch", "streams"), default="batch",
                     help="how the sweep's instances share a GPU: batch = shared launches (reart_relax_step_batch), streams = one "
                          "stream per instance")
     ap.add_argument("--sweep-instances", type=int, default=6,
-                    help="after the headline (one instance per GPU) also time this many concurrent instances per GPU "
+                    help="--full: after the headline (one instance per GPU) also time this many concurrent instances per GPU "
                          "(--sweep-mode) and report the aggregate as `sweep` (0 = skip)")
-    ap.add_argument("--profile-steps", type=int, default=20, help="eager steps timed per phase with HIP events")
+    ap.add_argument("--profile-steps", type=int, default=20, help="--full: eager steps timed per phase with HIP events")
     ap.add_argument("--deterministic", dest="deterministic", action="store_true", default=True,
                     help="(default, as in run_robot.py) assignment-bound configs: tied optima settled canonically")
     ap.add_argument("--no-deterministic", dest="deterministic", action="store_false")
     ap.add_argument("--one-mode", action="store_true", help="nao_projection: do not repeat the bounded sample in the other mode")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="relax: after the timed steps write what the last one computed (rank 0, first instance) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="relax: after the headline also measure what it does not need -- the sweep, per-phase times, the launch-chain "
+                         "floor, the CPU baselines, the end-of-run figures and the `secondary` legs (each still subject to its own "
+                         "option above).  Without it a run sets up, warms up, times the steps and prints the headline line.  The other "
+                         "configs always print their whole line")
     args = ap.parse_args()
     if args.dump_outputs and args.config != "relax":
         raise SystemExit("--dump-outputs: only the relax config (the headline loop) dumps its outputs")
     # an explicit --steps N always means N (1500 used to be a sentinel for "the whole run" of the nao configs)
-    args.full = args.steps is None
+    args.whole_run = args.steps is None
     from reart_amd.utils import lap as _lap
 
     _lap.CANONICAL_TIES = bool(args.deterministic)      # the product loops' default (run_robot.py / sweep: --deterministic)
@@ -963,7 +972,7 @@ def main():
         return
     if args.config in ("nao", "nao_recipe", "nao_projection"):
         if args.config == "nao_projection":
-            out = bench_nao_projection(args, dev, n_iter=None if args.full else args.steps, windows=15 if args.full else 3)
+            out = bench_nao_projection(args, dev, n_iter=None if args.whole_run else args.steps, windows=15 if args.whole_run else 3)
         else:
             out = bench_nao(args, dev) if args.config == "nao" else bench_nao_recipe(args, dev)
         if rank == 0:
@@ -1042,7 +1051,8 @@ def main():
     # independent instances on a GPU; their launches interleave on separate streams and fill the issue slots
     # a single latency-bound instance leaves idle
     sweep = None
-    if K == 1 and args.sweep_instances > 1 and args.sweep_mode == "batch":
+    run_sweep = args.full and K == 1 and args.sweep_instances > 1
+    if run_sweep and args.sweep_mode == "batch":
         # the instances advance in SHARED launches (reart_relax_step_batch): every kernel of the iteration runs once with
         # one argument block per instance
         from reart_amd.relax import RelaxBatch
@@ -1070,7 +1080,7 @@ def main():
                  "per_gpu": round(Ks * sw_steps / el_s, 3), "n_gpus": world, "mode": "batch", "steps": sw_steps, "warmup": sw_warm,
                  "graph_replays": batch.graph_replays, "eager_steps": batch.eager_steps}
         del sw_eng, batch
-    elif K == 1 and args.sweep_instances > 1:
+    elif run_sweep:
         Ks = args.sweep_instances
         sw_eng, sw_st = [], []
         for k in range(Ks):
@@ -1121,7 +1131,7 @@ def main():
         ranks_info = [me]
 
     # per-phase device time of the same step (eager, HIP events on the launch stream)
-    phases = eng.step_timed(args.profile_steps) if args.profile_steps > 0 else {}
+    phases = eng.step_timed(args.profile_steps) if args.full and args.profile_steps > 0 else {}
     if rank == 0:
         B = T - 1
         # Dominant kernel: the search launch.  With the flow loss it is ONE kernel (knn_pruned_pair_kernel)
@@ -1171,7 +1181,7 @@ def main():
                     "algorithmic_pairs_per_launch": nn_pairs, "algorithmic_speedup": round(nn_pairs / executed, 3),
                     "algorithmic_frac": round(nn_flops / t_nn / 1e12 / FP32_PEAK_TFLOPS, 4),
                     "hbm_gbs": round(nn_bytes / t_nn / 1e9, 3), "algorithmic_bytes": nn_bytes}
-            if use_flow and P_BENCH == 20:
+            if args.full and use_flow and P_BENCH == 20:
                 try:       # the five-launch chain with free arithmetic, measured now (an aid: never costs the line)
                     fl_us, fl_small = step_chain_floor(dev, N, B)
                     roof["step_floor_us"] = round(fl_us, 3)
@@ -1180,13 +1190,13 @@ def main():
                 except Exception as exc:
                     roof["step_floor_us"] = None
         cpu = cpu_torch = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             cpu = cpu_baseline(seq, T, N, cano_idx)
             cpu_torch = cpu_baseline_torch(seq, T, N, cano_idx)
         # secondary figure: what ends an instance (reference run_robot.py:224-330) -- structure extraction and
         # the model-selection energy on the state reached above; outside the timed region, never part of `value`
         end_of_run = None
-        if not args.no_tail:
+        if args.full and not args.no_tail:
             try:
                 from reart_amd import tail
 
@@ -1265,7 +1275,7 @@ def main():
             "final_losses": {"recon": float(energies[0][0]), "flow": float(energies[0][1]),
                              "per_rank_total": [float(e[2]) for e in energies]},
         }
-        if world == 1 and not args.no_secondary:
+        if args.full and world == 1 and not args.no_secondary:
             # BASELINE configs[4], the extractor of configs[2] and configs[2] itself (nao, 15 000 iterations) in the SAME line
             # (short in-process runs, a few seconds each),
             # each with its own roofline and CPU baseline; `python bench.py --config kinematic|extractor` gives the full lines

@@ -21,7 +21,8 @@ def _run(*argv, timeout=600):
 
 
 def test_headline_line_contract(dev):
-    d = _run("--gpus", "1", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-secondary", "--no-tail", "--sweep-instances", "0")
+    d = _run("--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline", "--no-secondary", "--no-tail",
+             "--sweep-instances", "0")
     assert d["metric"] == "relaxation-loop iterations/sec" and d["unit"] == "iterations/s" and d["n_gpus"] == 1
     assert d["steps"] == 20 and d["warmup"] == 5 and d["higher_is_better"] is True and d["scaling"] == "weak"
     assert d["dtype"] == "f32" and d["data"] == "synthetic" and d["vs_baseline"] is None
@@ -34,6 +35,21 @@ def test_headline_line_contract(dev):
     assert r["traffic"] is None or isinstance(r["traffic"], (int, float))        # a number of bytes (or null), as the contract says
     # the launch chain with its arithmetic removed, measured in the run: below the step, the small kernels' share below the whole
     assert 0 < r["step_floor_small_kernels_us"] < r["step_floor_us"] < 1e3 * d["ms_per_step"] and 0 < r["step_floor_frac"] < 1
+
+
+def test_plain_run_is_the_headline_alone(dev):
+    """Without --full the line carries the headline and what the timed steps measured themselves (the search launch's device
+    stamps), and nothing that takes runs of its own: no sweep, phases, launch-chain floor, CPU baselines, end-of-run or secondary."""
+    d = _run("--gpus", "1", "--steps", "20", "--warmup", "5")
+    assert d["metric"] == "relaxation-loop iterations/sec" and d["unit"] == "iterations/s" and d["n_gpus"] == 1
+    assert d["steps"] == 20 and d["warmup"] == 5 and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert abs(d["ms_per_step"] * d["value"] - 1e3) < 1.0 and d["value"] > 1000
+    assert d["config"]["graph_replays"] >= 1 and d["config"]["eager_steps"] == 0
+    r = d["roofline"]
+    assert r["bound"] == "valu" and 0 < r["frac"] < 1 and r["kernel_ms"] < d["ms_per_step"] and r["launches_measured"] == 20
+    assert not any(k.startswith("step_floor") for k in r), r
+    assert d["sweep"] is None and d["phases_ms"] == {} and d["end_of_run"] is None
+    assert d["cpu_baseline"] is None and d["cpu_baseline_torch"] is None and "secondary" not in d
 
 
 def test_dump_outputs(dev, tmp_path):
@@ -66,10 +82,10 @@ def _strings(x, path=""):
 
 
 def test_default_line_fits_the_drivers_record(dev):
-    """`python bench.py` with every leg (short windows): ONE line of at most 5 KB -- numbers and labels of at most 80
+    """`python bench.py --full` with every leg (short windows): ONE line of at most 5 KB -- numbers and labels of at most 80
     characters, no prose -- so that the tail the driver stores holds secondary.*.value, sweep.per_gpu, end_of_run, rccl_world
     and ranks (VERDICT r04 #6); per-solve percentiles and the bounded sample of the README.md:125 projection are in it."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "100", "--warmup", "150"], capture_output=True, timeout=1500, cwd=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "100", "--warmup", "150"], capture_output=True, timeout=1500, cwd=ROOT)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     lines = [l for l in r.stdout.decode().splitlines() if l.strip()]
     assert len(lines) == 1

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of search tuning: prints it/s, kernel_ms, pairs.  Every run under `timeout` (a hang must not take the box).
-run() { echo "== $*"; env "$@" timeout 120 python bench.py --no-cpu-baseline --sweep-instances 0 --no-tail --profile-steps 20 2>/dev/null | python -c "
+run() { echo "== $*"; env "$@" timeout 120 python bench.py --full --no-cpu-baseline --sweep-instances 0 --no-tail --profile-steps 20 2>/dev/null | python -c "
 import json,sys
 try:
     d=json.loads(sys.stdin.read()); r=d['roofline'] or {}

@@ -2,7 +2,7 @@
 # A/B of the headline iteration on ONE box: tools/ab_headline.sh tag1 tag2 ...  (tag "base" = the product library; others
 # reart_amd/csrc/libreart_hip_<tag>.so), two rounds each, interleaved; prints it/s, search kernel_ms, per-phase eager times.
 run() { lib=reart_amd/csrc/libreart_hip_$1.so; [ "$1" = base ] && lib=reart_amd/csrc/libreart_hip.so
-  REART_LIB=$lib timeout 200 python bench.py --no-cpu-baseline --no-secondary --sweep-instances 0 --no-tail --profile-steps 20 2>/dev/null | python -c "
+  REART_LIB=$lib timeout 200 python bench.py --full --no-cpu-baseline --no-secondary --sweep-instances 0 --no-tail --profile-steps 20 2>/dev/null | python -c "
 import json,sys
 try:
     d=json.loads(sys.stdin.read()); r=d['roofline'] or {}

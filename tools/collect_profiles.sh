@@ -18,9 +18,9 @@ if python3 -c "import sys; sys.exit(0 if float('$KMS') > 0.038 else 1)"; then
   echo "slow-search box: this set is the SLOW kind" | tee $O/slowbox.txt
   { date; rocm-smi --showcomputepartition --showmemorypartition --showclocks --showperflevel --showpower 2>&1; rocminfo 2>&1 | grep -i -E "xnack|Compute Unit|Max Clock|Cacheline|L2|L3|Marketing|Coherent|Memory Properties" | sort | uniq -c; env | grep -E "^(HSA|HIP|ROC|GPU|AMD)" ; } >> $O/slowbox.txt 2>&1
 fi
-# 0. the plain bench lines (no profiler)
-timeout 900 python3 bench.py > $O/bench_default.json 2> $O/bench_default.err
-timeout 300 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary > $O/bench_driver_args.json 2> $O/bench_driver_args.err
+# 0. the bench lines (no profiler)
+timeout 900 python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+timeout 300 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary > $O/bench_driver_args.json 2> $O/bench_driver_args.err
 timeout 600 python3 bench.py --config kinematic > $O/bench_kinematic.json 2> $O/bench_kinematic.err
 timeout 600 python3 bench.py --config nao_recipe > $O/bench_nao_recipe.json 2> $O/bench_nao_recipe.err
 timeout 600 python3 bench.py --config nao > $O/bench_nao.json 2> $O/bench_nao.err
@@ -76,8 +76,8 @@ for C in FETCH_SIZE WRITE_SIZE SQ_INSTS_VALU SQ_ACTIVE_INST_VALU GRBM_GUI_ACTIVE
 done
 # the counter summary the bench line cites, stamped with the sources it was measured on
 python3 tools/pmc_search_json.py $O > $O/pmc_search.json 2> $O/pmc_search_json.err
-# the bench line of the driver's exact command, last (every leg, both modes of the projection)
-timeout 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_default.json 2> $O/bench_driver_default.err
+# the bench line of the driver's command with every leg, last (both modes of the projection)
+timeout 900 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_default.json 2> $O/bench_driver_default.err
 # keep the merge-back small: only the summaries travel
 find $O -mindepth 1 -maxdepth 1 -type d -exec rm -rf {} +
 ls -la $O
