@@ -14,7 +14,8 @@
  *     throws.  (The reference's wrappers return 1 and exit(-1) on launch failure,
  *     networks/pointnet_lib/src/ball_query.cpp:25, ball_query_gpu.cu:62-66.)
  *   - fp32 data, int64 indices at the chamferdist / knn_cuda boundaries, int32 at
- *     the pointnet2_cuda boundary, exactly as the reference interfaces.
+ *     the pointnet2_cuda boundary, exactly as the reference interfaces; the K-NN
+ *     forward also takes fp64 clouds (reart_knn_points_idx_f64), as upstream's does.
  *
  * Each entry point names the reference interface (file:line under the upstream
  * stevenlsw/reart tree) it replaces.
@@ -73,6 +74,24 @@ int reart_knn_points_idx(const float *p1, const float *p2,
                          int N, int P1, int P2, int D, int K,
                          float *dists, int64_t *idx,
                          void *workspace, size_t workspace_bytes, void *stream);
+
+/* The float64 form of chamferdist._C.knn_points_idx (the upstream forward dispatches
+ * on float and double and returns dists in the input's dtype).  Same arguments, status
+ * codes and contract as reart_knn_points_idx with double in place of float:
+ *   p1 [N,P1,D], p2 [N,P2,D] f64 contiguous, 1 <= D <= REART_MAX_D, 1 <= K <= REART_MAX_K_LIST
+ *   (0: invalid argument, above: unsupported); dists [N,P1,K] f64 squared L2, idx [N,P1,K] i64,
+ *   ascending by (distance, index); rows >= lengths1[n] and slots >= lengths2[n] are zero.
+ * Distance contract: ((d0*d0)+(d1*d1))+(d2*d2)+... with dc = p1[c]-p2[c], summed in ascending
+ * c, every operation a correctly rounded fp64 one: no FMA, no matrix cores.  NaN / Inf
+ * coordinates are outside the contract.  One kernel serves every D and K (csrc/knn_f64.hip).
+ * There is no float64 backward (the upstream backward is float-only).
+ * workspace: reart_knn_points_workspace_bytes_f64(N,P1,P2,D,K) bytes (0 when D or K is out of range). */
+size_t reart_knn_points_workspace_bytes_f64(int N, int P1, int P2, int D, int K);
+int reart_knn_points_idx_f64(const double *p1, const double *p2,
+                             const int64_t *lengths1, const int64_t *lengths2,
+                             int N, int P1, int P2, int D, int K,
+                             double *dists, int64_t *idx,
+                             void *workspace, size_t workspace_bytes, void *stream);
 
 /* Replaces chamferdist._C.knn_points_backward(p1,p2,lengths1,lengths2,idx,grad_dists)
  * (utils/chamfer.py:206-208).  p1 [N,P1,D], p2 [N,P2,D], 1 <= D <= REART_MAX_D;

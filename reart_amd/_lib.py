@@ -31,6 +31,8 @@ PROTOTYPES = {
     "reart_knn_points_workspace_bytes": (c_size_t, [c_int] * 4),
     "reart_knn_points_workspace_bytes_d": (c_size_t, [c_int] * 5),
     "reart_knn_points_idx": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, c_size_t, P]),
+    "reart_knn_points_workspace_bytes_f64": (c_size_t, [c_int] * 5),
+    "reart_knn_points_idx_f64": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, c_size_t, P]),
     "reart_knn_points_backward_workspace_bytes": (c_size_t, [c_int] * 4),
     "reart_knn_points_backward": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, c_size_t, P]),
     "reart_chamfer_bidir_workspace_bytes": (c_size_t, [c_int] * 2),

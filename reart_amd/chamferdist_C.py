@@ -24,14 +24,17 @@ def _check_dim(what, D):
 
 
 def knn_points_idx(p1, p2, lengths1, lengths2, K, version=-1):
-    """-> (idx int64 [N,P1,K], dists float32 [N,P1,K] squared L2), cf. utils/chamfer.py:174.
+    """-> (idx int64 [N,P1,K], dists [N,P1,K] squared L2 in the clouds' dtype), cf. utils/chamfer.py:174.
 
-    p1 [N,P1,D], p2 [N,P2,D] with 1 <= D <= 256 (REART_MAX_D); D > 256 raises NotImplementedError.
-    1 <= K <= 1024: at D = 3, K <= 16 keeps each query's list in registers, larger K in LDS; other D keep it in
-    LDS (same result, bit for bit); K > 1024 raises NotImplementedError."""
+    p1 [N,P1,D], p2 [N,P2,D], both float32 or both float64 (like the upstream forward, which dispatches on float and
+    double); mixed or other dtypes raise TypeError.  1 <= D <= 256 (REART_MAX_D); D > 256 raises NotImplementedError.
+    1 <= K <= 1024; K > 1024 raises NotImplementedError.  float32: at D = 3, K <= 16 keeps each query's list in
+    registers, larger K in LDS; other D keep it in LDS (same result, bit for bit).  float64: one LDS-list kernel for
+    every D and K (``reart_knn_points_idx_f64``), distances summed in fp64."""
     _lib.require_gpu(p1, p2, lengths1, lengths2)
-    if p1.dtype != torch.float32 or p2.dtype != torch.float32:
-        raise TypeError("knn_points_idx expects float32 point clouds")
+    if p1.dtype != p2.dtype or p1.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"knn_points_idx expects float32 or float64 point clouds of one dtype, got {p1.dtype} and "
+                        f"{p2.dtype}")
     p1, p2 = p1.contiguous(), p2.contiguous()
     N, P1, D = p1.shape
     P2 = p2.shape[1]
@@ -40,20 +43,31 @@ def knn_points_idx(p1, p2, lengths1, lengths2, K, version=-1):
     _check_dim("knn_points_idx", D)
     l1 = _as_len(lengths1, N, P1, p1.device)
     l2 = _as_len(lengths2, N, P2, p1.device)
-    dists = torch.empty((N, P1, K), dtype=torch.float32, device=p1.device)
+    dists = torch.empty((N, P1, K), dtype=p1.dtype, device=p1.device)
     idx = torch.empty((N, P1, K), dtype=torch.int64, device=p1.device)
     L = _lib.lib()
-    nbytes = L.reart_knn_points_workspace_bytes_d(N, P1, P2, D, K)
+    if p1.dtype == torch.float64:
+        nbytes, run, name = L.reart_knn_points_workspace_bytes_f64(N, P1, P2, D, K), L.reart_knn_points_idx_f64, \
+            "reart_knn_points_idx_f64"
+    else:
+        nbytes, run, name = L.reart_knn_points_workspace_bytes_d(N, P1, P2, D, K), L.reart_knn_points_idx, \
+            "reart_knn_points_idx"
     ws = _lib.workspace(nbytes, p1.device)
-    rc = L.reart_knn_points_idx(_lib.ptr(p1), _lib.ptr(p2), _lib.ptr(l1), _lib.ptr(l2), N, P1, P2, D, K,
-                                _lib.ptr(dists), _lib.ptr(idx), _lib.ptr(ws), ws.numel(), _lib.stream())
-    _lib.check(rc, "reart_knn_points_idx")
+    rc = run(_lib.ptr(p1), _lib.ptr(p2), _lib.ptr(l1), _lib.ptr(l2), N, P1, P2, D, K,
+             _lib.ptr(dists), _lib.ptr(idx), _lib.ptr(ws), ws.numel(), _lib.stream())
+    _lib.check(rc, name)
     return idx, dists
 
 
 def knn_points_backward(p1, p2, lengths1, lengths2, idx, grad_dists):
-    """-> (grad_p1 [N,P1,D], grad_p2 [N,P2,D]), cf. utils/chamfer.py:206-208; 1 <= D <= 256 (REART_MAX_D)."""
+    """-> (grad_p1 [N,P1,D], grad_p2 [N,P2,D]), cf. utils/chamfer.py:206-208; 1 <= D <= 256 (REART_MAX_D).
+
+    float32 only, like the upstream backward: p1, p2 and grad_dists of any other dtype raise TypeError (the autograd
+    wrapper in utils/chamfer.py casts float64 clouds to float32 before this call, as the reference does)."""
     _lib.require_gpu(p1, p2, idx, grad_dists)
+    if p1.dtype != torch.float32 or p2.dtype != torch.float32 or grad_dists.dtype != torch.float32:
+        raise TypeError(f"knn_points_backward expects float32 p1, p2 and grad_dists, got {p1.dtype}, {p2.dtype} and "
+                        f"{grad_dists.dtype}")
     p1, p2 = p1.contiguous(), p2.contiguous()
     idx, grad_dists = idx.contiguous(), grad_dists.contiguous()
     N, P1, D = p1.shape

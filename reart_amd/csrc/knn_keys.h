@@ -1,14 +1,47 @@
-// reart_amd/csrc/knn_keys.h -- the per-query ranked list of the LDS-list K-NN kernels (knn_list.hip, knn_dim.hip).
+// reart_amd/csrc/knn_keys.h -- the per-query ranked list of the LDS-list K-NN kernels (knn_list.hip, knn_dim.hip,
+// knn_f64.hip).
 //
-// A list holds a query's K best targets so far as K ascending 64-bit keys in LDS, key = (bits of the fp32
-// distance) << 32 | j.  Distances are >= +0, so integer order is (distance, index) order and every key is
-// distinct.  A wave that found candidates (keys below the list's K-th key) sorts them across its 64 lanes and
-// merges them in: every candidate and every list entry finds its new slot by counting the other side's smaller
-// keys (binary searches), and entries pushed past K fall off.
+// A list holds a query's K best targets so far as K ascending keys in LDS.  The fp32 searches use a 64-bit key,
+// (bits of the fp32 distance) << 32 | j; the fp64 search uses KeyF64, the pair (bits of the fp64 distance, j) in
+// lexicographic order.  Distances are >= +0, so either order is (distance, index) order and every key is distinct.
+// A wave that found candidates (keys below the list's K-th key) sorts them across its 64 lanes and merges them in:
+// every candidate and every list entry finds its new slot by counting the other side's smaller keys (binary
+// searches), and entries pushed past K fall off.  The helpers are templates over the key type; a key type brings
+// kl_shfl_xor, kl_cas, operator< and a kl_none specialisation (the all-ones key, above every real key).
 #pragma once
 #include "common.h"
 
 typedef unsigned long long u64;
+
+// fp64 search key: distance bits, then index; 16 B in LDS
+struct __attribute__((aligned(16))) KeyF64 {
+    u64 d;
+    unsigned j, pad;
+};
+
+__device__ __forceinline__ bool operator<(const KeyF64 &a, const KeyF64 &b) {
+    return a.d < b.d || (a.d == b.d && a.j < b.j);
+}
+
+// c ? a : b, per component (a select of whole structs goes through scratch memory)
+__device__ __forceinline__ KeyF64 kl_sel(bool c, KeyF64 a, KeyF64 b) {
+    return KeyF64{c ? a.d : b.d, c ? a.j : b.j, 0u};
+}
+
+// one compare-exchange of the bitonic network: min(o, v) if keep_min, else max(o, v)
+__device__ __forceinline__ u64 kl_cas(bool keep_min, u64 o, u64 v) {
+    return keep_min ? (o < v ? o : v) : (o > v ? o : v);
+}
+__device__ __forceinline__ KeyF64 kl_cas(bool keep_min, KeyF64 o, KeyF64 v) {
+    return kl_sel(keep_min ? o < v : v < o, o, v);
+}
+
+template <class Key>
+__device__ __forceinline__ Key kl_none();
+template <>
+__device__ __forceinline__ u64 kl_none<u64>() { return ~0ull; }
+template <>
+__device__ __forceinline__ KeyF64 kl_none<KeyF64>() { return KeyF64{~0ull, ~0u, 0u}; }
 
 // the wave's LDS accesses before this point are complete, and the compiler moves none across it
 __device__ __forceinline__ void kl_wave_sync() {
@@ -22,22 +55,28 @@ __device__ __forceinline__ u64 kl_shfl_xor(u64 v, int m) {
     return ((u64)(unsigned)hi << 32) | (unsigned)lo;
 }
 
+__device__ __forceinline__ KeyF64 kl_shfl_xor(KeyF64 v, int m) {
+    return KeyF64{kl_shfl_xor(v.d, m), (unsigned)__shfl_xor((int)v.j, m, 64), 0u};
+}
+
 // ascending across the 64 lanes (bitonic network)
-__device__ __forceinline__ u64 kl_sort64(u64 v, int lane) {
+template <class Key>
+__device__ __forceinline__ Key kl_sort64(Key v, int lane) {
 #pragma unroll
     for (int k = 2; k <= 64; k <<= 1) {
 #pragma unroll
         for (int j = k >> 1; j > 0; j >>= 1) {
-            const u64 o = kl_shfl_xor(v, j);
+            const Key o = kl_shfl_xor(v, j);
             const bool keep_min = ((lane & j) == 0) == ((lane & k) == 0);
-            v = keep_min ? (o < v ? o : v) : (o > v ? o : v);
+            v = kl_cas(keep_min, o, v);
         }
     }
     return v;
 }
 
 // number of entries of the ascending array a[0..n) below v
-__device__ __forceinline__ int kl_count_below(const u64 *a, int n, u64 v) {
+template <class Key>
+__device__ __forceinline__ int kl_count_below(const Key *a, int n, Key v) {
     int lo = 0, hi = n;
     while (lo < hi) {
         const int mid = (lo + hi) >> 1;
@@ -47,14 +86,14 @@ __device__ __forceinline__ int kl_count_below(const u64 *a, int n, u64 v) {
 }
 
 // Merge c sorted candidates into the list lst[0..K) (NE = list entries per lane, K <= 64 * NE).  v: this lane's
-// candidate, ascending across the lanes, lanes >= c hold ~0; cand: 64 keys of LDS scratch.  Called by the whole
-// wave; returns the list's new K-th key.
-template <int NE>
-__device__ __forceinline__ u64 kl_merge(u64 *lst, u64 *cand, int K, u64 v, int c, int lane) {
+// candidate, ascending across the lanes, lanes >= c hold kl_none; cand: 64 keys of LDS scratch.  Called by the
+// whole wave; returns the list's new K-th key.
+template <int NE, class Key>
+__device__ __forceinline__ Key kl_merge(Key *lst, Key *cand, int K, Key v, int c, int lane) {
     cand[lane] = v;
-    u64 old[NE];
+    Key old[NE];
 #pragma unroll
-    for (int u = 0; u < NE; ++u) old[u] = (lane + 64 * u < K) ? lst[lane + 64 * u] : ~0ull;
+    for (int u = 0; u < NE; ++u) old[u] = (lane + 64 * u < K) ? lst[lane + 64 * u] : kl_none<Key>();
     kl_wave_sync();
     // new slots: a candidate moves up by the list entries below it, an entry by the candidates below it
     const int cpos = lane < c ? lane + kl_count_below(lst, K, v) : K;

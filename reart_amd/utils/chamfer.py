@@ -33,6 +33,8 @@ class _knn_points(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_dists, grad_idx):
+        # The native backward is float32 only, as upstream (utils/chamfer.py:196-208 casts too); autograd casts the
+        # gradients back to a float64 input's dtype.
         p1, p2, lengths1, lengths2, idx = ctx.saved_tensors
         grad_p1, grad_p2 = _C.knn_points_backward(
             p1.float(), p2.float(), lengths1, lengths2, idx, grad_dists.float()
@@ -43,8 +45,9 @@ class _knn_points(Function):
 def knn_points(p1, p2, lengths1=None, lengths2=None, K=1, version=-1, return_nn=False, return_sorted=True):
     """K nearest neighbours of every p1 point in p2 (utils/chamfer.py:212-286).
 
-    p1 [N,P1,D], p2 [N,P2,D] with 1 <= D <= 256 and 1 <= K <= 1024 (above: NotImplementedError).
-    Returns the namedtuple ``(dists [N,P1,K] squared, idx [N,P1,K] int64, knn or None)``.
+    p1 [N,P1,D], p2 [N,P2,D] with 1 <= D <= 256 and 1 <= K <= 1024 (above: NotImplementedError), both float32 or
+    both float64 (otherwise TypeError).  Returns the namedtuple ``(dists [N,P1,K] squared in the clouds' dtype,
+    idx [N,P1,K] int64, knn or None)``; gradients reach float64 clouds through the float32 backward, as upstream.
     """
     if p1.shape[0] != p2.shape[0]:
         raise ValueError("pts1 and pts2 must have the same batch dimension.")
@@ -63,7 +66,7 @@ def knn_points(p1, p2, lengths1=None, lengths2=None, K=1, version=-1, return_nn=
 
 def knn_gather(x, idx, lengths=None):
     """x [N,M,U], idx [N,L,K] -> [N,L,K,U] with x_out[n,l,k] = x[n, idx[n,l,k]]
-    (utils/chamfer.py:289-337); entries with k >= lengths[n] are zero."""
+    (utils/chamfer.py:289-337); entries with k >= lengths[n] are zero.  Any dtype of x (the result keeps it)."""
     N, M, U = x.shape
     n2, L, K = idx.shape
     if N != n2:
@@ -78,7 +81,8 @@ def knn_gather(x, idx, lengths=None):
 
 
 class ChamferDistance(torch.nn.Module):
-    """Per-point (un-reduced) Chamfer distance, cf. utils/chamfer.py:19-132, for clouds of any dimension D <= 256.
+    """Per-point (un-reduced) Chamfer distance, cf. utils/chamfer.py:19-132, for clouds of any dimension D <= 256,
+    both float32 or both float64 (the distances come back in that dtype; otherwise TypeError).
 
     ``reduction`` is validated and then ignored, exactly like the reference (its reduction
     block is commented out, utils/chamfer.py:104-117): the result has shape [B, P].
