@@ -38,6 +38,7 @@ struct BaseBwdArgs {
     int N, P, B, H;
     int nchunk;                 // ceil(N / cpts)
     int cpts;                   // points per backward workgroup: 64, 32 or 16 (0: the default, 32)
+    int dp_sep;                 // set by the launcher: the hidden gradient has an LDS tile of its own (else it overwrites the h tile)
     float *partial;             // [nchunk][n_out]
     // finalize
     float *gW1, *gb1, *gW2, *g6d, *gt;

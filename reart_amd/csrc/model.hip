@@ -490,28 +490,39 @@ __global__ __launch_bounds__(256) void rt_table_kernel(const float *__restrict__
     for (int c = 0; c < 3; ++c) table[12 * (size_t)e + 9 + c] = pt[3 * (size_t)e + c];
 }
 
-// (1) One workgroup per chunk of 64 points, W = ceil(P/2) waves x the same points:
-//   a. wave g: dL/dw[n,p] = sum_t G[t,n].(R[t,p] x_n + t[t,p]) for parts {2g, 2g+1}; the [R|t]
-//      table is wave-uniform and read with scalar loads
-//   b. softmax backward -> ds[n,:] (LDS); wave g: hidden gradient dp[n,j] for its slice of j
+// (1) One workgroup per chunk of up to 64 points, BW_WAVES waves x the same points:
+//   a. dL/dw[n,p] = sum_t G[t,n].(R[t,p] x_n + t[t,p]) as one matrix product, one 16 x 16 tile per wave
+//   b. softmax backward -> ds[n,:] (LDS): wave g < ceil(P/2) for parts {2g, 2g+1}, y from the LDS copy of the yT tile
 //   c. partial sums over the chunk of every parameter gradient, each output accumulated
 //      sequentially over the chunk's points (ascending n) -> deterministic:
 //        gW2[p,j] = sum_n ds[n,p] h[n,j];  gW1[j,c] = sum_n dp[n,j] x[n,c];  gb1[j] = sum_n dp[n,j]
 //        gR[t,p]  = sum_{n:k_n=p} w_n G[t,n] x_n^T;  gt[t,p] = sum_{n:k_n=p} w_n G[t,n]
-//      For gR/gt the chunk's points are first ordered by part with a stable in-wave counting
-//      sort (ballot + popcount), so thread (t, entry) walks each part's points in ascending n
-//      with a register accumulator -- no LDS read-modify-write chain, no atomics.
+//      Behind the barrier that completes ds the reductions need nothing from one another, so the waves split by ROLE
+//      instead of walking them in turn: waves [0, BW_MFMA) take the gR|gt and gW2 tiles, waves [BW_MFMA, BW_WAVES) the
+//      hidden gradient dp (b') and then gW1 / gb1 (c3) of THEIR OWN 32 rows j of dp -- so c3 needs no barrier at all,
+//      only the wave's own LDS order.  dp has storage of its own (the h tile stays read-only for the gW2 tiles); where
+//      the LDS budget does not allow that (a.dp_sep == 0) dp overwrites the h tile as before and one workgroup barrier
+//      separates the two roles.
 #define BW_LD (RED_CHUNK + 1)
+#define BW_WAVES 16                       // block size of every instance: the launch bound, the kernel's strides, the launcher
+#define BW_HID (BW_WAVES / 4)             // waves of the hidden-gradient role: dp, then gW1 / gb1 (4 row tiles at H = 128)
+#define BW_MFMA (BW_WAVES - BW_HID)       // waves of the gR|gt / gW2 role (12 tiles at B = 19, H = 128)
+#ifdef REART_PHASE_CLOCK   // stamp of another wave's lane 0 (the roles of the tail)
+#define PHASE_TS_WAVE(which, k, wave) do { if (blockIdx.x == 1 && (int)threadIdx.x == 64 * (wave)) g_phase_ts[which][k] = __builtin_amdgcn_s_memtime(); } while (0)
+#else
+#define PHASE_TS_WAVE(which, k, wave) do { } while (0)
+#endif
 
 template <int PP, bool BATCH>
-__global__ __launch_bounds__(64 * (((PP > 0 ? PP : 32) + FW_PG - 1) / FW_PG)) void base_bwd_block_kernel(Batched<BaseBwdArgs> ab) {
+__global__ __launch_bounds__(64 * BW_WAVES) void base_bwd_block_kernel(Batched<BaseBwdArgs> ab) {
     const BaseBwdArgs &a = ab.a[BATCH ? blockIdx.y : 0];
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int PMAX = (PP > 0) ? PP : 32;
-    constexpr int W = (PMAX + FW_PG - 1) / FW_PG;
+    constexpr int W = BW_WAVES;
     constexpr int BS = 64 * W;
+    static_assert(2 * W >= PMAX, "phase b: one wave per part pair");
     const int P = (PP > 0) ? PP : a.P;
-    float *s_h = smem;                               // [H][BW_LD]  hT tile, later dp tile
+    float *s_h = smem;                               // [H][BW_LD]  hT tile (a.dp_sep == 0: later the dp tile)
     float *s_ds = s_h + (size_t)a.H * BW_LD;         // [PMAX][BW_LD]  dw, later ds
     float *s_x = s_ds + (size_t)PMAX * BW_LD;        // [RED_CHUNK][3]
     float *s_w = s_x + RED_CHUNK * 3;                // [RED_CHUNK]
@@ -519,8 +530,11 @@ __global__ __launch_bounds__(64 * (((PP > 0 ? PP : 32) + FW_PG - 1) / FW_PG)) vo
     float *s_G = (float *)(s_kn + RED_CHUNK + PMAX + 4);  // [B][RED_CHUNK*3]  upstream gradient tile
     float *s_w2T = s_G + (size_t)a.B * RED_CHUNK * 3;// [H][PMAX]
     float *s_rt = s_w2T + (size_t)a.H * PMAX;        // [B*P][12]  [R|t] rows
+    float *s_y = s_rt + (size_t)a.B * a.P * 12;      // [PMAX][BW_LD]  yT tile
+    const int dp_ld = a.dp_sep ? a.cpts + 1 : BW_LD;
+    float *s_dp = a.dp_sep ? s_y + (size_t)PMAX * BW_LD : s_h;   // [H][dp_ld]  hidden gradient
     const int tid = threadIdx.x, lane = tid & 63, grp = tid >> 6, chunk = blockIdx.x;
-    // a workgroup owns a.cpts (64 or 32) points; the tiles keep their 64-point layout (columns >= cn are zero), the
+    // a workgroup owns a.cpts (64, 32 or 16) points; the tiles keep their 64-point layout (columns >= cn are zero), the
     // matrix-core loops stop at cn: with 32 points twice as many workgroups each run half the reductions
     const int n0 = chunk * a.cpts;
     const int cn = (a.N - n0) < a.cpts ? (a.N - n0) : a.cpts;
@@ -531,8 +545,10 @@ __global__ __launch_bounds__(64 * (((PP > 0 ? PP : 32) + FW_PG - 1) / FW_PG)) vo
     // Tile loads.  Every group issues a batch of unconditional loads (clamped addresses, masked
     // afterwards), and the first batch of EVERY group is in flight before anything is stored to LDS:
     // written as plain guarded loops the compiler serialises the loads and the prologue becomes a
-    // chain of a dozen L2 / HBM round trips (measured 25 k cycles, now one round trip deep).
-    constexpr int UH = 13, UG = 6, UR = 8;   // H = 128, B = 19, P = 20: one batch each
+    // chain of a dozen L2 / HBM round trips (measured 25 k cycles, now one round trip deep).  The yT tile and
+    // hard_idx are part of that batch: y_k and phase b's y[p] are LDS reads, no second global round trip.
+    constexpr int UH = (128 * RED_CHUNK + BS - 1) / BS, UG = (19 * RED_CHUNK * 3 + BS - 1) / BS,
+                  UR = (19 * 20 * 12 + BS - 1) / BS, UY = (PMAX * RED_CHUNK + BS - 1) / BS;   // H = 128, B = 19, P = 20: one batch each
     const int ilast = cn - 1, nH = a.H * RED_CHUNK, nG = a.B * RED_CHUNK * 3, rlast = 3 * cn - 1, nR = a.B * a.P * 12;
     const bool live = lane < cn;
     const int n = live ? n0 + lane : n0;
@@ -540,7 +556,7 @@ __global__ __launch_bounds__(64 * (((PP > 0 ? PP : 32) + FW_PG - 1) / FW_PG)) vo
 #pragma unroll
         for (int u = 0; u < UH; ++u) {
             const int e = e0 + u * BS;
-            const int ec = e < nH ? e : tid;
+            const int ec = e < nH ? e : lane;
             const int j = ec >> 6, i = ec & 63;            // RED_CHUNK == 64
             v[u] = a.hT[(size_t)j * a.N + n0 + (i < cn ? i : ilast)];
         }
@@ -558,7 +574,7 @@ __global__ __launch_bounds__(64 * (((PP > 0 ? PP : 32) + FW_PG - 1) / FW_PG)) vo
 #pragma unroll
         for (int u = 0; u < UG; ++u) {
             const int e = e0 + u * BS;
-            const int ec = e < nG ? e : tid;
+            const int ec = e < nG ? e : lane;
             const int t = ec / (RED_CHUNK * 3), r0_ = ec - t * (RED_CHUNK * 3);
             const int r = r0_ < 3 * cn ? r0_ : rlast;
             g[u] = a.G[3 * ((size_t)t * a.N + n0) + r];
@@ -589,27 +605,28 @@ __global__ __launch_bounds__(64 * (((PP > 0 ? PP : 32) + FW_PG - 1) / FW_PG)) vo
     };
     auto load_r = [&](int e0, float (&v)[UR]) {
 #pragma unroll
-        for (int u = 0; u < UR; ++u) v[u] = a.rt_table[e0 + u * BS < nR ? e0 + u * BS : tid];
+        for (int u = 0; u < UR; ++u) v[u] = a.rt_table[e0 + u * BS < nR ? e0 + u * BS : 0];
     };
     auto store_r = [&](int e0, const float (&v)[UR]) {
 #pragma unroll
         for (int u = 0; u < UR; ++u)
             if (e0 + u * BS < nR) s_rt[e0 + u * BS] = v[u];
     };
-    float vh[UH], vg[UG], vgh[UG], vgl[UG], vr[UR], vw[PMAX];
+    float vh[UH], vg[UG], vgh[UG], vgl[UG], vr[UR], vw[PMAX], vy[UY];
     load_g(tid, vg, vgh, vgl);     // produced by the previous kernels on other XCDs: the longest latency first
     load_h(tid, vh);
     load_r(tid, vr);
     const int jw = tid < a.H ? tid : 0;
 #pragma unroll
     for (int p = 0; p < PMAX; ++p) vw[p] = a.W2[(size_t)(p < P ? p : 0) * a.H + jw];
+#pragma unroll
+    for (int u = 0; u < UY; ++u) {   // rows >= P and columns >= cn repeat real entries: finite, never part of a result
+        const int e = tid + u * BS, p = e >> 6, i = e & 63;
+        vy[u] = a.yT[(size_t)(p < P ? p : 0) * a.N + n0 + (i < cn ? i : ilast)];
+    }
     const float x0 = a.cano[3 * (size_t)n], x1 = a.cano[3 * (size_t)n + 1], x2 = a.cano[3 * (size_t)n + 2];
     int kn = -1;
-    float yk = 0.f;
-    if (grp == 0) {
-        kn = live ? a.hard_idx[n] : -1;
-        yk = a.yT[(size_t)(kn < 0 ? 0 : kn) * a.N + n];
-    }
+    if (grp == 0) kn = live ? a.hard_idx[n] : -1;
     store_g(tid, vg, vgh, vgl);
     store_h(tid, vh);
     store_r(tid, vr);
@@ -617,13 +634,17 @@ __global__ __launch_bounds__(64 * (((PP > 0 ? PP : 32) + FW_PG - 1) / FW_PG)) vo
 #pragma unroll
         for (int p = 0; p < PMAX; ++p) s_w2T[tid * PMAX + p] = vw[p];
     }
+#pragma unroll
+    for (int u = 0; u < UY; ++u) {
+        const int e = tid + u * BS;
+        if (e < PMAX * RED_CHUNK) s_y[(e >> 6) * BW_LD + (e & 63)] = vy[u];
+    }
     for (int e0 = tid + UG * BS; e0 < nG; e0 += UG * BS) { load_g(e0, vg, vgh, vgl); store_g(e0, vg, vgh, vgl); }
     for (int e0 = tid + UH * BS; e0 < nH; e0 += UH * BS) { load_h(e0, vh); store_h(e0, vh); }
     for (int e0 = tid + UR * BS; e0 < nR; e0 += UR * BS) { load_r(e0, vr); store_r(e0, vr); }
     for (int j = tid + BS; j < a.H; j += BS)
         for (int p = 0; p < P; ++p) s_w2T[j * PMAX + p] = a.W2[(size_t)p * a.H + j];
     if (grp == 0) {
-        s_w[lane] = (1.0f - yk) + yk;
         s_x[3 * lane] = live ? x0 : 0.f; s_x[3 * lane + 1] = live ? x1 : 0.f; s_x[3 * lane + 2] = live ? x2 : 0.f;
         s_kn[lane] = kn;
     }
@@ -679,125 +700,150 @@ __global__ __launch_bounds__(64 * (((PP > 0 ? PP : 32) + FW_PG - 1) / FW_PG)) vo
     }
     __syncthreads();
     PHASE_TS(1, 2);
-    const float dw0 = has0 ? s_ds[p0 * BW_LD + lane] : 0.f;
-    const float dw1 = has1 ? s_ds[(p0 + 1) * BW_LD + lane] : 0.f;
     // b. softmax backward: dot over all parts in ascending order, ds for this wave's parts
-    const float tau = a.tau_ptr ? a.tau_ptr[0] : a.tau;
-    float dot = 0.f;
-#pragma unroll
-    for (int p = 0; p < PMAX; ++p)
-        if (PP > 0 || p < P) dot = fmaf(a.yT[(size_t)p * a.N + n], s_ds[p * BW_LD + lane], dot);
+    if (grp == 0) {
+        const float yk = s_y[(kn < 0 ? 0 : kn) * BW_LD + lane];
+        s_w[lane] = (1.0f - yk) + yk;
+    }
     float ds0 = 0.f, ds1 = 0.f;
-    if (has0) ds0 = (a.yT[(size_t)p0 * a.N + n] * (dw0 - dot)) / tau;
-    if (has1) ds1 = (a.yT[(size_t)(p0 + 1) * a.N + n] * (dw1 - dot)) / tau;
+    if (has0) {
+        const float dw0 = s_ds[p0 * BW_LD + lane];
+        const float dw1 = has1 ? s_ds[(p0 + 1) * BW_LD + lane] : 0.f;
+        const float tau = a.tau_ptr ? a.tau_ptr[0] : a.tau;
+        float dot = 0.f;
+#pragma unroll
+        for (int p = 0; p < PMAX; ++p)
+            if (PP > 0 || p < P) dot = fmaf(s_y[p * BW_LD + lane], s_ds[p * BW_LD + lane], dot);
+        ds0 = (s_y[p0 * BW_LD + lane] * (dw0 - dot)) / tau;
+        if (has1) ds1 = (s_y[(p0 + 1) * BW_LD + lane] * (dw1 - dot)) / tau;
+    }
     __syncthreads();  // every wave has read dw before it is overwritten by ds
     if (has0) s_ds[p0 * BW_LD + lane] = live ? ds0 : 0.f;
     if (has1) s_ds[(p0 + 1) * BW_LD + lane] = live ? ds1 : 0.f;
     __syncthreads();
     PHASE_TS(1, 3);
-    // c1. gW2[p,j] = sum_i ds[p,i] h[j,i] on the matrix cores: v_mfma_f32_32x32x2_f32 is bit for bit the
-    // ascending-i fmaf chain (cdna guide section 3).  One 32 (parts) x 32 (hidden) tile per wave.
-    for (int tile = grp; tile * 32 < a.H; tile += W) {
+    // From here on ds, h, G, x, w, kn and W2T are read-only: the roles run side by side.
+    const int n2 = (a.B * 12 + 31) >> 5, n1 = (a.H + 31) >> 5;   // gR|gt tiles (dealt first: the longer ones), gW2 tiles
+    if (grp < BW_MFMA) {
         typedef float f16v __attribute__((ext_vector_type(16)));
-        f16v c = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        const int pr = lane & 31, jc = tile * 32 + (lane & 31), kh = lane >> 5;
-        const float *ap = s_ds + (pr < P ? pr : 0) * BW_LD + kh;
-        const float *bp = s_h + (jc < a.H ? jc : 0) * BW_LD + kh;
-        const bool aok = pr < P, bok = jc < a.H;
-        for (int kb = 0; kb < cn16; kb += 16) {
+        for (int g = grp; g < n2 + n1; g += BW_MFMA) {
+            f16v c = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            const int pr = lane & 31, kh = lane >> 5;
+            if (g >= n2) {
+                // c1. gW2[p,j] = sum_i ds[p,i] h[j,i] on the matrix cores: v_mfma_f32_32x32x2_f32 is bit for bit the
+                // ascending-i fmaf chain (cdna guide section 3).  One 32 (parts) x 32 (hidden) tile per wave.
+                const int jc = (g - n2) * 32 + (lane & 31);
+                const float *ap = s_ds + (pr < P ? pr : 0) * BW_LD + kh;
+                const float *bp = s_h + (jc < a.H ? jc : 0) * BW_LD + kh;
+                const bool aok = pr < P, bok = jc < a.H;
+                for (int kb = 0; kb < cn16; kb += 16) {
 #pragma unroll
-            for (int kk = kb; kk < kb + 16; kk += 2) {
-                const float av = aok ? ap[kk] : 0.f;
-                const float bv = bok ? bp[kk] : 0.f;
-                c = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, c, 0, 0, 0);
+                    for (int kk = kb; kk < kb + 16; kk += 2) {
+                        const float av = aok ? ap[kk] : 0.f;
+                        const float bv = bok ? bp[kk] : 0.f;
+                        c = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, c, 0, 0, 0);
+                    }
+                }
+                // C/D layout: row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5), col = lane & 31
+#pragma unroll
+                for (int reg = 0; reg < 16; ++reg) {
+                    const int prow_p = (reg & 3) + 8 * (reg >> 2) + 4 * kh;
+                    if (prow_p < P && bok) prow[off_gW2() + prow_p * a.H + jc] = c[reg];
+                }
+                PHASE_TS_WAVE(1, 5, n2 % BW_MFMA);
+            } else {
+                // c2. gR | gt on the matrix cores:  out[p][(t, e)] = sum_n onehot[p][n] * v[n][(t, e)]  with
+                //   v = (w_n G[t,n,r]) x_n[c]  (e = 3 r + c < 9)   or   w_n G[t,n,e-9]  (translation),
+                // the operands built on the fly from the LDS tiles.  A one-hot left factor makes every product
+                // exact (1 * v = v, 0 * v = 0), so each output is the ascending-n running sum of its part's
+                // points: deterministic, no sorting, no atomics.
+                const int col = g * 32 + (lane & 31);
+                const bool cok = col < a.B * 12;
+                const int t = cok ? col / 12 : 0, e = cok ? col - t * 12 : 0;
+                const int gr = e < 9 ? e / 3 : e - 9, xc = e < 9 ? e - 3 * (e / 3) : 0;
+                const float *gcol = s_G + t * (RED_CHUNK * 3) + gr;
+                for (int kb = 0; kb < cn16; kb += 16) {
+#pragma unroll
+                    for (int kk = kb; kk < kb + 16; kk += 2) {
+                        const int n = kk + kh;
+                        const float av = (s_kn[n] == pr) ? 1.f : 0.f;
+                        float bv = s_w[n] * gcol[3 * n];
+                        if (e < 9) bv = bv * s_x[3 * n + xc];
+                        c = __builtin_amdgcn_mfma_f32_32x32x2f32(av, cok ? bv : 0.f, c, 0, 0, 0);
+                    }
+                }
+#pragma unroll
+                for (int reg = 0; reg < 16; ++reg) {
+                    const int prow_p = (reg & 3) + 8 * (reg >> 2) + 4 * kh;
+                    if (prow_p < P && cok) prow[off_gRt(a.P, a.H) + (t * a.P + prow_p) * 12 + e] = c[reg];
+                }
+                PHASE_TS_WAVE(1, 4, 0);
             }
         }
-        // C/D layout: row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5), col = lane & 31
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-            const int prow_p = (reg & 3) + 8 * (reg >> 2) + 4 * kh;
-            if (prow_p < P && bok) prow[off_gW2() + prow_p * a.H + jc] = c[reg];
-        }
     }
-    PHASE_TS(1, 4);
-    // c2. gR | gt on the matrix cores:  out[p][(t, e)] = sum_n onehot[p][n] * v[n][(t, e)]  with
-    //   v = (w_n G[t,n,r]) x_n[c]  (e = 3 r + c < 9)   or   w_n G[t,n,e-9]  (translation),
-    // the operands built on the fly from the LDS tiles.  A one-hot left factor makes every product
-    // exact (1 * v = v, 0 * v = 0), so each output is the ascending-n running sum of its part's
-    // points: deterministic, no sorting, no atomics.
-    for (int tile = grp; tile * 32 < a.B * 12; tile += W) {
+    if (!a.dp_sep) __syncthreads();  // uniform.  dp overwrites the h tile: the gW2 tiles have consumed it
+    if (grp >= BW_MFMA) {
         typedef float f16v __attribute__((ext_vector_type(16)));
-        f16v c = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        const int pr = lane & 31, col = tile * 32 + (lane & 31), kh = lane >> 5;
-        const bool cok = col < a.B * 12;
-        const int t = cok ? col / 12 : 0, e = cok ? col - t * 12 : 0;
-        const int gr = e < 9 ? e / 3 : e - 9, xc = e < 9 ? e - 3 * (e / 3) : 0;
-        const float *gcol = s_G + t * (RED_CHUNK * 3) + gr;
-        for (int kb = 0; kb < cn16; kb += 16) {
+        // one 32-row tile of j per wave and turn: dp of these rows (b'), then their gW1 / gb1 (c3)
+        for (int jt = grp - BW_MFMA; jt < n1; jt += BW_HID) {
+            const int j0 = 32 * jt, j1 = (j0 + 32 < a.H) ? j0 + 32 : a.H;
+            // b'. dp[n,j] = relu'(h) * sum_p W2[p,j] ds[p] on the matrix cores, the ascending-p fmaf chain from zero that
+            // v_mfma_f32_32x32x2_f32 is bit for bit (rows = points, columns = j, k = p; a part beyond P adds fma(0, 0, acc)
+            // = acc: the chain starts at +0 and so never holds -0).  The W2T row of a VALU lane would be a broadcast LDS
+            // read per (j, p) and wave; here it is one operand read per instruction.
+            const int jc = j0 + (lane & 31), kh = lane >> 5;
+            const bool jok = jc < a.H;
+            const float *bp = s_w2T + (jok ? jc : 0) * PMAX + kh;
+            for (int nb = 0; nb < cn16; nb += 32) {
+                f16v c = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                const float *ap = s_ds + kh * BW_LD + nb + (lane & 31);
 #pragma unroll
-            for (int kk = kb; kk < kb + 16; kk += 2) {
-                const int n = kk + kh;
-                const float av = (s_kn[n] == pr) ? 1.f : 0.f;
-                float bv = s_w[n] * gcol[3 * n];
-                if (e < 9) bv = bv * s_x[3 * n + xc];
-                c = __builtin_amdgcn_mfma_f32_32x32x2f32(av, cok ? bv : 0.f, c, 0, 0, 0);
+                for (int p = 0; p < PMAX; p += 2) {   // PMAX is even
+                    const bool pok = PP > 0 || p + kh < P;
+                    const float av = pok ? ap[p * BW_LD] : 0.f;
+                    const float bv = (pok && jok) ? bp[p] : 0.f;
+                    c = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, c, 0, 0, 0);
+                }
+                // C/D layout: row (point) = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5), col (j) = lane & 31
+#pragma unroll
+                for (int reg = 0; reg < 16; ++reg) {
+                    const int nn = nb + (reg & 3) + 8 * (reg >> 2) + 4 * kh;
+                    if (jok && nn < a.cpts) {
+                        const float h = s_h[jc * BW_LD + nn];
+                        s_dp[jc * dp_ld + nn] = (nn < cn && h > 0.f) ? c[reg] : 0.f;
+                    }
+                }
             }
-        }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // c3 reads the rows this very wave wrote, other lanes' entries
+            __builtin_amdgcn_wave_barrier();
+            PHASE_TS_WAVE(1, 6, BW_MFMA);
+            // c3. gW1 / gb1 partial from (dp, x): output o = (j, c), two outputs per lane in flight.  c == 3 (gb1) runs the
+            // same chain with x = 1: fmaf(d, 1, acc) is d + acc rounded once, bit for bit the plain sum.
+            {
+                const int ob = 4 * j0 + lane;
+                const bool ok0 = ob < 4 * j1, ok1 = ob + 64 < 4 * j1;
+                const int ja = ok0 ? ob >> 2 : j0, jb = ok1 ? (ob + 64) >> 2 : ja, c = ob & 3, xo = c < 3 ? c : 0;
+                float acc0 = 0.f, acc1 = 0.f;
+                for (int ib = 0; ib < cn16; ib += 16) {
 #pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-            const int prow_p = (reg & 3) + 8 * (reg >> 2) + 4 * kh;
-            if (prow_p < P && cok) prow[off_gRt(a.P, a.H) + (t * a.P + prow_p) * 12 + e] = c[reg];
-        }
-    }
-    PHASE_TS(1, 5);
-    // every lane needs all ds of its point for the hidden gradient
-    float dsr[PMAX];
-#pragma unroll
-    for (int p = 0; p < PMAX; ++p) dsr[p] = (PP > 0 || p < P) ? s_ds[p * BW_LD + lane] : 0.f;
-    __syncthreads();  // the h tile and ds have been consumed by c1
-    PHASE_TS(1, 6);
-    // b'. dp[n,j] = relu'(h) * sum_p W2[p,j] ds[p], written over the h tile
-    const int jq = (a.H + W - 1) / W, j0 = grp * jq, j1 = (j0 + jq < a.H) ? j0 + jq : a.H;
-    for (int j = j0; j < j1; ++j) {
-        float dh = 0.f;
-        if (PMAX % 4 == 0) {
-#pragma unroll
-            for (int p4 = 0; p4 < PMAX / 4; ++p4) {
-                const float4 wv = *(const float4 *)(s_w2T + j * PMAX + 4 * p4);
-                const float w4[4] = {wv.x, wv.y, wv.z, wv.w};
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-                    if (PP > 0 || 4 * p4 + u < P) dh = fmaf(w4[u], dsr[4 * p4 + u], dh);
+                    for (int i = ib; i < ib + 16; ++i) {
+                        const float xs = s_x[3 * i + xo], xv = c < 3 ? xs : 1.0f;
+                        acc0 = fmaf(s_dp[ja * dp_ld + i], xv, acc0);
+                        acc1 = fmaf(s_dp[jb * dp_ld + i], xv, acc1);
+                    }
+                }
+                if (c < 3) {
+                    if (ok0) prow[off_gW1(a.P, a.H) + 3 * ja + c] = acc0;
+                    if (ok1) prow[off_gW1(a.P, a.H) + 3 * jb + c] = acc1;
+                } else {
+                    if (ok0) prow[off_gb1(a.P, a.H) + ja] = acc0;
+                    if (ok1) prow[off_gb1(a.P, a.H) + jb] = acc1;
+                }
             }
-        } else {
-#pragma unroll
-            for (int p = 0; p < PMAX; ++p)
-                if (PP > 0 || p < P) dh = fmaf(s_w2T[j * PMAX + p], dsr[p], dh);
-        }
-        const float h = s_h[j * BW_LD + lane];
-        s_h[j * BW_LD + lane] = (live && h > 0.f) ? dh : 0.f;
-    }
-    __syncthreads();
-    PHASE_TS(1, 7);
-    // c3. gW1 / gb1 partial from (dp, x)
-    for (int o = tid; o < 4 * a.H; o += BS) {
-        const int j = o >> 2, c = o & 3;
-        float acc = 0.f;
-        if (c < 3) {
-            for (int ib = 0; ib < cn16; ib += 16) {
-#pragma unroll
-                for (int i = ib; i < ib + 16; ++i) acc = fmaf(s_h[j * BW_LD + i], s_x[3 * i + c], acc);
-            }
-            prow[off_gW1(a.P, a.H) + 3 * j + c] = acc;
-        } else {
-            for (int ib = 0; ib < cn16; ib += 16) {
-#pragma unroll
-                for (int i = ib; i < ib + 16; ++i) acc += s_h[j * BW_LD + i];
-            }
-            prow[off_gb1(a.P, a.H) + j] = acc;
+            PHASE_TS_WAVE(1, 7, BW_MFMA);
         }
     }
-    PHASE_TS(1, 8);
+    PHASE_SYNC_TS(1, 8);   // diagnostic build only: the workgroup's end = the slower role's
 }
 
 // (2) sum the chunk partials in ascending chunk order; Gram-Schmidt backward for the
@@ -1009,9 +1055,8 @@ static int launch_bwd_block(const BaseBwdArgs *ak, int K, size_t lds, hipStream_
         (hipFuncSetAttribute((const void *)base_bwd_block_kernel<PP, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024) != hipSuccess ||
          hipFuncSetAttribute((const void *)base_bwd_block_kernel<PP, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024) != hipSuccess))
         return REART_ERR_LAUNCH;
-    constexpr int W = (((PP > 0) ? PP : 32) + FW_PG - 1) / FW_PG;
-    if (K == 1) hipLaunchKernelGGL((base_bwd_block_kernel<PP, false>), dim3(ak[0].nchunk), dim3(64 * W), lds, st, reart_batched(ak, 1));
-    else hipLaunchKernelGGL((base_bwd_block_kernel<PP, true>), dim3(ak[0].nchunk, K), dim3(64 * W), lds, st, reart_batched(ak, K));
+    if (K == 1) hipLaunchKernelGGL((base_bwd_block_kernel<PP, false>), dim3(ak[0].nchunk), dim3(64 * BW_WAVES), lds, st, reart_batched(ak, 1));
+    else hipLaunchKernelGGL((base_bwd_block_kernel<PP, true>), dim3(ak[0].nchunk, K), dim3(64 * BW_WAVES), lds, st, reart_batched(ak, K));
     return REART_OK;
 }
 
@@ -1042,9 +1087,15 @@ int reart_base_backward_batch(const BaseBwdArgs *args, const FinalizeAdam *adam,
         }
     }
     const int PMAX = (a0.P == 20 || a0.P == 10 || a0.P == 8) ? a0.P : 32;
-    const size_t lds = sizeof(float) * ((size_t)(a0.H + PMAX) * BW_LD + RED_CHUNK * 5 + PMAX + 4 +
-                                        (size_t)a0.B * RED_CHUNK * 3 + (size_t)a0.H * PMAX + 12 * (size_t)a0.B * a0.P);
+    size_t lds = sizeof(float) * ((size_t)(a0.H + PMAX) * BW_LD + RED_CHUNK * 5 + PMAX + 4 +
+                                  (size_t)a0.B * RED_CHUNK * 3 + (size_t)a0.H * PMAX + 12 * (size_t)a0.B * a0.P +
+                                  (size_t)PMAX * BW_LD);
     if (lds > 152 * 1024) return REART_ERR_UNSUPPORTED;
+    // the hidden gradient gets a tile of its own ([H][cpts + 1]) where it fits: then the tail's roles overlap
+    const size_t lds_dp = sizeof(float) * (size_t)a0.H * (a0.cpts + 1);
+    const int dp_sep = lds + lds_dp <= 152 * 1024;
+    if (dp_sep) lds += lds_dp;
+    for (int k = 0; k < K; ++k) ak[k].dp_sep = dp_sep;
     int rc;
     switch (a0.P) {
         case 20: rc = launch_bwd_block<20>(ak, K, lds, st); break;

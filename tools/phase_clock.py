@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Shader-clock stamps inside base_fwd_kernel / base_bwd_block_kernel (workgroup 1, thread 0).
+"""Shader-clock stamps inside base_fwd_kernel / base_bwd_block_kernel (workgroup 1; thread 0, and lane 0 of one wave per role).
     make -C reart_amd/csrc stats && REART_LIB=reart_amd/csrc/libreart_hip_stats.so python tools/phase_clock.py"""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -22,8 +22,14 @@ for rep in range(3):
             TICK_US = wall / (ts[n - 1] - ts[0])
             print(f"{name}: s_memtime runs at {1e-3 / TICK_US:.3f} GHz here ({ts[n - 1] - ts[0]} ticks in {wall:.2f} us)")
         if w == 1:
-            x = v[16:32]
-            print("bwd prologue (serialised): hT tile", x[9] - x[0], "G tile", x[10] - x[9], "rt", x[11] - x[10], "W2T", x[12] - x[11], "rest", x[1] - x[12])
+            # stamps 0..3 are thread 0's (tile loads | a. dw | b. softmax backward, ds complete); behind stamp 3 the waves split by
+            # role and each role stamps its own end: 4 gR|gt tile (wave 0), 5 gW2 tile (first wave that has one), 6 / 7 hidden
+            # gradient dp, then gW1 / gb1 (first wave of that role); 8 after a closing barrier = the slower role
+            us = lambda k0, k1: (ts[k1] - ts[k0]) * TICK_US
+            print(f"bwd_block (us): tile loads {us(0, 1):.2f} | a. dw {us(1, 2):.2f} | b. ds {us(2, 3):.2f} | roles side by side from stamp 3: "
+                  f"gR|gt tile ends +{us(3, 4):.2f}, gW2 tile ends +{us(3, 5):.2f}, dp ends +{us(3, 6):.2f}, gW1/gb1 end +{us(3, 7):.2f}, "
+                  f"all waves done +{us(3, 8):.2f} | total {us(0, 8):.2f} us: the lifetime of ONE workgroup (block 1)")
+            continue
         print(name, "deltas (s_memtime ticks):", [ts[i + 1] - ts[i] for i in range(n - 1)], "total", ts[n - 1] - ts[0],
               f"= {(ts[n - 1] - ts[0]) * TICK_US:.2f} us: the lifetime of ONE workgroup (block 1)")
     fz = v[8:16]          # [0][8] body start, [9] body end, [10] after the ticket, [14] kernel entry (before the bookkeeping's speculative part)
