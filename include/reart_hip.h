@@ -63,7 +63,8 @@ const char *reart_status_string(int status);
  * Distance contract: ((d0*d0)+(d1*d1))+(d2*d2)+... with dc = p1[c]-p2[c], summed in
  * ascending c, fp32, no FMA; ties -> lowest j.
  * 1 <= K <= REART_MAX_K_LIST.  D = 3: K <= REART_MAX_K runs the register-list kernels,
- * larger K the LDS-list kernel; D != 3: the any-D LDS-list kernel (same result contract).
+ * larger K the LDS-list kernel; D != 3: the any-D LDS-list kernel of csrc/knn_anyd.hip (same
+ * result contract).
  * workspace (SoA target image + per-slice partial results; D != 3 also a query image):
  *   reart_knn_points_workspace_bytes_d(N,P1,P2,D,K) bytes (0 when D or K is out of range);
  *   reart_knn_points_workspace_bytes(N,P1,P2,K) is the D = 3 size. */
@@ -83,7 +84,8 @@ int reart_knn_points_idx(const float *p1, const float *p2,
  *   ascending by (distance, index); rows >= lengths1[n] and slots >= lengths2[n] are zero.
  * Distance contract: ((d0*d0)+(d1*d1))+(d2*d2)+... with dc = p1[c]-p2[c], summed in ascending
  * c, every operation a correctly rounded fp64 one: no FMA, no matrix cores.  NaN / Inf
- * coordinates are outside the contract.  One kernel serves every D and K (csrc/knn_f64.hip).
+ * coordinates are outside the contract.  One kernel serves every D and K (csrc/knn_anyd.hip,
+ * the any-D search in double).
  * There is no float64 backward (the upstream backward is float-only).
  * workspace: reart_knn_points_workspace_bytes_f64(N,P1,P2,D,K) bytes (0 when D or K is out of range). */
 size_t reart_knn_points_workspace_bytes_f64(int N, int P1, int P2, int D, int K);

@@ -154,13 +154,11 @@ size_t reart_knn_list_workspace_bytes(int N, int P1, int P2, int K);
 int reart_knn_list_run(const float *q, const float *t, const int64_t *lenq, const int64_t *lent, int N, int P1,
                        int P2, int K, int euclidean, float *dists, int64_t *idx, void *workspace,
                        size_t workspace_bytes, hipStream_t st);
-// ---- K-NN for D != 3, 1 <= D <= REART_MAX_D (knn_dim.hip) -----------------------------------
-int reart_knn_dim_run(const float *q, const float *t, const int64_t *lenq, const int64_t *lent, int N, int P1, int P2,
-                      int D, int K, int euclidean, float *dists, int64_t *idx, void *workspace, size_t workspace_bytes,
-                      hipStream_t st);
-int reart_knn_dim_backward_launch(const float *p1, const float *p2, const int64_t *lengths1, const int64_t *lengths2,
-                                  const int64_t *idx, const float *grad_dists, int N, int P1, int P2, int D, int K,
-                                  float *grad_p1, float *grad_p2, int *workspace, hipStream_t st);
+// ---- K-NN for 1 <= D <= REART_MAX_D, T = float (D != 3) or double (knn_anyd.hip) -----------
+template <class T>
+int reart_knn_anyd_run(const T *q, const T *t, const int64_t *lenq, const int64_t *lent, int N, int P1, int P2, int D,
+                       int K, int euclidean, T *dists, int64_t *idx, void *workspace, size_t workspace_bytes,
+                       hipStream_t st);
 #ifndef NN_BOX
 #define NN_BOX 16   // targets per bounding box of the block-skip test (16, 32 or 64; measured 4545 / 4438 / 4321 it/s)
 #endif

@@ -2,7 +2,7 @@
 //
 // Replaces chamferdist._C.knn_points_idx / knn_points_backward (reference
 // utils/chamfer.py:174,206-208) and knn_cuda.KNN.forward (run_robot.py:65-66).
-// These kernels serve D = 3; the entry points send other D to knn_dim.hip.
+// These kernels serve float32 at D = 3; the entry points send other D and float64 to knn_anyd.hip.
 //
 // Design (DESIGN.md section "K-NN"):
 //   * The kernel is fp32-VALU bound (8 flop per pair against 24 B per point), so the
@@ -24,9 +24,6 @@
 #include "internal.h"
 #include "blocksort.h"
 #include <math.h>
-
-
-
 
 // ---------------------------------------------------------------------------------
 // AoS [n][P][3]  ->  SoA [n][3][Ppad], entries j >= length padded with +INF
@@ -459,28 +456,55 @@ extern "C" size_t reart_chamfer_bidir_workspace_bytes(int N, int P) {
     return pl.total;
 }
 
-extern "C" int reart_knn_points_idx(const float *p1, const float *p2, const int64_t *lengths1,
-                                    const int64_t *lengths2, int N, int P1, int P2, int D, int K,
-                                    float *dists, int64_t *idx, void *workspace,
-                                    size_t workspace_bytes, void *stream) {
+// The register search above serves float32 at D = 3, K <= REART_MAX_K; every other problem goes to knn_anyd.hip or
+// knn_list.hip.  q [N,P1,D] queries, t [N,P2,D] targets, all sizes >= 1 and within the ceilings.
+static int knn_route(const float *q, const float *t, const int64_t *lenq, const int64_t *lent, int N, int P1, int P2,
+                     int D, int K, int euclidean, float *dists, int64_t *idx, void *workspace, size_t workspace_bytes,
+                     hipStream_t st) {
+    if (D != 3)
+        return reart_knn_anyd_run(q, t, lenq, lent, N, P1, P2, D, K, euclidean, dists, idx, workspace, workspace_bytes, st);
+    if (K > REART_MAX_K)
+        return reart_knn_list_run(q, t, lenq, lent, N, P1, P2, K, euclidean, dists, idx, workspace, workspace_bytes, st);
+    return reart_knn_run(1, &q, &t, &lenq, &lent, N, &P1, &P2, K, euclidean, &dists, &idx, workspace, workspace_bytes, st);
+}
+static int knn_route(const double *q, const double *t, const int64_t *lenq, const int64_t *lent, int N, int P1, int P2,
+                     int D, int K, int euclidean, double *dists, int64_t *idx, void *workspace, size_t workspace_bytes,
+                     hipStream_t st) {
+    return reart_knn_anyd_run(q, t, lenq, lent, N, P1, P2, D, K, euclidean, dists, idx, workspace, workspace_bytes, st);
+}
+
+// reart_knn_points_idx (T = float) and reart_knn_points_idx_f64 (T = double)
+template <class T>
+static int knn_points_idx(const T *p1, const T *p2, const int64_t *lengths1, const int64_t *lengths2, int N, int P1,
+                          int P2, int D, int K, T *dists, int64_t *idx, void *workspace, size_t workspace_bytes,
+                          hipStream_t st) {
     if (N < 0 || P1 < 0 || P2 < 0 || K < 1 || D < 1) return REART_ERR_INVALID_ARG;
     if (D > REART_MAX_D || K > REART_MAX_K_LIST) return REART_ERR_UNSUPPORTED;
     if (N == 0 || P1 == 0) return REART_OK;
     if (!dists || !idx) return REART_ERR_INVALID_ARG;
-    hipStream_t st = (hipStream_t)stream;
     if (P2 == 0) {  // nothing to search: zero padded outputs (utils/chamfer.py:163-170)
-        if (hipMemsetAsync(dists, 0, sizeof(float) * (size_t)N * P1 * K, st) != hipSuccess ||
+        if (hipMemsetAsync(dists, 0, sizeof(T) * (size_t)N * P1 * K, st) != hipSuccess ||
             hipMemsetAsync(idx, 0, sizeof(int64_t) * (size_t)N * P1 * K, st) != hipSuccess)
             return REART_ERR_LAUNCH;
         return REART_OK;
     }
     if (!p1 || !p2) return REART_ERR_INVALID_ARG;
-    if (D != 3)
-        return reart_knn_dim_run(p1, p2, lengths1, lengths2, N, P1, P2, D, K, 0, dists, idx, workspace, workspace_bytes, st);
-    if (K > REART_MAX_K)
-        return reart_knn_list_run(p1, p2, lengths1, lengths2, N, P1, P2, K, 0, dists, idx, workspace, workspace_bytes, st);
-    const int64_t *lq[1] = {lengths1}, *lt[1] = {lengths2};
-    return reart_knn_run(1, &p1, &p2, lq, lt, N, &P1, &P2, K, 0, &dists, &idx, workspace, workspace_bytes, st);
+    return knn_route(p1, p2, lengths1, lengths2, N, P1, P2, D, K, 0, dists, idx, workspace, workspace_bytes, st);
+}
+
+extern "C" int reart_knn_points_idx(const float *p1, const float *p2, const int64_t *lengths1,
+                                    const int64_t *lengths2, int N, int P1, int P2, int D, int K,
+                                    float *dists, int64_t *idx, void *workspace,
+                                    size_t workspace_bytes, void *stream) {
+    return knn_points_idx(p1, p2, lengths1, lengths2, N, P1, P2, D, K, dists, idx, workspace, workspace_bytes,
+                          (hipStream_t)stream);
+}
+
+extern "C" int reart_knn_points_idx_f64(const double *p1, const double *p2, const int64_t *lengths1,
+                                        const int64_t *lengths2, int N, int P1, int P2, int D, int K, double *dists,
+                                        int64_t *idx, void *workspace, size_t workspace_bytes, void *stream) {
+    return knn_points_idx(p1, p2, lengths1, lengths2, N, P1, P2, D, K, dists, idx, workspace, workspace_bytes,
+                          (hipStream_t)stream);
 }
 
 extern "C" int reart_chamfer_bidir(const float *x, const float *y, int N, int P, float *d_xy,
@@ -505,14 +529,8 @@ extern "C" int reart_knn_cuda(const float *ref, const float *query, int B, int n
     if (k > nr) return REART_ERR_INVALID_ARG;  // knn_cuda asserts k <= number of references
     if (B == 0 || nq == 0) return REART_OK;
     if (!ref || !query || !dist || !idx) return REART_ERR_INVALID_ARG;
-    if (D != 3)
-        return reart_knn_dim_run(query, ref, nullptr, nullptr, B, nq, nr, D, k, euclidean ? 1 : 0, dist, idx, workspace,
-                                 workspace_bytes, (hipStream_t)stream);
-    if (k > REART_MAX_K)
-        return reart_knn_list_run(query, ref, nullptr, nullptr, B, nq, nr, k, euclidean ? 1 : 0, dist, idx, workspace,
-                                  workspace_bytes, (hipStream_t)stream);
-    return reart_knn_run(1, &query, &ref, nullptr, nullptr, B, &nq, &nr, k, euclidean ? 1 : 0, &dist, &idx,
-                   workspace, workspace_bytes, (hipStream_t)stream);
+    return knn_route(query, ref, nullptr, nullptr, B, nq, nr, D, k, euclidean ? 1 : 0, dist, idx, workspace,
+                     workspace_bytes, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------
@@ -522,50 +540,57 @@ extern "C" int reart_knn_cuda(const float *ref, const float *query, int B, int n
 // One workgroup per batch element does a counting sort of the (i,k) pairs by target
 // index in the caller's workspace, sorts every bucket ascending and accumulates in that
 // order -- the same order the CPU loop uses, with no floating-point atomics.
+// DS = 3: D = 3, the three sums of a point in registers, one pass over its pairs.  DS = 0: any D, read at run
+// time, one pass per component.  Every component sums in the same order either way: grad_p1 over k ascending,
+// grad_p2 over the bucket in ascending (i, k), v = (2g) * diff, no FMA.
 // ---------------------------------------------------------------------------------
-#define BWD_BS RS_BS
-
-__global__ __launch_bounds__(BWD_BS) void knn_bwd_kernel(
+template <int DS>
+__global__ __launch_bounds__(RS_BS) void knn_bwd_kernel(
     const float *__restrict__ p1, const float *__restrict__ p2, const int64_t *__restrict__ len1,
-    const int64_t *__restrict__ len2, const int64_t *__restrict__ idx,
-    const float *__restrict__ gd, int P1, int P2, int K, int nbits, float *__restrict__ g1,
-    float *__restrict__ g2, int *__restrict__ ws) {
+    const int64_t *__restrict__ len2, const int64_t *__restrict__ idx, const float *__restrict__ gd, int P1, int P2,
+    int Drt, int K, int nbits, float *__restrict__ g1, float *__restrict__ g2, int *__restrict__ ws) {
     __shared__ int s_cnt[RS_DIG * RS_BS];
     __shared__ int s_wave[RS_BS / 64];
+    constexpr int CH = DS ? DS : 1;   // components per pass
+    const int D = DS ? DS : Drt;
     const int n = blockIdx.x, tid = threadIdx.x;
     int n1 = len1 ? (int)len1[n] : P1;
     int n2 = len2 ? (int)len2[n] : P2;
     n1 = n1 < P1 ? n1 : P1;
     n2 = n2 < P2 ? n2 : P2;
     const int kk = K < n2 ? K : n2;
-    p1 += (size_t)n * P1 * 3; p2 += (size_t)n * P2 * 3;
+    p1 += (size_t)n * P1 * D; p2 += (size_t)n * P2 * D;
     idx += (size_t)n * P1 * K; gd += (size_t)n * P1 * K;
-    g1 += (size_t)n * P1 * 3; g2 += (size_t)n * P2 * 3;
+    g1 += (size_t)n * P1 * D; g2 += (size_t)n * P2 * D;
     int *cnt = ws + (size_t)n * (2 * (size_t)P2 + 2 * (size_t)P1 * K);  // [P2]
     int *off = cnt + P2;                                                 // [P2]
     int *bufA = off + P2, *bufB = bufA + (size_t)P1 * K;                 // [P1*K] each
 
-    for (int j = tid; j < P2; j += BWD_BS) cnt[j] = 0;
+    for (int j = tid; j < P2; j += RS_BS) cnt[j] = 0;
     __syncthreads();
-    // grad_p1 and bucket counts (integer atomics: order-independent result)
-    for (int i = tid; i < P1; i += BWD_BS) {
-        float ax = 0.f, ay = 0.f, az = 0.f;
-        if (i < n1) {
-            const float x = p1[3 * i], y = p1[3 * i + 1], z = p1[3 * i + 2];
-            for (int k = 0; k < kk; ++k) {
-                const int j = (int)idx[(size_t)i * K + k];
-                const float c = 2.0f * gd[(size_t)i * K + k];
-                ax += c * (x - p2[3 * j]);
-                ay += c * (y - p2[3 * j + 1]);
-                az += c * (z - p2[3 * j + 2]);
-                atomicAdd(&cnt[j], 1);
+    // grad_p1 and, in the first pass, bucket counts (integer atomics: order-independent result)
+    for (int i = tid; i < P1; i += RS_BS) {
+        const float *x = p1 + (size_t)i * D;
+        for (int c0 = 0; c0 < D; c0 += CH) {
+            float a[CH];
+#pragma unroll
+            for (int u = 0; u < CH; ++u) a[u] = 0.f;
+            if (i < n1) {
+                for (int k = 0; k < kk; ++k) {
+                    const int j = (int)idx[(size_t)i * K + k];
+                    const float cf = 2.0f * gd[(size_t)i * K + k];
+#pragma unroll
+                    for (int u = 0; u < CH; ++u) a[u] += cf * (x[c0 + u] - p2[(size_t)j * D + c0 + u]);
+                    if (c0 == 0) atomicAdd(&cnt[j], 1);
+                }
             }
+#pragma unroll
+            for (int u = 0; u < CH; ++u) g1[(size_t)i * D + c0 + u] = a[u];
         }
-        g1[3 * i] = ax; g1[3 * i + 1] = ay; g1[3 * i + 2] = az;
     }
     __syncthreads();
     // exclusive scan of cnt -> off
-    const int chunk = (P2 + BWD_BS - 1) / BWD_BS;
+    const int chunk = (P2 + RS_BS - 1) / RS_BS;
     const int c0 = tid * chunk < P2 ? tid * chunk : P2, c1 = (c0 + chunk < P2) ? c0 + chunk : P2;
     int tot = 0;
     for (int j = c0; j < c1; ++j) tot += cnt[j];
@@ -576,19 +601,23 @@ __global__ __launch_bounds__(BWD_BS) void knn_bwd_kernel(
     const int *sorted = block_stable_sort_ids(M, nbits, bufA, bufB, s_cnt, s_wave, [&](int e) {
         return (int)idx[(size_t)(e / kk) * K + (e % kk)];
     });
-    for (int j = tid; j < P2; j += BWD_BS) {
-        const int o = off[j], c = cnt[j];
-        float ax = 0.f, ay = 0.f, az = 0.f;
-        const float x = p2[3 * j], y = p2[3 * j + 1], z = p2[3 * j + 2];
-        for (int a = 0; a < c; ++a) {
-            const int e = sorted[o + a];
-            const int i = e / kk, k = e % kk;
-            const float cf = 2.0f * gd[(size_t)i * K + k];
-            ax -= cf * (p1[3 * i] - x);
-            ay -= cf * (p1[3 * i + 1] - y);
-            az -= cf * (p1[3 * i + 2] - z);
+    for (int j = tid; j < P2; j += RS_BS) {
+        const int o = off[j], cj = cnt[j];
+        const float *y = p2 + (size_t)j * D;
+        for (int c0 = 0; c0 < D; c0 += CH) {
+            float a[CH];
+#pragma unroll
+            for (int u = 0; u < CH; ++u) a[u] = 0.f;
+            for (int m = 0; m < cj; ++m) {
+                const int e = sorted[o + m];
+                const int i = e / kk, k = e % kk;
+                const float cf = 2.0f * gd[(size_t)i * K + k];
+#pragma unroll
+                for (int u = 0; u < CH; ++u) a[u] -= cf * (p1[(size_t)i * D + c0 + u] - y[c0 + u]);
+            }
+#pragma unroll
+            for (int u = 0; u < CH; ++u) g2[(size_t)j * D + c0 + u] = a[u];
         }
-        g2[3 * j] = ax; g2[3 * j + 1] = ay; g2[3 * j + 2] = az;
     }
 }
 
@@ -617,11 +646,8 @@ extern "C" int reart_knn_points_backward(const float *p1, const float *p2, const
         return REART_ERR_INVALID_ARG;
     if (workspace_bytes < reart_knn_points_backward_workspace_bytes(N, P1, P2, K))
         return REART_ERR_INVALID_ARG;
-    if (D != 3)
-        return reart_knn_dim_backward_launch(p1, p2, lengths1, lengths2, idx, grad_dists, N, P1, P2, D, K, grad_p1,
-                                             grad_p2, (int *)workspace, st);
-    hipLaunchKernelGGL(knn_bwd_kernel, dim3(N), dim3(BWD_BS), 0, st, p1, p2, lengths1, lengths2, idx,
-                       grad_dists, P1, P2, K, reart_bits_for(P2), grad_p1, grad_p2, (int *)workspace);
+    hipLaunchKernelGGL(D == 3 ? knn_bwd_kernel<3> : knn_bwd_kernel<0>, dim3(N), dim3(RS_BS), 0, st, p1, p2, lengths1,
+                       lengths2, idx, grad_dists, P1, P2, D, K, reart_bits_for(P2), grad_p1, grad_p2, (int *)workspace);
     REART_CHECK_LAUNCH();
     return REART_OK;
 }

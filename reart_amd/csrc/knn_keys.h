@@ -1,5 +1,5 @@
-// reart_amd/csrc/knn_keys.h -- the per-query ranked list of the LDS-list K-NN kernels (knn_list.hip, knn_dim.hip,
-// knn_f64.hip).
+// reart_amd/csrc/knn_keys.h -- the per-query ranked list of the LDS-list K-NN kernels (knn_list.hip,
+// knn_anyd.hip).
 //
 // A list holds a query's K best targets so far as K ascending keys in LDS.  The fp32 searches use a 64-bit key,
 // (bits of the fp32 distance) << 32 | j; the fp64 search uses KeyF64, the pair (bits of the fp64 distance, j) in
@@ -7,7 +7,7 @@
 // A wave that found candidates (keys below the list's K-th key) sorts them across its 64 lanes and merges them in:
 // every candidate and every list entry finds its new slot by counting the other side's smaller keys (binary
 // searches), and entries pushed past K fall off.  The helpers are templates over the key type; a key type brings
-// kl_shfl_xor, kl_cas, operator< and a kl_none specialisation (the all-ones key, above every real key).
+// kl_sel, kl_shfl_xor, kl_cas, operator< and a kl_none specialisation (the all-ones key, above every real key).
 #pragma once
 #include "common.h"
 
@@ -24,6 +24,7 @@ __device__ __forceinline__ bool operator<(const KeyF64 &a, const KeyF64 &b) {
 }
 
 // c ? a : b, per component (a select of whole structs goes through scratch memory)
+__device__ __forceinline__ u64 kl_sel(bool c, u64 a, u64 b) { return c ? a : b; }
 __device__ __forceinline__ KeyF64 kl_sel(bool c, KeyF64 a, KeyF64 b) {
     return KeyF64{c ? a.d : b.d, c ? a.j : b.j, 0u};
 }

@@ -1,5 +1,5 @@
-"""GPU parity of the K-nearest search and its backward for points of any dimension D != 3 (csrc/knn_dim.hip) against
-the CPU oracle: bit-exact indices, distances and gradients through knn_points / chamferdist_C / ChamferDistance /
+"""GPU parity of the K-nearest search and its backward for points of any dimension D != 3 (csrc/knn_anyd.hip,
+knn_bwd_kernel of csrc/knn.hip) against the CPU oracle: bit-exact indices, distances and gradients through knn_points / chamferdist_C / ChamferDistance /
 knn_cuda.KNN, the reference's own mutual-nearest-descriptor matches, and the D ceiling."""
 import os
 

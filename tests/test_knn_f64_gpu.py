@@ -1,4 +1,4 @@
-"""GPU parity of the float64 K-nearest search (csrc/knn_f64.hip, reart_knn_points_idx_f64) against the float64 numpy
+"""GPU parity of the float64 K-nearest search (csrc/knn_anyd.hip, reart_knn_points_idx_f64) against the float64 numpy
 restatement of its contract (tests/knn_f64_ref.py): bit-exact indices and distances through chamferdist_C /
 knn_points / knn_gather / ChamferDistance, orders that only float64 resolves, ties and ragged lengths, wide launches,
 gradients through the float32 backward, and the dtype / size errors."""

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""GPU timing of the K-nearest search for points of any dimension D != 3 (csrc/knn_dim.hip); prints one JSON line.
+"""GPU timing of the K-nearest search for points of any dimension D != 3 (csrc/knn_anyd.hip); prints one JSON line.
 
   knn_points     N in {1, 8}, P1 = P2 = 4096, D in {2, 6, 16, 64, 128, 256}, K in {1, 8, 64, 1024}
   KNN(k=1)       19 pairs of 4096 x 64-D descriptors (transpose_mode=False, [19, 64, 4096]: the matching="mnn" shape)

@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
-"""GPU timing of the float64 K-nearest search (csrc/knn_f64.hip); prints one JSON line.
+"""GPU timing of the float64 K-nearest search (csrc/knn_anyd.hip, float64); prints one JSON line.
 
   knn_points     N in {1, 8}, P1 = P2 = 4096, D in {3, 16, 64, 256}, K in {1, 8, 64, 1024}
 
 each row times the float64 search, the float32 search on the same clouds cast to float32 (knn.hip / knn_list.hip at
-D = 3, knn_dim.hip otherwise) and float64 torch.cdist(...).topk(K, largest=False) on the same GPU (speed only: its
+D = 3, knn_anyd.hip otherwise) and float64 torch.cdist(...).topk(K, largest=False) on the same GPU (speed only: its
 rounding differs from the search's contract).  Times are device-event means over `--reps` calls after `--warmup`
 calls, in milliseconds.
 Usage: python tools/bench_knn_f64.py [--reps 5] [--warmup 2]"""
