@@ -340,22 +340,24 @@ int reart_relax_step(const reart_relax_config *cfg, const reart_relax_buffers *b
                      void *workspace, size_t workspace_bytes, void *stream);
 /* K independent instances of ONE shape (same N, B, P, H, M_max and switches in every cfgs[k]; clouds, parameters,
  * canonical index, seed and learning rates are each instance's own) advance one iteration in the five launches of a
- * single instance: every kernel runs once with K argument blocks, instance k on row k of its grid.  cfgs / bufs are
+ * single instance: every kernel runs once with K argument blocks, instance k on plane k of its grid.  cfgs / bufs are
  * arrays of K, workspaces[k] is instance k's workspace (each prepared with reart_relax_prepare).  Each instance
  * computes exactly what reart_relax_step computes for it.  This is how a sweep over canonical frames
  * (/root/reference/README.md:60, run_robot.py: one process per cano_idx) fills the chip: one instance occupies a fraction
  * of the 256 compute units and is a chain of dependent launches.  Box-pruned search paths: Chamfer + flow loss (five
  * launches), Chamfer only, and the assignment loss with or without flow (run_robot.py:164-192: the pairs in each
- * instance's assign_map); every instance in the same mode, 1 <= K <= 6; REART_ERR_UNSUPPORTED / REART_ERR_INVALID_ARG
- * otherwise. */
+ * instance's assign_map); every instance in the same mode, 1 <= K <= 6.  Any other search path (use_grid,
+ * search_mode 1, use_boxes 0, tune_cloud): REART_ERR_UNSUPPORTED, for K = 1 as well; instances that differ in shape or
+ * mode, or K out of range: REART_ERR_INVALID_ARG. */
 int reart_relax_step_batch(const reart_relax_config *cfgs, const reart_relax_buffers *bufs, void *const *workspaces,
                            size_t workspace_bytes, int K, void *stream);
 /* measurement aid: the same sequence with hipEvents between phases on `stream`; synchronises
  * and ADDS per-phase milliseconds to the HOST array h_ms[REART_RELAX_PHASES]:
- * 0 forward, 1 flow K=3 search, 2 flow blend, 3 Chamfer K=1 search, 4 Chamfer merge + gradient,
- * 5 model backward + Adam + bookkeeping, 6-7 unused.  In the default configuration (pruned searches,
- * flow loss on) both searches share ONE launch and both consumers share ONE launch: phases 1-2 are
- * then empty, 3 = the search launch, 4 = the consumer launch.  Always serial (no fork/join); event
+ * 0 forward, 1 flow K=3 search, 2 flow blend, 3 Chamfer K=1 search, 4 Chamfer merge + gradient (or the
+ * assignment loss), 5 model backward + Adam + bookkeeping, 6-7 unused.  With the pruned searches (the
+ * default) every search of the iteration is ONE launch, and it is timed as phase 1: phase 3 is then
+ * empty.  With the flow loss on as well (the default configuration) both consumers share ONE launch:
+ * 2 is empty too, 1 = the search launch, 4 = the consumer launch.  Always serial (no fork/join); event
  * pairs around single launches over-read short kernels by a few microseconds. */
 #define REART_RELAX_PHASES 8
 int reart_relax_step_timed(const reart_relax_config *cfg, const reart_relax_buffers *bufs,

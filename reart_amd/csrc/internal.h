@@ -48,8 +48,10 @@ struct AdamSeg { float *p; const float *g; float *m; float *v; int n; float lr; 
 struct AdamArgs { AdamSeg seg[8]; int nseg; float beta1, beta2, eps; const int64_t *step_ptr; int step; };
 
 // Several independent instances of one shape in ONE launch (relax batch): the kernels of the fused step take their
-// argument block K times and pick theirs by blockIdx.y.  6 blocks of the largest (SearchArgs) stay within the 4 KB
-// kernel-argument segment with room for the runtime's hidden arguments.
+// argument block K times and pick theirs by the grid's last dimension (blockIdx.y where the kernel's own grid is a row,
+// blockIdx.z for the stand-alone consumers of step.hip, whose own grid is a plane); with one instance they are instantiated
+// to read block 0.  6 blocks of the largest (SearchArgs) stay within the 4 KB kernel-argument segment with room for the
+// runtime's hidden arguments.
 #define REART_BATCH_MAX 6
 template <class A>
 struct Batched { A a[REART_BATCH_MAX]; };
@@ -59,8 +61,7 @@ static inline Batched<A> reart_batched(const A *a, int K) {
     for (int k = 0; k < K && k < REART_BATCH_MAX; ++k) b.a[k] = a[k];
     return b;
 }
-int reart_base_forward_ex(const BaseFwdArgs &a, hipStream_t st);
-int reart_base_forward_batch(const BaseFwdArgs *a, int K, hipStream_t st);          // same shapes, K <= REART_BATCH_MAX
+int reart_base_forward_launch(const BaseFwdArgs *a, int K, hipStream_t st);         // same shapes, 1 <= K <= REART_BATCH_MAX
 struct FinalizeAdam {
     int enabled;
     float *W1, *b1, *W2, *p6d, *pt;   // parameters (updated in place)
@@ -83,10 +84,8 @@ struct StepBook {
     int ring, n_iter;
     float lambda_flow, fixed_tau, end_tau, start_tau, beta1, beta2;
 };
-int reart_base_backward_batch(const BaseBwdArgs *args, const FinalizeAdam *adam, const StepBook *book, void *const *workspaces,
-                              size_t workspace_bytes, int K, hipStream_t st);
-int reart_base_backward_ex(BaseBwdArgs a, const FinalizeAdam *adam, const StepBook *book, void *workspace,
-                           size_t workspace_bytes, hipStream_t st);
+int reart_base_backward_launch(const BaseBwdArgs *args, const FinalizeAdam *adam, const StepBook *book, void *const *workspaces,
+                               size_t workspace_bytes, int K, hipStream_t st);     // adam / book: arrays of K, or NULL
 #ifdef __HIPCC__
 // cosine schedule of utils/model_utils.py:33-37 evaluated in double like the host code
 __device__ __forceinline__ float reart_tau_schedule(long cur_iter, int n_iter, float end_t, float start_t) {

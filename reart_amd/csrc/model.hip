@@ -403,7 +403,8 @@ static void launch_base_fwd(const BaseFwdArgs *a, int K, hipStream_t st) {
     else launch_base_fwd_t<PP, true>(a, K, st);
 }
 
-static int dispatch_base_fwd(const BaseFwdArgs *ak, int K, hipStream_t st) {
+// the forward's one entry: K instances of one shape in one launch (K = 1: the C ABI below and the single fused step)
+int reart_base_forward_launch(const BaseFwdArgs *ak, int K, hipStream_t st) {
     if (K < 1 || K > REART_BATCH_MAX) return REART_ERR_INVALID_ARG;
     const BaseFwdArgs &a = ak[0];
     for (int k = 1; k < K; ++k)      // one launch geometry for all
@@ -436,7 +437,7 @@ extern "C" int reart_base_forward(const float *cano, int N, int P, int B, const 
     a.gumbel = gumbel; a.tau = tau; a.N = N; a.P = P; a.B = B; a.H = H; a.Npad = 0;
     a.out = out; a.seg_part = seg_part; a.trans_list = trans_list; a.yT = yT; a.hT = hT;
     a.hard_idx = hard_idx;
-    return dispatch_base_fwd(&a, 1, (hipStream_t)stream);
+    return reart_base_forward_launch(&a, 1, (hipStream_t)stream);
 }
 
 // The production noise stream, exported: out[n][p] = the Gumbel sample the forward kernel draws for (point n, part p) in
@@ -463,10 +464,6 @@ extern "C" int reart_gumbel_noise(uint64_t seed, int64_t iter, int N, int P, flo
     REART_CHECK_LAUNCH();
     return REART_OK;
 }
-
-// entry used by the fused step (step.hip)
-int reart_base_forward_ex(const BaseFwdArgs &a, hipStream_t st) { return dispatch_base_fwd(&a, 1, st); }
-int reart_base_forward_batch(const BaseFwdArgs *a, int K, hipStream_t st) { return dispatch_base_fwd(a, K, st); }
 
 // ------------------------------------------------------------------------------- backward
 // layout of one partial row / of the reduced gradient vector
@@ -1060,10 +1057,11 @@ static int launch_bwd_block(const BaseBwdArgs *ak, int K, size_t lds, hipStream_
     return REART_OK;
 }
 
-// K instances of one shape (K = 1: the plain entry); workspaces[k] is instance k's backward workspace.
-// a.rt_table == NULL: the table is built into the workspace first (one extra tiny launch per instance)
-int reart_base_backward_batch(const BaseBwdArgs *args, const FinalizeAdam *adam, const StepBook *book, void *const *workspaces,
-                              size_t workspace_bytes, int K, hipStream_t st) {
+// The backward's one entry: K instances of one shape (K = 1: the C ABI below and the single fused step); workspaces[k] is
+// instance k's backward workspace.  a.rt_table == NULL: the table is built into the workspace first (one extra tiny launch
+// per instance)
+int reart_base_backward_launch(const BaseBwdArgs *args, const FinalizeAdam *adam, const StepBook *book, void *const *workspaces,
+                               size_t workspace_bytes, int K, hipStream_t st) {
     if (K < 1 || K > REART_BATCH_MAX) return REART_ERR_INVALID_ARG;
     BaseBwdArgs ak[REART_BATCH_MAX];
     for (int k = 0; k < K; ++k) ak[k] = args[k];
@@ -1119,12 +1117,6 @@ int reart_base_backward_batch(const BaseBwdArgs *args, const FinalizeAdam *adam,
     return REART_OK;
 }
 
-int reart_base_backward_ex(BaseBwdArgs a, const FinalizeAdam *adam, const StepBook *book, void *workspace,
-                           size_t workspace_bytes, hipStream_t st) {
-    void *w[1] = {workspace};
-    return reart_base_backward_batch(&a, adam, book, w, workspace_bytes, 1, st);
-}
-
 extern "C" int reart_base_backward(const float *cano, int N, int P, int B, const float *W1,
                                    const float *b1, const float *W2, int H, const float *prop6d,
                                    const float *propt, const float *yT, const float *hT,
@@ -1140,7 +1132,7 @@ extern "C" int reart_base_backward(const float *cano, int N, int P, int B, const
     a.cano = cano; a.W2 = W2; a.p6d = prop6d; a.pt = propt; a.yT = yT; a.hT = hT;
     a.hard_idx = hard_idx; a.tau = tau; a.G = G; a.N = N; a.P = P; a.B = B; a.H = H;
     a.gW1 = gW1; a.gb1 = gb1; a.gW2 = gW2; a.g6d = g6d; a.gt = gt;
-    return reart_base_backward_ex(a, nullptr, nullptr, workspace, workspace_bytes, (hipStream_t)stream);
+    return reart_base_backward_launch(&a, nullptr, nullptr, &workspace, workspace_bytes, 1, (hipStream_t)stream);
 }
 
 // --------------------------------------------------------------- hard-label rigid apply

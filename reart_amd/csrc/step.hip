@@ -539,22 +539,14 @@ __device__ __forceinline__ void chamfer_grad_body(const CGradArgs &a, const int 
     }
 }
 
-template <bool ONE>
-__global__ __launch_bounds__(CG_BS) void chamfer_grad_kernel(CGradArgs a) {
-    chamfer_grad_body<ONE>(a, blockIdx.x, blockIdx.y, gridDim.x);
+// the stand-alone consumers; BATCH: K instances in one launch, instance k on the grid's plane z = k
+template <bool ONE, bool BATCH>
+__global__ __launch_bounds__(CG_BS) void chamfer_grad_kernel(Batched<CGradArgs> ab) {
+    chamfer_grad_body<ONE>(ab.a[BATCH ? blockIdx.z : 0], blockIdx.x, blockIdx.y, gridDim.x);
 }
-template <bool ONE>
-__global__ __launch_bounds__(FLOW_BS) void flow_blend_kernel(FlowArgs a) {
-    flow_blend_body<ONE, FLOW_BS>(a, blockIdx.x, blockIdx.y, gridDim.x);
-}
-// the same consumers for K instances in one launch (reart_relax_step_batch): instance k on the grid's plane z = k
-template <bool ONE>
-__global__ __launch_bounds__(CG_BS) void chamfer_grad_batch_kernel(Batched<CGradArgs> ab) {
-    chamfer_grad_body<ONE>(ab.a[blockIdx.z], blockIdx.x, blockIdx.y, gridDim.x);
-}
-template <bool ONE>
-__global__ __launch_bounds__(FLOW_BS) void flow_blend_batch_kernel(Batched<FlowArgs> ab) {
-    flow_blend_body<ONE, FLOW_BS>(ab.a[blockIdx.z], blockIdx.x, blockIdx.y, gridDim.x);
+template <bool ONE, bool BATCH>
+__global__ __launch_bounds__(FLOW_BS) void flow_blend_kernel(Batched<FlowArgs> ab) {
+    flow_blend_body<ONE, FLOW_BS>(ab.a[BATCH ? blockIdx.z : 0], blockIdx.x, blockIdx.y, gridDim.x);
 }
 // Both consumers of the searches in ONE launch (same reason as knn_pruned_pair_kernel): workgroups
 // [0, nflow) blend the flow of (frame pair, 1024 points), the rest reduce the Chamfer gradient.
@@ -715,27 +707,42 @@ __device__ __forceinline__ void assign_grad_body(const AssignArgs &a, int bx, in
         a.loss_part[(size_t)b * gx + bx] = t * (double)a.lambda;
     }
 }
-__global__ __launch_bounds__(CG_BS) void assign_grad_kernel(AssignArgs a) { assign_grad_body(a, blockIdx.x, blockIdx.y, gridDim.x); }
-__global__ __launch_bounds__(CG_BS) void assign_grad_batch_kernel(Batched<AssignArgs> ab) {
-    assign_grad_body(ab.a[blockIdx.z], blockIdx.x, blockIdx.y, gridDim.x);
+template <bool BATCH>
+__global__ __launch_bounds__(CG_BS) void assign_grad_kernel(Batched<AssignArgs> ab) {
+    assign_grad_body(ab.a[BATCH ? blockIdx.z : 0], blockIdx.x, blockIdx.y, gridDim.x);
 }
 
 // ------------------------------------------------------------------------------ the step
 #define MARK(k) do { if (ev) (void)hipEventRecord(ev[k], st); } while (0)
 
-// the four launches of the default iteration (box-pruned search, Chamfer + flow) as argument blocks: what
-// reart_relax_step_batch collects from every instance before it launches each kernel once for all of them
+// Which launches an iteration consists of and their grids.  All int and without padding: instances can share their
+// launches (reart_relax_step_batch) when this member is equal byte for byte.
+struct StepGeom {
+    int pruned, grid;            // searches: box-pruned and warm-started (prune.hip) | brute-force slices, with `grid` the exact
+                                 // grids where the targets do not move
+    int flow;                    // flow loss on
+    int merged;                  // pruned, Chamfer + flow: ONE search launch, ONE consumer launch (post_kernel)
+    int has_search;              // pruned: there is a search launch (none for the assignment loss without flow) ...
+    int static_order;            // ... in its cloud-resident form, whose items keep their launch order
+    int has_fl, has_aa, has_cg;  // stand-alone consumers: flow blend, assignment loss, Chamfer gradient
+    int fl_one, cg_one;          // at most four partial lists per query for that consumer (its ONE instantiation)
+    int fgx, fgy, ncg, post_blocks, N, B;
+};
+// One instance's iteration as data: the argument block of every launch and the geometry of the launches.  step_describe
+// fills it, step_launch launches it -- for one instance, or for K of equal geometry at once.
 struct StepLaunch {
-    BaseFwdArgs fa; SearchArgs sa; PostArgs pa; int post_blocks;
-    BaseBwdArgs ba; FinalizeAdam ad; StepBook bk; void *ws_bwd; size_t bwd_bytes;
-    // the unmerged iterations (Chamfer only; assignment loss [+ flow]): separate consumers after the search
-    int merged, has_search, has_fl, has_aa, has_cg, fgx, fgy, ncg, nB;
+    StepGeom g;
+    BaseFwdArgs fa; SearchArgs sa; KnnArgs ka, k3; GridQueryArgs gq3, gq1; PostArgs pa;
     FlowArgs fl; AssignArgs aa; CGradArgs cg;
+    BaseBwdArgs ba; FinalizeAdam ad; StepBook bk; void *ws_bwd; size_t bwd_bytes;
+    int auto_s1, auto_s3;                      // no explicit tune_slices / tune_slices_flow: the launch picks by K
+    void *aux_stream, *ev_fork, *ev_join;      // brute-force / grid variants: the flow branch beside the Chamfer search
 };
 
-static int relax_step_impl(const reart_relax_config *cfg, const reart_relax_buffers *bufs,
-                           void *workspace, size_t workspace_bytes, void *stream, hipEvent_t *ev,
-                           bool forward_only = false, StepLaunch *collect = nullptr) {
+// Every argument check and every argument block of an iteration.  A function of its arguments only: no launch, no
+// event, no call of the runtime (so the refusals are testable without a device).
+static int step_describe(const reart_relax_config *cfg, const reart_relax_buffers *bufs, void *workspace, size_t workspace_bytes,
+                         bool forward_only, StepLaunch *out) {
     StepPlan p;
     if (!cfg || !bufs) return REART_ERR_INVALID_ARG;
     int rc = step_plan(cfg, &p);
@@ -745,13 +752,16 @@ static int relax_step_impl(const reart_relax_config *cfg, const reart_relax_buff
         !bufs->pc_trans || !bufs->iter || !bufs->tau)
         return REART_ERR_INVALID_ARG;
     const reart_relax_config &c = *cfg;
+    StepLaunch &L = *out;
+    L = StepLaunch{};
+    StepGeom &g = L.g;
     char *ws = (char *)workspace;
-    hipStream_t st = (hipStream_t)stream;
     const int N = c.N, B = c.B, P = c.P, H = c.H;
     float *G = (float *)(ws + p.o_G);
+    g.N = N; g.B = B; g.pruned = p.pruned; g.grid = c.use_grid ? 1 : 0; g.flow = c.use_flow ? 1 : 0;
 
-    // 1. forward: seg head + Gumbel-softmax + 6D + rigid apply (networks/model.py:39-70)
-    BaseFwdArgs fa = {};
+    // forward: seg head + Gumbel-softmax + 6D + rigid apply (networks/model.py:39-70)
+    BaseFwdArgs &fa = L.fa;
     fa.cano = bufs->cano; fa.W1 = bufs->W1; fa.b1 = bufs->b1; fa.W2 = bufs->W2; fa.p6d = bufs->p6d;
     fa.pt = bufs->pt; fa.gumbel = bufs->gumbel; fa.tau_ptr = bufs->tau; fa.iter_ptr = bufs->iter;
     fa.seed = c.seed; fa.tau = 1.0f; fa.N = N; fa.P = P; fa.B = B; fa.H = H; fa.Npad = p.Npad;
@@ -761,20 +771,13 @@ static int relax_step_impl(const reart_relax_config *cfg, const reart_relax_buff
     fa.rt_table = (float *)(ws + p.o_rt);
     fa.boxes = c.use_boxes ? (float *)(ws + p.o_boxX) : nullptr;
     fa.pts = c.tune_fwd_pts;
-    MARK(0);
-    if (collect) collect->fa = fa;
-    else {
-        rc = reart_base_forward_ex(fa, st);
-        if (rc != REART_OK) return rc;
-    }
-    MARK(1);
     if (forward_only) return REART_OK;
     if (c.use_assign && !bufs->assign_map) return REART_ERR_INVALID_ARG;
 
     const int nqg = reart_div_up(N, NN_BS);
     const int *qmap = (const int *)(ws + p.o_qmap);
     // job descriptions: K = 1 x -> y (0), y -> x (1); K = 3 flow
-    KnnArgs ka = {};
+    KnnArgs &ka = L.ka, &k3 = L.k3;
     ka.N = B; ka.S = p.S1; ka.K = 1; ka.euclidean = 0;
     for (int j = 0; j < 2; ++j) {
         KnnJob &kj = ka.job[j];
@@ -789,7 +792,6 @@ static int relax_step_impl(const reart_relax_config *cfg, const reart_relax_buff
         kj.cost = p.pruned ? (unsigned int *)(ws + p.o_cost) + (size_t)j * B * nqg : nullptr;
     }
     ka.items0 = B * nqg * p.S1; ka.items = 2 * ka.items0;
-    KnnArgs k3 = {};
     if (c.use_flow) {
         k3.N = B; k3.S = p.S3; k3.K = 3; k3.euclidean = 0;
         KnnJob &kj = k3.job[0];
@@ -804,31 +806,16 @@ static int relax_step_impl(const reart_relax_config *cfg, const reart_relax_buff
         k3.job[1] = kj;
         k3.items0 = B * nqg * p.S3; k3.items = k3.items0;
     }
-    // consumers' argument blocks
-    int S3 = p.S3, S0 = p.S1, nfp = 0;
-    FlowArgs fl = {};
     const bool chamfer = !c.use_assign;
     // merged: Chamfer + flow on the pruned path -- ONE search launch, ONE consumer launch
     const bool merged = p.pruned && c.use_flow && chamfer;
-    if (collect && !p.pruned) return REART_ERR_UNSUPPORTED;         // the brute-force / grid variants launch as they go
-    if (collect) {
-        collect->merged = merged ? 1 : 0; collect->has_search = collect->has_fl = collect->has_aa = collect->has_cg = 0;
-        collect->nB = B;
-    }
-    // Brute-force / grid variants keep their separate launches; with an auxiliary stream from the caller their
-    // flow branch runs beside the Chamfer search (fork / join).  The timed variant is always serial.
-    const bool forked = !p.pruned && !ev && bufs->aux_stream && bufs->ev_fork && bufs->ev_join && c.use_flow;
-    hipStream_t fst = forked ? (hipStream_t)bufs->aux_stream : st;
-    if (forked) {
-        if (hipEventRecord((hipEvent_t)bufs->ev_fork, st) != hipSuccess) return REART_ERR_LAUNCH;
-        if (hipStreamWaitEvent(fst, (hipEvent_t)bufs->ev_fork, 0) != hipSuccess) return REART_ERR_LAUNCH;
-    }
+    g.merged = merged ? 1 : 0;
+    L.aux_stream = bufs->aux_stream; L.ev_fork = bufs->ev_fork; L.ev_join = bufs->ev_join;
 
-    // 2. the searches
-    int search_wgs = 0;
-    bool search_static_order = false;
+    // the searches
+    int search_wgs = 0, S3 = p.S3, S0 = p.S1;
     if (p.pruned) {
-        SearchArgs sa = {};
+        SearchArgs &sa = L.sa;
         sa.G = B * nqg; sa.S1 = p.W1; sa.S3 = p.W3; sa.sparse = p.sparse; sa.share = c.tune_share < 0 ? 0 : (c.tune_share == 1 ? 1 : 2); sa.interleave = c.tune_xcd > 0 ? 0 : 1;
         sa.cloud_resident = c.tune_cloud > 0 ? 1 : 0; sa.cloud_slices = c.tune_cloud > 0 ? c.tune_cloud : 0;
         if (chamfer) { sa.k1[0] = ka.job[0]; sa.k1[1] = ka.job[1]; sa.n1 = 2; }
@@ -836,36 +823,39 @@ static int relax_step_impl(const reart_relax_config *cfg, const reart_relax_buff
         if (c.profile && merged) {
             sa.prof = (unsigned long long *)(ws + p.o_prof); sa.prof_pairs = (unsigned int *)(ws + p.o_prof_pairs);
         }
+        L.auto_s1 = c.tune_slices == 0; L.auto_s3 = c.tune_slices_flow == 0;
         if (sa.n1 + sa.n3 > 0) {
             search_wgs = reart_search_workgroups(sa);
-            search_static_order = search_wgs != reart_search_grid(sa.n1, sa.n3, sa.G);   // cloud-resident form: fixed order
-            if (collect) {
-                if (search_static_order) return REART_ERR_UNSUPPORTED;
-                collect->sa = sa; collect->has_search = 1;
-            } else {
-                rc = reart_search_launch(sa, st);
-                if (rc != REART_OK) return rc;
-            }
+            g.static_order = search_wgs != reart_search_grid(sa.n1, sa.n3, sa.G);   // cloud-resident form: fixed order
+            g.has_search = 1;
         }
-    } else {
+    } else if (c.use_grid) {
         if (c.use_flow) {
-            if (c.use_grid) {
-                GridBuildArgs gr = {};
-                reart_grid_layout(ws + p.o_gridR, B, p.gstrideR, &gr);
-                GridQueryArgs gq = {};
-                gq.q = bufs->pc_trans; gq.q_alt = bufs->cano; gq.qmap = qmap; gq.nq = N; gq.E = B; gq.stride = p.gstrideR;
-                gq.gx = gr.gx; gq.gy = gr.gy; gq.gz = gr.gz; gq.gorig = gr.gorig; gq.cell_start = gr.cell_start;
-                gq.meta = gr.meta; gq.od = (float *)(ws + p.o_pd3); gq.oi = (int *)(ws + p.o_pi3);
-                rc = reart_grid_query_launch(gq, 3, fst);
-                S3 = 1;
-            } else {
-                rc = reart_knn_launch_slices(k3, 3, fst);
-            }
-            if (rc != REART_OK) return rc;
+            GridBuildArgs gr = {};
+            reart_grid_layout(ws + p.o_gridR, B, p.gstrideR, &gr);
+            GridQueryArgs &gq = L.gq3;
+            gq.q = bufs->pc_trans; gq.q_alt = bufs->cano; gq.qmap = qmap; gq.nq = N; gq.E = B; gq.stride = p.gstrideR;
+            gq.gx = gr.gx; gq.gy = gr.gy; gq.gz = gr.gz; gq.gorig = gr.gorig; gq.cell_start = gr.cell_start;
+            gq.meta = gr.meta; gq.od = (float *)(ws + p.o_pd3); gq.oi = (int *)(ws + p.o_pi3);
+            S3 = 1;
+        }
+        if (chamfer) {
+            // pc_list never changes: pc_trans -> pc_list goes through its pre-built exact grid, and only pc_list -> pc_trans
+            // (moving targets) is searched by brute force
+            GridBuildArgs gy = {};
+            reart_grid_layout(ws + p.o_gridY, B, p.gstrideY, &gy);
+            GridQueryArgs &gq = L.gq1;
+            gq.q = bufs->pc_trans; gq.nq = N; gq.E = B; gq.stride = p.gstrideY; gq.gx = gy.gx; gq.gy = gy.gy; gq.gz = gy.gz;
+            gq.gorig = gy.gorig; gq.cell_start = gy.cell_start; gq.meta = gy.meta;
+            gq.od = (float *)(ws + p.o_pd0); gq.oi = (int *)(ws + p.o_pi0);
+            S0 = 1;
+            ka.job[0] = ka.job[1];
+            ka.items = ka.items0;
         }
     }
-    MARK(2);
-    // 3. flow consumer (separate launch unless merged): top-3 merge / rescan, blend, flow-loss term + gradient
+    // flow consumer: top-3 merge / rescan, blend, flow-loss term + gradient
+    int nfp = 0;
+    FlowArgs &fl = L.fl;
     if (c.use_flow) {
         fl.pd = (const float *)(ws + p.o_pd3); fl.pi = (const int *)(ws + p.o_pi3); fl.ref_flow = bufs->ref_flow;
         fl.ref_off = bufs->ref_off; fl.qmap = qmap; fl.X = bufs->pc_trans; fl.cano = bufs->cano; fl.N = N; fl.B = B;
@@ -878,67 +868,32 @@ static int relax_step_impl(const reart_relax_config *cfg, const reart_relax_buff
         // POST_FBS threads (the other waves leave at once: the hardware barrier counts live waves only) -- the blend is a chain
         // of gathers, 16 waves of them on ONE compute unit queue up behind its one address unit; four times the workgroups of
         // four waves spread them over four times the compute units
-        const dim3 fg(reart_div_up(N, merged ? POST_FBS : FLOW_BS), B);
-        nfp = fg.x * fg.y;
-        if (!merged && collect) {
-            if (fl.S > 4) return REART_ERR_UNSUPPORTED;
-            collect->fl = fl; collect->fgx = fg.x; collect->fgy = fg.y; collect->has_fl = 1;
-        } else if (!merged) {
-            if (fl.S <= 4) hipLaunchKernelGGL(flow_blend_kernel<true>, fg, dim3(FLOW_BS), 0, fst, fl);
-            else hipLaunchKernelGGL(flow_blend_kernel<false>, fg, dim3(FLOW_BS), 0, fst, fl);
-            REART_CHECK_LAUNCH();
-        }
+        g.fgx = reart_div_up(N, merged ? POST_FBS : FLOW_BS); g.fgy = B;
+        nfp = g.fgx * g.fgy;
+        g.has_fl = merged ? 0 : 1; g.fl_one = fl.S <= 4;
     }
-    if (forked && hipEventRecord((hipEvent_t)bufs->ev_join, fst) != hipSuccess) return REART_ERR_LAUNCH;
-    MARK(3);
-
+    g.ncg = reart_div_up(N, CG_RANGE);
     if (c.use_assign) {
         // assignment loss instead of the Chamfer loss: no search, the pairs come from the caller's assign_map
-        MARK(4);
-        AssignArgs aa = {};
+        AssignArgs &aa = L.aa;
         aa.X = bufs->pc_trans; aa.Y = bufs->pc_list; aa.map = bufs->assign_map; aa.N = N; aa.B = B;
         aa.lambda = c.lambda_assign; aa.G = G; aa.loss_part = (double *)(ws + p.o_floss);
-        if (collect) { collect->aa = aa; collect->has_aa = 1; }
-        else {
-            hipLaunchKernelGGL(assign_grad_kernel, dim3(reart_div_up(N, CG_BS), B), dim3(CG_BS), 0, st, aa);
-            REART_CHECK_LAUNCH();
-        }
+        g.has_aa = 1;
     } else {
-        // Chamfer (utils/chamfer.py:78-94) on the brute-force paths.  pc_list never changes: with use_grid the
-        // direction pc_trans -> pc_list goes through its pre-built exact grid, and only pc_list -> pc_trans (moving
-        // targets) is searched by brute force; without it both directions share one brute-force launch.
-        if (!p.pruned) {
-            if (c.use_grid) {
-                GridBuildArgs gy = {};
-                reart_grid_layout(ws + p.o_gridY, B, p.gstrideY, &gy);
-                GridQueryArgs gq = {};
-                gq.q = bufs->pc_trans; gq.nq = N; gq.E = B; gq.stride = p.gstrideY; gq.gx = gy.gx; gq.gy = gy.gy; gq.gz = gy.gz;
-                gq.gorig = gy.gorig; gq.cell_start = gy.cell_start; gq.meta = gy.meta;
-                gq.od = (float *)(ws + p.o_pd0); gq.oi = (int *)(ws + p.o_pi0);
-                rc = reart_grid_query_launch(gq, 1, st);
-                if (rc != REART_OK) return rc;
-                S0 = 1;
-                ka.job[0] = ka.job[1];
-                ka.items = ka.items0;
-            }
-            rc = reart_knn_launch_slices(ka, 1, st);
-            if (rc != REART_OK) return rc;
-        }
-        MARK(4);
         // merge + recon loss + direct gradient term + fixed-point scatter (fully parallel)
-        CGradArgs cg = {};
+        CGradArgs &cg = L.cg;
         cg.X = bufs->pc_trans; cg.Y = bufs->pc_list;
         cg.pd0 = (const float *)(ws + p.o_pd0); cg.pi0 = (const int *)(ws + p.o_pi0);
         cg.pd1 = (const float *)(ws + p.o_pd1); cg.pi1 = (const int *)(ws + p.o_pi1);
         cg.fx_bits = (const int *)(ws + p.o_fx);
         cg.N = N; cg.B = B; cg.S0 = S0; cg.S1 = p.S1; cg.G = G;
         cg.loss_part = (double *)(ws + p.o_floss);
-        const int ncg = reart_div_up(N, CG_RANGE);
+        g.has_cg = merged ? 0 : 1; g.cg_one = cg.S0 <= 4 && cg.S1 <= 4;
         if (merged) {
-            PostArgs pa = {};
-            pa.fl = fl; pa.cg = cg; pa.nfx = reart_div_up(N, POST_FBS); pa.nflow = pa.nfx * B; pa.ncx = ncg;
-            pa.nwork = pa.nflow + ncg * B;
-            const bool reorder = c.tune_reorder >= 0 && !search_static_order;
+            PostArgs &pa = L.pa;
+            pa.fl = fl; pa.cg = cg; pa.nfx = g.fgx; pa.nflow = pa.nfx * B; pa.ncx = g.ncg;
+            pa.nwork = pa.nflow + g.ncg * B;
+            const bool reorder = c.tune_reorder >= 0 && !g.static_order;
             for (int j = 0; j < 3; ++j) {
                 const KnnJob &kj = j < 2 ? ka.job[j] : k3.job[0];
                 pa.od.cost[j] = reorder ? kj.cost : nullptr;
@@ -946,57 +901,150 @@ static int relax_step_impl(const reart_relax_config *cfg, const reart_relax_buff
             }
             pa.od.groups = B * nqg; pa.od.per = c.tune_xcd > 0 ? reart_div_up(B * nqg, 8) : B * nqg;
             pa.norder = reorder ? 3 : 0;
-            int nblk = pa.nwork + pa.norder;
+            g.post_blocks = pa.nwork + pa.norder;
             if (c.profile) {
                 pa.od.prof = (const unsigned long long *)(ws + p.o_prof);
                 pa.od.prof_pairs = (const unsigned int *)(ws + p.o_prof_pairs);
                 pa.od.prof_acc = (unsigned long long *)(ws + p.o_prof_acc);
                 pa.od.nprof = search_wgs;
-                nblk += 1;
+                g.post_blocks += 1;
             }
-            if (collect) { collect->pa = pa; collect->post_blocks = nblk; }
-            else hipLaunchKernelGGL((post_kernel<true, false>), dim3(nblk), dim3(CG_BS), 0, st, reart_batched(&pa, 1));
-        } else if (collect) {
-            if (cg.S0 > 4 || cg.S1 > 4) return REART_ERR_UNSUPPORTED;
-            collect->cg = cg; collect->ncg = ncg; collect->has_cg = 1;
-        } else if (cg.S0 <= 4 && cg.S1 <= 4) hipLaunchKernelGGL(chamfer_grad_kernel<true>, dim3(ncg, B), dim3(CG_BS), 0, st, cg);
-        else hipLaunchKernelGGL(chamfer_grad_kernel<false>, dim3(ncg, B), dim3(CG_BS), 0, st, cg);
-        REART_CHECK_LAUNCH();
+        }
     }
-    MARK(5);
-
-    if (forked && hipStreamWaitEvent(st, (hipEvent_t)bufs->ev_join, 0) != hipSuccess) return REART_ERR_LAUNCH;
-    // 6-7. model backward; the finalize kernel also applies Adam with the reference's two
+    // model backward; the finalize kernel also applies Adam with the reference's two
     // parameter groups (run_robot.py:146-148) to the parameter each thread just reduced
     float *grads = (float *)(ws + p.o_grads);
     float *gW1 = grads, *gb1 = gW1 + 3 * H, *gW2 = gb1 + H, *g6d = gW2 + P * H, *gt = g6d + 6 * B * P;
-    BaseBwdArgs ba = {};
+    BaseBwdArgs &ba = L.ba;
     ba.cano = bufs->cano; ba.W2 = bufs->W2; ba.p6d = bufs->p6d; ba.pt = bufs->pt; ba.yT = fa.yT; ba.hT = fa.hT;
     ba.hard_idx = fa.hard_idx; ba.tau_ptr = bufs->tau; ba.tau = 1.0f; ba.G = G; ba.rt_table = fa.rt_table;
     ba.cano_idx = c.cano_idx;
     ba.gpf = c.use_flow ? (const float *)(ws + p.o_gpf) : nullptr;
     ba.cpts = c.tune_bwd_pts;
     ba.N = N; ba.P = P; ba.B = B; ba.H = H; ba.gW1 = gW1; ba.gb1 = gb1; ba.gW2 = gW2; ba.g6d = g6d; ba.gt = gt;
-    FinalizeAdam ad = {};
+    FinalizeAdam &ad = L.ad;
     ad.enabled = 1; ad.W1 = bufs->W1; ad.b1 = bufs->b1; ad.W2 = bufs->W2; ad.p6d = bufs->p6d; ad.pt = bufs->pt;
     ad.m = bufs->adam_m; ad.v = bufs->adam_v; ad.seg_lr = c.seg_lr; ad.trans_lr = c.trans_lr;
     ad.beta1 = c.beta1; ad.beta2 = c.beta2; ad.eps = c.eps; ad.step_ptr = bufs->iter;
     ad.weight_decay = c.weight_decay;
     ad.bias_corr = (const double *)(ws + p.o_bc);
     // loss log, iter++, next tau and bias corrections: last workgroup of the finalize kernel
-    const int ncgp = reart_div_up(N, CG_RANGE);
-    StepBook bk = {};
-    bk.enabled = 1; bk.frame_loss = (const double *)(ws + p.o_floss); bk.n_frame_part = B * ncgp;
+    StepBook &bk = L.bk;
+    bk.enabled = 1; bk.frame_loss = (const double *)(ws + p.o_floss); bk.n_frame_part = B * g.ncg;
     bk.flow_part = (const double *)(ws + p.o_fpart); bk.n_flow_part = nfp;
     bk.iter = bufs->iter; bk.tau = bufs->tau; bk.losses = bufs->losses; bk.bias_corr = (double *)(ws + p.o_bc);
     bk.ticket = (unsigned int *)(ws + p.o_ticket);
     bk.ring = c.ring; bk.n_iter = c.n_iter; bk.lambda_flow = c.lambda_flow; bk.fixed_tau = c.fixed_tau;
     bk.end_tau = c.end_tau; bk.start_tau = c.start_tau; bk.beta1 = c.beta1; bk.beta2 = c.beta2;
-    if (collect) {
-        collect->ba = ba; collect->ad = ad; collect->bk = bk; collect->ws_bwd = ws + p.o_bwd; collect->bwd_bytes = p.bwd_bytes;
-        return REART_OK;
+    L.ws_bwd = ws + p.o_bwd; L.bwd_bytes = p.bwd_bytes;
+    return REART_OK;
+}
+
+// What reart_relax_step_batch takes (for any K) and what step_launch takes for K > 1: the box-pruned paths with the search
+// in its group form, and consumers that merge at most four partial lists per query
+static bool step_batchable(const StepGeom &g) {
+    return g.pruned && !g.static_order && (!g.has_fl || g.fl_one) && (!g.has_cg || g.cg_one);
+}
+
+// member m of L[0..K): the argument of a batched kernel or launcher
+template <class A>
+static Batched<A> gather(const StepLaunch *L, int K, A StepLaunch::*m) {
+    Batched<A> b = {};
+    for (int k = 0; k < K; ++k) b.a[k] = L[k].*m;
+    return b;
+}
+
+// The launch sequence of one iteration for K instances of one geometry (L[0].g; the caller has compared them): every kernel
+// runs once, instance k on plane k of its grid.  K = 1 is the single step.  ev: the events of the timed entry.
+static int step_launch(const StepLaunch *L, int K, hipStream_t st, hipEvent_t *ev, bool forward_only) {
+    const StepGeom &g = L[0].g;
+    if (K > 1 && !step_batchable(g)) return REART_ERR_UNSUPPORTED;
+    // 1. forward: seg head + Gumbel-softmax + 6D + rigid apply (networks/model.py:39-70)
+    MARK(0);
+    int rc = reart_base_forward_launch(gather(L, K, &StepLaunch::fa).a, K, st);
+    if (rc != REART_OK) return rc;
+    MARK(1);
+    if (forward_only) return REART_OK;
+    // Brute-force / grid variants keep their separate launches; with an auxiliary stream from the caller their
+    // flow branch runs beside the Chamfer search (fork / join).  The timed variant is always serial.
+    const bool forked = !g.pruned && !ev && L[0].aux_stream && L[0].ev_fork && L[0].ev_join && g.flow;
+    hipStream_t fst = forked ? (hipStream_t)L[0].aux_stream : st;
+    if (forked) {
+        if (hipEventRecord((hipEvent_t)L[0].ev_fork, st) != hipSuccess) return REART_ERR_LAUNCH;
+        if (hipStreamWaitEvent(fst, (hipEvent_t)L[0].ev_fork, 0) != hipSuccess) return REART_ERR_LAUNCH;
     }
-    rc = reart_base_backward_ex(ba, &ad, &bk, ws + p.o_bwd, p.bwd_bytes, st);
+    // 2. the searches: pruned, ONE launch for all of them; otherwise the flow search here and the Chamfer search below
+    if (g.has_search) {
+        Batched<SearchArgs> sa = gather(L, K, &StepLaunch::sa);
+        // Box slices per search workgroup: ONE instance wants three waves per workgroup (its launch is only a few wave
+        // lifetimes long: shorter waves, more of them in flight); with K instances in the launch the chip is full anyway and
+        // the launch is bound by the instructions it issues, of which every extra wave of a workgroup repeats the prologue and
+        // the coarse rounds: measured for K = 6, aggregate it/s: 3 slices 22.7 k, 2 slices 23.8 k, 1 slice 24.5 k (K = 2: best with 2).  Same
+        // results whatever the count; an explicit tune_slices is kept.
+        const int auto_s = K >= 3 ? 1 : (K == 2 ? 2 : 3);      // measured grid (K x slices): profiles/r03_search_ab_runs.txt
+        for (int k = 0; k < K; ++k) {
+            if (L[k].auto_s1) sa.a[k].S1 = auto_s;
+            if (L[k].auto_s3) sa.a[k].S3 = L[k].auto_s1 ? auto_s : sa.a[k].S1;
+        }
+        rc = K == 1 ? reart_search_launch(sa.a[0], st) : reart_search_launch_batch(sa.a, K, st);
+        if (rc != REART_OK) return rc;
+    } else if (!g.pruned && g.flow) {
+        rc = g.grid ? reart_grid_query_launch(L[0].gq3, 3, fst) : reart_knn_launch_slices(L[0].k3, 3, fst);
+        if (rc != REART_OK) return rc;
+    }
+    MARK(2);
+    // 3. flow consumer (separate launch unless merged): top-3 merge / rescan, blend, flow-loss term + gradient
+    if (g.has_fl) {
+        const dim3 fg(g.fgx, g.fgy, K);
+        const Batched<FlowArgs> fb = gather(L, K, &StepLaunch::fl);
+        if (K > 1) hipLaunchKernelGGL((flow_blend_kernel<true, true>), fg, dim3(FLOW_BS), 0, fst, fb);
+        else if (g.fl_one) hipLaunchKernelGGL((flow_blend_kernel<true, false>), fg, dim3(FLOW_BS), 0, fst, fb);
+        else hipLaunchKernelGGL((flow_blend_kernel<false, false>), fg, dim3(FLOW_BS), 0, fst, fb);
+        REART_CHECK_LAUNCH();
+    }
+    if (forked && hipEventRecord((hipEvent_t)L[0].ev_join, fst) != hipSuccess) return REART_ERR_LAUNCH;
+    MARK(3);
+    if (g.has_aa) {
+        // 4. assignment loss instead of the Chamfer loss: no search, the pairs come from the caller's assign_map
+        MARK(4);
+        const dim3 ag(reart_div_up(g.N, CG_BS), g.B, K);
+        const Batched<AssignArgs> ab = gather(L, K, &StepLaunch::aa);
+        if (K > 1) hipLaunchKernelGGL(assign_grad_kernel<true>, ag, dim3(CG_BS), 0, st, ab);
+        else hipLaunchKernelGGL(assign_grad_kernel<false>, ag, dim3(CG_BS), 0, st, ab);
+    } else {
+        // 4. Chamfer (utils/chamfer.py:78-94).  Brute-force paths: its search first -- with use_grid one direction goes
+        // through the grid, without it both directions share one brute-force launch
+        if (!g.pruned) {
+            if (g.grid) {
+                rc = reart_grid_query_launch(L[0].gq1, 1, st);
+                if (rc != REART_OK) return rc;
+            }
+            rc = reart_knn_launch_slices(L[0].ka, 1, st);
+            if (rc != REART_OK) return rc;
+        }
+        MARK(4);
+        // merge + recon loss + direct gradient term + fixed-point scatter; merged: with the flow consumer in one launch
+        if (g.merged) {
+            const Batched<PostArgs> pb = gather(L, K, &StepLaunch::pa);
+            if (K > 1) hipLaunchKernelGGL((post_kernel<true, true>), dim3(g.post_blocks, K), dim3(CG_BS), 0, st, pb);
+            else hipLaunchKernelGGL((post_kernel<true, false>), dim3(g.post_blocks), dim3(CG_BS), 0, st, pb);
+        } else {
+            const dim3 cgd(g.ncg, g.B, K);
+            const Batched<CGradArgs> cb = gather(L, K, &StepLaunch::cg);
+            if (K > 1) hipLaunchKernelGGL((chamfer_grad_kernel<true, true>), cgd, dim3(CG_BS), 0, st, cb);
+            else if (g.cg_one) hipLaunchKernelGGL((chamfer_grad_kernel<true, false>), cgd, dim3(CG_BS), 0, st, cb);
+            else hipLaunchKernelGGL((chamfer_grad_kernel<false, false>), cgd, dim3(CG_BS), 0, st, cb);
+        }
+    }
+    REART_CHECK_LAUNCH();
+    MARK(5);
+    if (forked && hipStreamWaitEvent(st, (hipEvent_t)L[0].ev_join, 0) != hipSuccess) return REART_ERR_LAUNCH;
+    // 5. model backward; its finalize kernel also applies Adam and does the iteration's bookkeeping
+    const Batched<BaseBwdArgs> ba = gather(L, K, &StepLaunch::ba);
+    const Batched<FinalizeAdam> ad = gather(L, K, &StepLaunch::ad);
+    const Batched<StepBook> bk = gather(L, K, &StepLaunch::bk);
+    const Batched<void *> wb = gather(L, K, &StepLaunch::ws_bwd);
+    rc = reart_base_backward_launch(ba.a, ad.a, bk.a, wb.a, L[0].bwd_bytes, K, st);
     if (rc != REART_OK) return rc;
     MARK(6);
     MARK(7);
@@ -1004,94 +1052,47 @@ static int relax_step_impl(const reart_relax_config *cfg, const reart_relax_buff
     return REART_OK;
 }
 
+static int relax_step_one(const reart_relax_config *cfg, const reart_relax_buffers *bufs, void *workspace, size_t workspace_bytes,
+                          void *stream, hipEvent_t *ev, bool forward_only) {
+    StepLaunch L;
+    const int rc = step_describe(cfg, bufs, workspace, workspace_bytes, forward_only, &L);
+    return rc != REART_OK ? rc : step_launch(&L, 1, (hipStream_t)stream, ev, forward_only);
+}
+
 extern "C" int reart_relax_step(const reart_relax_config *cfg, const reart_relax_buffers *bufs,
                                 void *workspace, size_t workspace_bytes, void *stream) {
-    return relax_step_impl(cfg, bufs, workspace, workspace_bytes, stream, nullptr);
+    return relax_step_one(cfg, bufs, workspace, workspace_bytes, stream, nullptr, false);
 }
 
 // K independent instances of ONE shape (same N, B, P, H, M_max and switches; poses, clouds, canonical index, seeds and
 // learning rates are each instance's own) advance one iteration in the launches of a single instance: every kernel of the
-// iteration runs once with K argument blocks, instance k on the grid's row k.  One instance leaves most of the chip idle
+// iteration runs once with K argument blocks, instance k on plane k of its grid.  One instance leaves most of the chip idle
 // (64-608 workgroups per launch on 256 compute units, and the iteration is a chain of five dependent launches): a sweep
 // over canonical frames (README.md:60) fills it this way instead of with K streams that the hardware queues interleave
 // as they please.  Each instance computes exactly what reart_relax_step computes for it.  Box-pruned search paths: the
 // merged Chamfer + flow iteration, Chamfer only, and the assignment loss with or without flow (the second phase of the
-// README recipe, run_robot.py:164-192); K <= 6.
+// README recipe, run_robot.py:164-192); K <= 6.  What K instances cannot share is refused for K = 1 as well.
 extern "C" int reart_relax_step_batch(const reart_relax_config *cfgs, const reart_relax_buffers *bufs, void *const *workspaces,
                                       size_t workspace_bytes, int K, void *stream) {
     if (!cfgs || !bufs || !workspaces || K < 1 || K > REART_BATCH_MAX) return REART_ERR_INVALID_ARG;
     static_assert(sizeof(Batched<SearchArgs>) <= 3584, "kernel-argument segment");
-    StepLaunch L[REART_BATCH_MAX] = {};
+    StepLaunch L[REART_BATCH_MAX];
     for (int k = 0; k < K; ++k) {
-        const int rc = relax_step_impl(&cfgs[k], &bufs[k], workspaces[k], workspace_bytes, stream, nullptr, false, &L[k]);
+        const int rc = step_describe(&cfgs[k], &bufs[k], workspaces[k], workspace_bytes, false, &L[k]);
         if (rc != REART_OK) return rc;
-        if (L[k].bwd_bytes != L[0].bwd_bytes || L[k].merged != L[0].merged || L[k].has_search != L[0].has_search ||
-            L[k].has_fl != L[0].has_fl || L[k].has_aa != L[0].has_aa || L[k].has_cg != L[0].has_cg || L[k].nB != L[0].nB)
-            return REART_ERR_INVALID_ARG;
-        if (L[0].merged && L[k].post_blocks != L[0].post_blocks) return REART_ERR_INVALID_ARG;
-        if (L[0].has_fl && (L[k].fgx != L[0].fgx || L[k].fgy != L[0].fgy)) return REART_ERR_INVALID_ARG;
-        if (L[0].has_cg && L[k].ncg != L[0].ncg) return REART_ERR_INVALID_ARG;
-        if (L[0].has_aa && L[k].aa.N != L[0].aa.N) return REART_ERR_INVALID_ARG;
+        if (!step_batchable(L[k].g)) return REART_ERR_UNSUPPORTED;
+        if (memcmp(&L[k].g, &L[0].g, sizeof(StepGeom)) != 0 || L[k].bwd_bytes != L[0].bwd_bytes) return REART_ERR_INVALID_ARG;
     }
-    hipStream_t st = (hipStream_t)stream;
-    BaseFwdArgs fa[REART_BATCH_MAX];
-    SearchArgs sa[REART_BATCH_MAX];
-    Batched<PostArgs> pa = {};
-    BaseBwdArgs ba[REART_BATCH_MAX];
-    FinalizeAdam ad[REART_BATCH_MAX];
-    StepBook bk[REART_BATCH_MAX];
-    void *wb[REART_BATCH_MAX];
-    for (int k = 0; k < K; ++k) {
-        fa[k] = L[k].fa; sa[k] = L[k].sa; pa.a[k] = L[k].pa; ba[k] = L[k].ba; ad[k] = L[k].ad; bk[k] = L[k].bk; wb[k] = L[k].ws_bwd;
-        // Box slices per search workgroup: ONE instance wants three waves per workgroup (its launch is only a few wave
-        // lifetimes long: shorter waves, more of them in flight); with K instances in the launch the chip is full anyway and
-        // the launch is bound by the instructions it issues, of which every extra wave of a workgroup repeats the prologue and
-        // the coarse rounds: measured for K = 6, aggregate it/s: 3 slices 22.7 k, 2 slices 23.8 k, 1 slice 24.5 k (K = 2: best with 2).  Same
-        // results whatever the count; an explicit tune_slices is kept.
-        const int auto_s = K >= 3 ? 1 : (K == 2 ? 2 : 3);      // measured grid (K x slices): profiles/r03_search_ab_runs.txt
-        if (cfgs[k].tune_slices == 0) sa[k].S1 = auto_s;
-        if (cfgs[k].tune_slices_flow == 0) sa[k].S3 = cfgs[k].tune_slices == 0 ? auto_s : sa[k].S1;
-    }
-    int rc = reart_base_forward_batch(fa, K, st);
-    if (rc != REART_OK) return rc;
-    if (L[0].has_search) {
-        rc = reart_search_launch_batch(sa, K, st);
-        if (rc != REART_OK) return rc;
-    }
-    if (L[0].merged) {
-        if (K == 1) hipLaunchKernelGGL((post_kernel<true, false>), dim3(L[0].post_blocks), dim3(CG_BS), 0, st, pa);
-        else hipLaunchKernelGGL((post_kernel<true, true>), dim3(L[0].post_blocks, K), dim3(CG_BS), 0, st, pa);
-        REART_CHECK_LAUNCH();
-    } else {
-        // the unmerged iterations: Chamfer only (search + its consumer), assignment loss (the caller's pairs) [+ flow: its
-        // search + consumer] -- the same separate consumers reart_relax_step launches, once for all K instances
-        if (L[0].has_fl) {
-            Batched<FlowArgs> fb = {};
-            for (int k = 0; k < K; ++k) fb.a[k] = L[k].fl;
-            hipLaunchKernelGGL(flow_blend_batch_kernel<true>, dim3(L[0].fgx, L[0].fgy, K), dim3(FLOW_BS), 0, st, fb);
-            REART_CHECK_LAUNCH();
-        }
-        if (L[0].has_aa) {
-            Batched<AssignArgs> ab = {};
-            for (int k = 0; k < K; ++k) ab.a[k] = L[k].aa;
-            hipLaunchKernelGGL(assign_grad_batch_kernel, dim3(reart_div_up(L[0].aa.N, CG_BS), L[0].nB, K), dim3(CG_BS), 0, st, ab);
-            REART_CHECK_LAUNCH();
-        }
-        if (L[0].has_cg) {
-            Batched<CGradArgs> cb = {};
-            for (int k = 0; k < K; ++k) cb.a[k] = L[k].cg;
-            hipLaunchKernelGGL(chamfer_grad_batch_kernel<true>, dim3(L[0].ncg, L[0].nB, K), dim3(CG_BS), 0, st, cb);
-            REART_CHECK_LAUNCH();
-        }
-    }
-    return reart_base_backward_batch(ba, ad, bk, wb, L[0].bwd_bytes, K, st);
+    return step_launch(L, K, (hipStream_t)stream, nullptr, false);
 }
 
-// Same launch sequence with a hipEvent between phases, recorded on `stream`; synchronises the
+// The same launch sequence with a hipEvent between phases, recorded on `stream`; synchronises the
 // stream and ADDS the per-phase milliseconds to h_ms[REART_RELAX_PHASES] (host memory).
-// Phases: 0 forward, 1 flow K=3 search, 2 flow blend, 3 Chamfer K=1 search, 4 Chamfer merge +
-// gradient scatter, 5 model backward + Adam (2 launches), 6 unused, 7 bookkeeping (always serial).  Measurement aid for
-// bench.py / profiling -- not graph-capturable.
+// Phases: 0 forward; 1 the box-pruned search launch (every search of the iteration: Chamfer K=1 and flow K=3), or the
+// flow K=3 search of the brute-force / grid variants; 2 flow blend where it is a launch of its own; 3 Chamfer K=1 search of
+// the brute-force / grid variants (empty on the pruned path); 4 the consumer: Chamfer merge + gradient, with the flow blend
+// when merged, or the assignment loss; 5 model backward + Adam + bookkeeping (2 launches); 6-7 unused.  Always serial.
+// Measurement aid for bench.py / profiling -- not graph-capturable.
 extern "C" int reart_relax_step_timed(const reart_relax_config *cfg, const reart_relax_buffers *bufs,
                                       void *workspace, size_t workspace_bytes, void *stream,
                                       float *h_ms) {
@@ -1099,7 +1100,7 @@ extern "C" int reart_relax_step_timed(const reart_relax_config *cfg, const reart
     hipEvent_t ev[REART_RELAX_PHASES + 1];
     for (int k = 0; k <= REART_RELAX_PHASES; ++k)
         if (hipEventCreate(&ev[k]) != hipSuccess) return REART_ERR_LAUNCH;
-    int rc = relax_step_impl(cfg, bufs, workspace, workspace_bytes, stream, ev);
+    int rc = relax_step_one(cfg, bufs, workspace, workspace_bytes, stream, ev, false);
     if (rc == REART_OK) {
         if (hipEventSynchronize(ev[REART_RELAX_PHASES]) != hipSuccess) rc = REART_ERR_LAUNCH;
         for (int k = 0; k < REART_RELAX_PHASES && rc == REART_OK; ++k) {
@@ -1143,7 +1144,7 @@ extern "C" int reart_relax_profile(const reart_relax_config *cfg, void *workspac
 
 extern "C" int reart_relax_forward(const reart_relax_config *cfg, const reart_relax_buffers *bufs,
                                    void *workspace, size_t workspace_bytes, void *stream) {
-    return relax_step_impl(cfg, bufs, workspace, workspace_bytes, stream, nullptr, true);
+    return relax_step_one(cfg, bufs, workspace, workspace_bytes, stream, nullptr, true);
 }
 
 

@@ -103,6 +103,89 @@ def test_new_entry_points_reject_bad_arguments_without_a_gpu():
     assert L.reart_cdist(None, None, 0, 4, 4, None, None) == 0
 
 
+INVALID_ARG, UNSUPPORTED = -1, -2   # REART_ERR_INVALID_ARG, REART_ERR_UNSUPPORTED (include/reart_hip.h)
+
+
+def _relax_case(**over):
+    """(cfg, bufs, workspace bytes) of a small fused-step problem whose buffers are a non-null dummy address: good for
+    calls that are refused before anything is launched."""
+    import ctypes
+
+    from reart_amd import relax
+
+    cfg = relax.RelaxConfig(N=256, P=4, B=3, H=16, cano_idx=1, use_flow=1, flow_k=3, M_max=64, M_total=192, n_iter=100, ring=8,
+                            lambda_flow=1.0, trans_lr=1e-2, seg_lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, start_tau=1.0,
+                            end_tau=0.1, use_boxes=1, lambda_assign=1.0)
+    for k, v in over.items():
+        setattr(cfg, k, v)
+    dummy = 4096
+    bufs = relax.RelaxBuffers(**{n: dummy for n, _ in relax.RelaxBuffers._fields_ if n not in ("aux_stream", "ev_fork", "ev_join")})
+    return cfg, bufs, relax._lib_fns().reart_relax_workspace_bytes(ctypes.byref(cfg))
+
+
+def _step(cfg, bufs, nbytes, workspace=4096):
+    import ctypes
+
+    from reart_amd import relax
+
+    return relax._lib_fns().reart_relax_step(ctypes.byref(cfg) if cfg is not None else None,
+                                             ctypes.byref(bufs) if bufs is not None else None, workspace, nbytes, None)
+
+
+def _step_batch(cases, K=None):
+    import ctypes
+
+    from reart_amd import relax
+
+    n = max(len(cases), 1)
+    cfgs = (relax.RelaxConfig * n)(*[c[0] for c in cases])
+    bufs = (relax.RelaxBuffers * n)(*[c[1] for c in cases])
+    ws = (ctypes.c_void_p * n)(*[4096] * n)
+    nbytes = max([c[2] for c in cases], default=0)
+    return relax._lib_fns().reart_relax_step_batch(cfgs, bufs, ws, nbytes, len(cases) if K is None else K, None)
+
+
+def test_step_entries_refuse_before_they_launch():
+    """Every refusal of reart_relax_step / reart_relax_step_batch is decided from the configuration and the buffer
+    addresses alone, before the first launch, so each is checked here without a device and with dummy addresses.  Left
+    out: what can only be decided after a launch (a kernel the runtime refuses: REART_ERR_LAUNCH) and the instances of a
+    batch that agree in geometry but differ in a tuning switch, which the launchers of the kernels turn down."""
+    good = _relax_case()
+    assert good[2] > 0
+    # reart_relax_step
+    assert _step(None, good[1], good[2]) == INVALID_ARG
+    assert _step(good[0], None, good[2]) == INVALID_ARG
+    assert _step(*good, workspace=None) == INVALID_ARG
+    assert _step(good[0], good[1], good[2] - 1) == INVALID_ARG
+    cfg, bufs, nbytes = _relax_case()
+    bufs.W1 = None
+    assert _step(cfg, bufs, nbytes) == INVALID_ARG
+    assert _step(_relax_case(P=33)[0], good[1], good[2]) == INVALID_ARG
+    assert _step(_relax_case(flow_k=2)[0], good[1], good[2]) == UNSUPPORTED
+    # reart_relax_step_batch: the instance count, then what no batch takes -- also not a batch of one
+    assert _step_batch([good], K=0) == INVALID_ARG
+    assert _step_batch([good] * 7) == INVALID_ARG
+    for over in (dict(use_grid=1), dict(search_mode=1), dict(use_boxes=0), dict(tune_cloud=1)):
+        assert _step_batch([_relax_case(**over)]) == UNSUPPORTED, over
+    assign = dict(use_assign=1, use_flow=0)
+    assert _step_batch([_relax_case(**assign), _relax_case(N=512, **assign)]) == INVALID_ARG
+    cfg, bufs, nbytes = _relax_case(**assign)
+    bufs.assign_map = None
+    assert _step_batch([(cfg, bufs, nbytes)]) == INVALID_ARG
+
+
+def test_step_refusals_need_no_call_of_the_runtime():
+    """Refusals that must not depend on the runtime's state (no device here; on a device, an earlier failed launch of
+    somebody else must not be reported in their place): Chamfer-mode instances that cannot share their launches, and a
+    single step with the assignment loss and no assign_map, which is refused before its forward is launched."""
+    cfg, bufs, nbytes = _relax_case(use_assign=1)
+    bufs.assign_map = None
+    assert _step(cfg, bufs, nbytes) == INVALID_ARG
+    good = _relax_case()
+    for over in (dict(N=512), dict(B=4), dict(use_flow=0), dict(use_assign=1)):
+        assert _step_batch([good, _relax_case(**over)]) == INVALID_ARG, over
+
+
 def test_structure_wrappers_have_no_cpu_fallback():
     from reart_amd.utils import graph_utils as gu
     from reart_amd.utils.lap import cdist
