@@ -42,6 +42,8 @@ typedef enum {
 #define REART_MAX_K_LIST 1024     /* K-NN searches with K > REART_MAX_K keep a    */
                                   /* sorted key list per query in LDS (one wave   */
                                   /* per query); above this they are unsupported  */
+#define REART_MAX_POSE_LEN 1024   /* frames B = T - 1 of the relaxation model and   */
+                                  /* the fused step: 1 <= B <= REART_MAX_POSE_LEN   */
 #define REART_MAX_D 256           /* point dimension of the K-NN searches and     */
                                   /* their backward: 1 <= D <= REART_MAX_D        */
 
@@ -190,7 +192,9 @@ int reart_flow_loss(const float *gt, const float *pred, const uint8_t *mask, int
  * (screw_se3/geo_utils.py:632-651) and the per-part rigid apply.
  *   out [B,N,3]; seg_part [N] i64 = arg-max of the noise-free logits (:70);
  *   trans_list [B,P,4,4]; saved for backward: yT [P,N], hT [H,N], hard_idx [N] i32.
- *   seg_part / trans_list / yT / hT / hard_idx may be NULL.  P <= 32. */
+ *   seg_part / trans_list / yT / hT / hard_idx may be NULL.  P <= 32.  A pose table [B,P] that fits in LDS is
+ *   served by the kernels of model.hip, a longer one (up to B = REART_MAX_POSE_LEN) by model_long.hip: the same
+ *   arithmetic per element, the same results bit for bit (see reart_base_path). */
 int reart_base_forward(const float *cano, int N, int P, int B,
                        const float *W1, const float *b1, const float *W2, int H,
                        const float *prop6d, const float *propt,
@@ -209,6 +213,12 @@ int reart_gumbel_noise(uint64_t seed, int64_t iter, int N, int P, float *out, vo
  * gradients of W1, b1, W2, proposal_6d [B,P,6], proposal_t [B,P,3].  Deterministic
  * (fixed-order chunked reductions, no atomics). */
 size_t reart_base_backward_workspace_bytes(int N, int P, int B, int H);
+/* Which kernels serve the model at a shape: 0 = pose table [B*P][12] (backward: also the gradient tile [B][64*3]) in LDS,
+ * 1 = the long path (forward: pose rows from a table in global memory; backward: frames in LDS tiles), chosen by fit alone
+ * and only where 0 does not fit; REART_ERR_UNSUPPORTED where neither serves (P > 32, B > REART_MAX_POSE_LEN beyond what
+ * fits in LDS, H too large for LDS).  backward: 0 = reart_base_forward, 1 = reart_base_backward.  The launchers decide
+ * with this very function.  Needs no device. */
+int reart_base_path(int P, int B, int H, int backward);
 int reart_base_backward(const float *cano, int N, int P, int B,
                         const float *W1, const float *b1, const float *W2, int H,
                         const float *prop6d, const float *propt,
@@ -251,7 +261,7 @@ int reart_adam_step_multi(int count, float *const *param, const float *const *gr
  * device memory, so one call enqueues a fixed launch sequence: capture it once in a
  * hipGraph / torch.cuda.CUDAGraph and replay. */
 typedef struct reart_relax_config {
-    int N, P, B, H;          /* points, parts (<=32), frames-1, seg-head width (128)      */
+    int N, P, B, H;          /* points, parts (<=32), frames-1 (<= REART_MAX_POSE_LEN), seg-head width (128) */
     int cano_idx;            /* position of the canonical frame in the T = B+1 sequence   */
     int use_flow;            /* --use_flow_loss                                           */
     int robust;              /* --use_robust_loss (Huber, delta 1)                        */
@@ -299,6 +309,8 @@ typedef struct reart_relax_config {
     int tune_share;          /* < 0: a query's search bound comes from its own seeds only; default: also from the    */
                              /*    seeds of the 15 neighbouring queries of its row (same results, fewer boxes), the  */
                              /*    candidates split over the waves of the search workgroup; 1: every wave all of them */
+    int tune_long;           /* 1: the model's long path (reart_base_path = 1) also where the pose table fits in LDS: */
+                             /*    same forward bit for bit, same backward sums; for tests and A/B timing            */
 } reart_relax_config;
 
 typedef struct reart_relax_buffers {
@@ -326,6 +338,10 @@ typedef struct reart_relax_buffers {
     const int *assign_map;
 } reart_relax_buffers;
 
+/* Bytes of one instance's workspace; 0 for a configuration the step does not take.  What grows with the sequence: the
+ * SoA images, search records and gradients are O(B * N); the backward's per-chunk partial rows are
+ * ceil(N / 16) * (P*H + 4*H + 12*B*P) floats (room for the 16-point form: at B = 1024, N = 4096, P = 20, H = 128 that is
+ * 256 rows of 1 MB, of which the default 32-point form writes 128 = 127 MB per iteration); the [R|t] table is 48 * B * P bytes. */
 size_t reart_relax_workspace_bytes(const reart_relax_config *cfg);
 /* once per problem: static SoA images of pc_list / reference sets, tau(iter) */
 int reart_relax_prepare(const reart_relax_config *cfg, const reart_relax_buffers *bufs,

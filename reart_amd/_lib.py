@@ -20,6 +20,7 @@ P = c_void_p  # every device pointer
 MAX_K = 16               # REART_MAX_K: K-NN list in registers
 MAX_K_LIST = 1024        # REART_MAX_K_LIST: K-NN list in LDS, the largest K of any search
 MAX_D = 256              # REART_MAX_D: point dimension of the K-NN searches and their backward
+MAX_POSE_LEN = 1024      # REART_MAX_POSE_LEN: frames T - 1 of the relaxation model and the fused step
 FPS_MAX_N_LDS = 12288    # REART_FPS_MAX_N_LDS: reart_fps, cloud staged in LDS
 FPS_MAX_N = 1 << 21      # REART_FPS_MAX_N: reart_fps_temp, 21-bit index in the tie key
 
@@ -50,6 +51,7 @@ PROTOTYPES = {
     "reart_base_forward": (c_int, [P, c_int, c_int, c_int, P, P, P, c_int, P, P, P, c_float, P, P, P, P, P, P, P]),
     "reart_gumbel_noise": (c_int, [ctypes.c_uint64, ctypes.c_int64, c_int, c_int, P, P]),
     "reart_base_backward_workspace_bytes": (c_size_t, [c_int] * 4),
+    "reart_base_path": (c_int, [c_int] * 4),
     "reart_base_backward": (c_int, [P, c_int, c_int, c_int, P, P, P, c_int, P, P, P, P, P, c_float, P,
                                     P, P, P, P, P, P, c_size_t, P]),
     "reart_compute_pc_transform": (c_int, [P, P, P, c_int, c_int, c_int, P, P]),

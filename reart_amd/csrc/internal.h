@@ -61,7 +61,8 @@ static inline Batched<A> reart_batched(const A *a, int K) {
     for (int k = 0; k < K && k < REART_BATCH_MAX; ++k) b.a[k] = a[k];
     return b;
 }
-int reart_base_forward_launch(const BaseFwdArgs *a, int K, hipStream_t st);         // same shapes, 1 <= K <= REART_BATCH_MAX
+// force_long: take the long path (model_long.hip) also where the pose table fits in LDS (reart_relax_config.tune_long)
+int reart_base_forward_launch(const BaseFwdArgs *a, int K, hipStream_t st, int force_long);   // same shapes, 1 <= K <= REART_BATCH_MAX
 struct FinalizeAdam {
     int enabled;
     float *W1, *b1, *W2, *p6d, *pt;   // parameters (updated in place)
@@ -85,7 +86,13 @@ struct StepBook {
     float lambda_flow, fixed_tau, end_tau, start_tau, beta1, beta2;
 };
 int reart_base_backward_launch(const BaseBwdArgs *args, const FinalizeAdam *adam, const StepBook *book, void *const *workspaces,
-                               size_t workspace_bytes, int K, hipStream_t st);     // adam / book: arrays of K, or NULL
+                               size_t workspace_bytes, int K, hipStream_t st, int force_long);     // adam / book: arrays of K, or NULL
+// ---- the same model for pose tables that do not fit in LDS (model_long.hip); which shapes: reart_base_path (model.hip)
+int reart_base_forward_long_launch(const BaseFwdArgs *a, int K, hipStream_t st);
+// the block kernel of the backward only (args as reart_base_backward_launch has prepared them: cpts, nchunk, partial, rt_table)
+int reart_base_backward_long_launch(const BaseBwdArgs *a, int K, hipStream_t st);
+// frames per LDS tile of that kernel (0: not even one fits); cpts = 0: without a hidden-gradient tile of its own
+int reart_base_bwd_long_tile(int P, int B, int H, int cpts, int *dp_sep, size_t *lds);
 #ifdef __HIPCC__
 // cosine schedule of utils/model_utils.py:33-37 evaluated in double like the host code
 __device__ __forceinline__ float reart_tau_schedule(long cur_iter, int n_iter, float end_t, float start_t) {

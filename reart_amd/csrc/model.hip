@@ -16,9 +16,9 @@
 // hidden activations, hard_idx [N] sampled part.
 #include "common.h"
 #include "internal.h"
+#include "model_dev.h"
 #include <math.h>
 
-#define RED_CHUNK 64    // points per partial-reduction chunk
 
 // ------------------------------------------------------------------------------- helpers
 #ifdef REART_PHASE_CLOCK   // diagnostic build only: shader-clock stamps of workgroup 0 per phase
@@ -37,108 +37,6 @@ extern "C" int reart_debug_phase_clock(unsigned long long *out) {
 #else
 #define PHASE_SYNC_TS(which, k) do { } while (0)
 #endif
-__device__ __forceinline__ float dot3f(const float *a, const float *b) {
-    return fmaf(a[2], b[2], fmaf(a[1], b[1], a[0] * b[0]));
-}
-__device__ __forceinline__ void cross3f(const float *a, const float *b, float *c) {
-    c[0] = a[1] * b[2] - a[2] * b[1];
-    c[1] = a[2] * b[0] - a[0] * b[2];
-    c[2] = a[0] * b[1] - a[1] * b[0];
-}
-__device__ __forceinline__ float norm3f(const float *a) {
-    return sqrtf((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]);
-}
-
-// screw_se3/geo_utils.py:632-651 (rows b1,b2,b3); same operation order as oracle/model.c
-__device__ __forceinline__ void r6d_to_matrix(const float *d6, float *R) {
-    const float *a1 = d6, *a2 = d6 + 3;
-    const float n1 = fmaxf(norm3f(a1), 1e-12f);
-    float b1[3] = {a1[0] / n1, a1[1] / n1, a1[2] / n1};
-    const float d = (b1[0] * a2[0] + b1[1] * a2[1]) + b1[2] * a2[2];
-    float u[3] = {a2[0] - d * b1[0], a2[1] - d * b1[1], a2[2] - d * b1[2]};
-    const float n2 = fmaxf(norm3f(u), 1e-12f);
-    float b2[3] = {u[0] / n2, u[1] / n2, u[2] / n2};
-    float b3[3];
-    cross3f(b1, b2, b3);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { R[c] = b1[c]; R[3 + c] = b2[c]; R[6 + c] = b3[c]; }
-}
-
-__device__ __forceinline__ void r6d_backward(const float *d6, const float *gR, float *g6) {
-    const float *a1 = d6, *a2 = d6 + 3;
-    const float n1r = norm3f(a1), n1 = fmaxf(n1r, 1e-12f);
-    float b1[3] = {a1[0] / n1, a1[1] / n1, a1[2] / n1};
-    const float d = (b1[0] * a2[0] + b1[1] * a2[1]) + b1[2] * a2[2];
-    float u[3] = {a2[0] - d * b1[0], a2[1] - d * b1[1], a2[2] - d * b1[2]};
-    const float n2r = norm3f(u), n2 = fmaxf(n2r, 1e-12f);
-    float b2[3] = {u[0] / n2, u[1] / n2, u[2] / n2};
-    float gb1[3] = {gR[0], gR[1], gR[2]}, gb2[3] = {gR[3], gR[4], gR[5]};
-    const float gb3[3] = {gR[6], gR[7], gR[8]};
-    float t[3];
-    cross3f(b2, gb3, t);
-    gb1[0] += t[0]; gb1[1] += t[1]; gb1[2] += t[2];
-    cross3f(gb3, b1, t);
-    gb2[0] += t[0]; gb2[1] += t[1]; gb2[2] += t[2];
-    float gu[3];
-    if (n2r > 1e-12f) {
-        const float s = dot3f(b2, gb2);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) gu[c] = (gb2[c] - b2[c] * s) / n2;
-    } else {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) gu[c] = gb2[c] / n2;
-    }
-    float ga2[3] = {gu[0], gu[1], gu[2]};
-    const float gd = -dot3f(gu, b1);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        gb1[c] += -d * gu[c] + gd * a2[c];
-        ga2[c] += gd * b1[c];
-    }
-    if (n1r > 1e-12f) {
-        const float s = dot3f(b1, gb1);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) g6[c] = (gb1[c] - b1[c] * s) / n1;
-    } else {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) g6[c] = gb1[c] / n1;
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) g6[3 + c] = ga2[c];
-}
-
-// v = R x + t with R row-major 3x3 (fmaf chain in ascending column order)
-__device__ __forceinline__ void apply_rt(const float *Rt /*[12]: R(9) t(3)*/, float x0, float x1,
-                                         float x2, float *v) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        float acc = x0 * Rt[3 * c];
-        acc = fmaf(x1, Rt[3 * c + 1], acc);
-        acc = fmaf(x2, Rt[3 * c + 2], acc);
-        v[c] = acc + Rt[9 + c];
-    }
-}
-
-// Philox4x32-10 counter-based generator (Salmon et al. 2011) for the in-kernel Gumbel noise
-__device__ __forceinline__ void philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
-                                           uint32_t k0, uint32_t k1, uint32_t *out) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-// -log(Exp(1)) sample: u in (0,1) -> e = -log u -> g = -log e   (F.gumbel_softmax recipe).
-// 23 random bits + 0.5: every value (k + 0.5) * 2^-23 is exactly representable, so u never
-// rounds to 1.0 (which would give e = 0, g = +inf and a NaN softmax once in 2^24 draws).
-__device__ __forceinline__ float gumbel_from_bits(uint32_t bits) {
-    const float u = ((float)(bits >> 9) + 0.5f) * (1.0f / 8388608.0f);
-    return -logf(-logf(u));
-}
 
 // ------------------------------------------------------------------------------- forward
 // Workgroup = W waves x the same 64 points, W = ceil(P/2): wave g owns parts {2g, 2g+1}.
@@ -150,8 +48,6 @@ __device__ __forceinline__ float gumbel_from_bits(uint32_t bits) {
 //   * the rigid apply of frame t is done by wave t mod W.
 // The kernel is latency bound (a few thousand dependent instructions per wave at one wave per
 // SIMD), so the design goal is the shortest per-wave instruction stream, not occupancy.
-#define FW_PTS 64
-#define FW_PG 2
 
 // HALF: a workgroup owns 32 points and the two halves of a wave work on different part pairs (lane = half * 32 +
 // point), so that the same chains run in W/2 waves per workgroup on twice as many workgroups (the kernel is bound by the
@@ -403,8 +299,31 @@ static void launch_base_fwd(const BaseFwdArgs *a, int K, hipStream_t st) {
     else launch_base_fwd_t<PP, true>(a, K, st);
 }
 
+// LDS bytes the launchers reserve a pose table of B frames against: the forward's bound (its largest instantiation) and the
+// backward's exact layout.  B = 0: what does not grow with the sequence -- all that the long kernels (model_long.hip) keep.
+static size_t base_fwd_lds_bound(int P, int B, int H) {
+    return ((size_t)B * P * 12 + 2 * FW_PTS * 32 + (size_t)H * (36 + FW_PTS) + 4 * FW_PTS) * sizeof(float);
+}
+static size_t base_bwd_lds(int P, int B, int H) {
+    const int PMAX = (P == 20 || P == 10 || P == 8) ? P : 32;
+    return sizeof(float) * ((size_t)(H + PMAX) * BW_LD + RED_CHUNK * 5 + PMAX + 4 +
+                            (size_t)B * RED_CHUNK * 3 + (size_t)H * PMAX + 12 * (size_t)B * P +
+                            (size_t)PMAX * BW_LD);
+}
+
+// Which kernels serve a shape: 0 = pose table in LDS (this file), 1 = the long path (model_long.hip), negative = neither.
+// By fit alone, and the launchers below ask this very function: a shape the in-LDS kernels take never reaches the long ones.
+extern "C" int reart_base_path(int P, int B, int H, int backward) {
+    if (P < 1 || B < 1 || H < 1) return REART_ERR_INVALID_ARG;
+    if (P > 32) return REART_ERR_UNSUPPORTED;
+    if ((backward ? base_bwd_lds(P, B, H) : base_fwd_lds_bound(P, B, H)) <= REART_MODEL_LDS_CAP) return 0;
+    if (B > REART_MAX_POSE_LEN) return REART_ERR_UNSUPPORTED;
+    if (backward) return reart_base_bwd_long_tile(P, B, H, 0, nullptr, nullptr) >= 1 ? 1 : REART_ERR_UNSUPPORTED;
+    return base_fwd_lds_bound(P, 0, H) <= REART_MODEL_LDS_CAP ? 1 : REART_ERR_UNSUPPORTED;
+}
+
 // the forward's one entry: K instances of one shape in one launch (K = 1: the C ABI below and the single fused step)
-int reart_base_forward_launch(const BaseFwdArgs *ak, int K, hipStream_t st) {
+int reart_base_forward_launch(const BaseFwdArgs *ak, int K, hipStream_t st, int force_long) {
     if (K < 1 || K > REART_BATCH_MAX) return REART_ERR_INVALID_ARG;
     const BaseFwdArgs &a = ak[0];
     for (int k = 1; k < K; ++k)      // one launch geometry for all
@@ -412,7 +331,9 @@ int reart_base_forward_launch(const BaseFwdArgs *ak, int K, hipStream_t st) {
             !ak[k].out_soa != !a.out_soa)
             return REART_ERR_INVALID_ARG;
     if (a.P < 1 || a.P > 32) return REART_ERR_UNSUPPORTED;
-    if (((size_t)a.B * a.P * 12 + 2 * FW_PTS * 32 + (size_t)a.H * (36 + FW_PTS) + 4 * FW_PTS) * sizeof(float) > 152 * 1024) return REART_ERR_UNSUPPORTED;
+    const int path = reart_base_path(a.P, a.B, a.H, 0);
+    if (path < 0) return path;
+    if (path == 1 || force_long) return reart_base_forward_long_launch(ak, K, st);
     switch (a.P) {
         case 20: launch_base_fwd<20>(ak, K, st); break;
         case 10: launch_base_fwd<10>(ak, K, st); break;
@@ -437,7 +358,7 @@ extern "C" int reart_base_forward(const float *cano, int N, int P, int B, const 
     a.gumbel = gumbel; a.tau = tau; a.N = N; a.P = P; a.B = B; a.H = H; a.Npad = 0;
     a.out = out; a.seg_part = seg_part; a.trans_list = trans_list; a.yT = yT; a.hT = hT;
     a.hard_idx = hard_idx;
-    return reart_base_forward_launch(&a, 1, (hipStream_t)stream);
+    return reart_base_forward_launch(&a, 1, (hipStream_t)stream, 0);
 }
 
 // The production noise stream, exported: out[n][p] = the Gumbel sample the forward kernel draws for (point n, part p) in
@@ -466,12 +387,6 @@ extern "C" int reart_gumbel_noise(uint64_t seed, int64_t iter, int N, int P, flo
 }
 
 // ------------------------------------------------------------------------------- backward
-// layout of one partial row / of the reduced gradient vector
-__host__ __device__ static inline int off_gW2() { return 0; }
-__host__ __device__ static inline int off_gW1(int P, int H) { return P * H; }
-__host__ __device__ static inline int off_gb1(int P, int H) { return P * H + 3 * H; }
-__host__ __device__ static inline int off_gRt(int P, int H) { return P * H + 4 * H; }
-__host__ __device__ static inline int n_out(int P, int H, int B) { return P * H + 4 * H + 12 * B * P; }
 
 // [R|t] table [B*P][12] in global memory, so that the backward can read it with scalar loads
 __global__ __launch_bounds__(256) void rt_table_kernel(const float *__restrict__ p6d,
@@ -500,10 +415,6 @@ __global__ __launch_bounds__(256) void rt_table_kernel(const float *__restrict__
 //      only the wave's own LDS order.  dp has storage of its own (the h tile stays read-only for the gW2 tiles); where
 //      the LDS budget does not allow that (a.dp_sep == 0) dp overwrites the h tile as before and one workgroup barrier
 //      separates the two roles.
-#define BW_LD (RED_CHUNK + 1)
-#define BW_WAVES 16                       // block size of every instance: the launch bound, the kernel's strides, the launcher
-#define BW_HID (BW_WAVES / 4)             // waves of the hidden-gradient role: dp, then gW1 / gb1 (4 row tiles at H = 128)
-#define BW_MFMA (BW_WAVES - BW_HID)       // waves of the gR|gt / gW2 role (12 tiles at B = 19, H = 128)
 #ifdef REART_PHASE_CLOCK   // stamp of another wave's lane 0 (the roles of the tail)
 #define PHASE_TS_WAVE(which, k, wave) do { if (blockIdx.x == 1 && (int)threadIdx.x == 64 * (wave)) g_phase_ts[which][k] = __builtin_amdgcn_s_memtime(); } while (0)
 #else
@@ -1061,7 +972,7 @@ static int launch_bwd_block(const BaseBwdArgs *ak, int K, size_t lds, hipStream_
 // instance k's backward workspace.  a.rt_table == NULL: the table is built into the workspace first (one extra tiny launch
 // per instance)
 int reart_base_backward_launch(const BaseBwdArgs *args, const FinalizeAdam *adam, const StepBook *book, void *const *workspaces,
-                               size_t workspace_bytes, int K, hipStream_t st) {
+                               size_t workspace_bytes, int K, hipStream_t st, int force_long) {
     if (K < 1 || K > REART_BATCH_MAX) return REART_ERR_INVALID_ARG;
     BaseBwdArgs ak[REART_BATCH_MAX];
     for (int k = 0; k < K; ++k) ak[k] = args[k];
@@ -1084,22 +995,23 @@ int reart_base_backward_launch(const BaseBwdArgs *args, const FinalizeAdam *adam
             a.rt_table = table;
         }
     }
-    const int PMAX = (a0.P == 20 || a0.P == 10 || a0.P == 8) ? a0.P : 32;
-    size_t lds = sizeof(float) * ((size_t)(a0.H + PMAX) * BW_LD + RED_CHUNK * 5 + PMAX + 4 +
-                                  (size_t)a0.B * RED_CHUNK * 3 + (size_t)a0.H * PMAX + 12 * (size_t)a0.B * a0.P +
-                                  (size_t)PMAX * BW_LD);
-    if (lds > 152 * 1024) return REART_ERR_UNSUPPORTED;
-    // the hidden gradient gets a tile of its own ([H][cpts + 1]) where it fits: then the tail's roles overlap
-    const size_t lds_dp = sizeof(float) * (size_t)a0.H * (a0.cpts + 1);
-    const int dp_sep = lds + lds_dp <= 152 * 1024;
-    if (dp_sep) lds += lds_dp;
-    for (int k = 0; k < K; ++k) ak[k].dp_sep = dp_sep;
+    const int path = reart_base_path(a0.P, a0.B, a0.H, 1);
+    if (path < 0) return path;
     int rc;
-    switch (a0.P) {
-        case 20: rc = launch_bwd_block<20>(ak, K, lds, st); break;
-        case 10: rc = launch_bwd_block<10>(ak, K, lds, st); break;
-        case 8: rc = launch_bwd_block<8>(ak, K, lds, st); break;
-        default: rc = launch_bwd_block<0>(ak, K, lds, st); break;
+    if (path == 1 || force_long) rc = reart_base_backward_long_launch(ak, K, st);   // the partial rows in frame tiles
+    else {
+        size_t lds = base_bwd_lds(a0.P, a0.B, a0.H);
+        // the hidden gradient gets a tile of its own ([H][cpts + 1]) where it fits: then the tail's roles overlap
+        const size_t lds_dp = sizeof(float) * (size_t)a0.H * (a0.cpts + 1);
+        const int dp_sep = lds + lds_dp <= 152 * 1024;
+        if (dp_sep) lds += lds_dp;
+        for (int k = 0; k < K; ++k) ak[k].dp_sep = dp_sep;
+        switch (a0.P) {
+            case 20: rc = launch_bwd_block<20>(ak, K, lds, st); break;
+            case 10: rc = launch_bwd_block<10>(ak, K, lds, st); break;
+            case 8: rc = launch_bwd_block<8>(ak, K, lds, st); break;
+            default: rc = launch_bwd_block<0>(ak, K, lds, st); break;
+        }
     }
     if (rc != REART_OK) return rc;
     Batched<FinalizeAdam> adb = {};
@@ -1132,7 +1044,7 @@ extern "C" int reart_base_backward(const float *cano, int N, int P, int B, const
     a.cano = cano; a.W2 = W2; a.p6d = prop6d; a.pt = propt; a.yT = yT; a.hT = hT;
     a.hard_idx = hard_idx; a.tau = tau; a.G = G; a.N = N; a.P = P; a.B = B; a.H = H;
     a.gW1 = gW1; a.gb1 = gb1; a.gW2 = gW2; a.g6d = g6d; a.gt = gt;
-    return reart_base_backward_launch(&a, nullptr, nullptr, &workspace, workspace_bytes, 1, (hipStream_t)stream);
+    return reart_base_backward_launch(&a, nullptr, nullptr, &workspace, workspace_bytes, 1, (hipStream_t)stream, 0);
 }
 
 // --------------------------------------------------------------- hard-label rigid apply

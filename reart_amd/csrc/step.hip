@@ -202,7 +202,8 @@ extern "C" int reart_relax_prepare(const reart_relax_config *cfg, const reart_re
     if (!workspace || workspace_bytes < p.total) return REART_ERR_INVALID_ARG;
     if (!bufs->cano || !bufs->pc_list || !bufs->iter || !bufs->tau) return REART_ERR_INVALID_ARG;
     if (cfg->use_flow && (!bufs->ref_loc || !bufs->ref_flow || !bufs->ref_off)) return REART_ERR_INVALID_ARG;
-    if (cfg->B > 1024) return REART_ERR_UNSUPPORTED;
+    static_assert(REART_MAX_POSE_LEN <= 1024, "relax_init_kernel: one thread per frame");
+    if (cfg->B > REART_MAX_POSE_LEN) return REART_ERR_UNSUPPORTED;
     char *ws = (char *)workspace;
     hipStream_t st = (hipStream_t)stream;
     SoaArgs sa = {};
@@ -727,6 +728,7 @@ struct StepGeom {
     int has_fl, has_aa, has_cg;  // stand-alone consumers: flow blend, assignment loss, Chamfer gradient
     int fl_one, cg_one;          // at most four partial lists per query for that consumer (its ONE instantiation)
     int fgx, fgy, ncg, post_blocks, N, B;
+    int long_model;              // tune_long: the model's long path also where the pose table fits in LDS
 };
 // One instance's iteration as data: the argument block of every launch and the geometry of the launches.  step_describe
 // fills it, step_launch launches it -- for one instance, or for K of equal geometry at once.
@@ -759,6 +761,7 @@ static int step_describe(const reart_relax_config *cfg, const reart_relax_buffer
     const int N = c.N, B = c.B, P = c.P, H = c.H;
     float *G = (float *)(ws + p.o_G);
     g.N = N; g.B = B; g.pruned = p.pruned; g.grid = c.use_grid ? 1 : 0; g.flow = c.use_flow ? 1 : 0;
+    g.long_model = c.tune_long > 0 ? 1 : 0;
 
     // forward: seg head + Gumbel-softmax + 6D + rigid apply (networks/model.py:39-70)
     BaseFwdArgs &fa = L.fa;
@@ -961,7 +964,7 @@ static int step_launch(const StepLaunch *L, int K, hipStream_t st, hipEvent_t *e
     if (K > 1 && !step_batchable(g)) return REART_ERR_UNSUPPORTED;
     // 1. forward: seg head + Gumbel-softmax + 6D + rigid apply (networks/model.py:39-70)
     MARK(0);
-    int rc = reart_base_forward_launch(gather(L, K, &StepLaunch::fa).a, K, st);
+    int rc = reart_base_forward_launch(gather(L, K, &StepLaunch::fa).a, K, st, g.long_model);
     if (rc != REART_OK) return rc;
     MARK(1);
     if (forward_only) return REART_OK;
@@ -1044,7 +1047,7 @@ static int step_launch(const StepLaunch *L, int K, hipStream_t st, hipEvent_t *e
     const Batched<FinalizeAdam> ad = gather(L, K, &StepLaunch::ad);
     const Batched<StepBook> bk = gather(L, K, &StepLaunch::bk);
     const Batched<void *> wb = gather(L, K, &StepLaunch::ws_bwd);
-    rc = reart_base_backward_launch(ba.a, ad.a, bk.a, wb.a, L[0].bwd_bytes, K, st);
+    rc = reart_base_backward_launch(ba.a, ad.a, bk.a, wb.a, L[0].bwd_bytes, K, st, g.long_model);
     if (rc != REART_OK) return rc;
     MARK(6);
     MARK(7);

@@ -67,7 +67,11 @@ def sample_gumbel(shape, device, dtype=torch.float32):
 
 
 class BaseModel(nn.Module):
-    """Relaxation model, cf. networks/model.py:11-70."""
+    """Relaxation model, cf. networks/model.py:11-70.
+
+    ``num_parts`` <= 32 and ``pose_len`` <= ``REART_MAX_POSE_LEN`` (1024).  A pose table that fits in LDS (at 20 parts:
+    ``pose_len`` <= 90 forward, <= 58 backward) runs the kernels of ``csrc/model.hip``, a longer one those of
+    ``csrc/model_long.hip``; ``reart_base_path`` tells which.  Same results either way."""
 
     def __init__(self, num_parts, pose_len, joint_trajectory=None, init_6d=None, init_t=None):
         super().__init__()
@@ -104,6 +108,9 @@ class BaseModel(nn.Module):
         gumbel = kwargs.get("gumbel")  # extension: injected noise (tests); default = torch RNG
         if gumbel is None:
             gumbel = sample_gumbel((cano_pc.shape[0], self.num_parts), cano_pc.device)
+        if p6d.shape[0] > _lib.MAX_POSE_LEN:
+            raise NotImplementedError(f"pose_len {p6d.shape[0]}: the relaxation model takes at most "
+                                      f"REART_MAX_POSE_LEN = {_lib.MAX_POSE_LEN} frames")
         W1, b1, W2 = self._weights()
         return _BaseForward.apply(cano_pc, W1, b1, W2, p6d, pt, gumbel, tau)
 

@@ -21,13 +21,15 @@ class RelaxConfig(ctypes.Structure):
                                                                                  ("use_assign", c_int), ("lambda_assign", c_float),
                                                                                  ("weight_decay", c_float)] + \
                [(n, c_int) for n in ("search_mode", "tune_slices", "tune_slices_flow", "tune_sparse", "tune_fwd_pts",
-                                     "tune_bwd_pts", "tune_reorder", "tune_cloud", "tune_xcd", "profile", "tune_share")]
+                                     "tune_bwd_pts", "tune_reorder", "tune_cloud", "tune_xcd", "profile", "tune_share",
+                                     "tune_long")]
 
 
 def tuning_from_env(env=None):
     """Experiment switches of the library, read ONCE per engine on the host (the library itself never looks at the
     environment): REART_SEARCH=brute, REART_PRUNE_SPLIT / REART_PRUNE_SPLIT3 (waves per search workgroup, 1..4),
-    REART_SPARSE (0 = dense scans only, 1..16), REART_FWD_PTS (64|32), REART_BWD_PTS (64|32|16), REART_REORDER=0, REART_CLOUD=1|2|4|8 (cloud-resident search: targets from an LDS copy, that many box slices per query group), REART_XCD=1 (one run of frames per XCD)."""
+    REART_SPARSE (0 = dense scans only, 1..16), REART_FWD_PTS (64|32), REART_BWD_PTS (64|32|16), REART_REORDER=0, REART_CLOUD=1|2|4|8 (cloud-resident search: targets from an LDS copy, that many box slices per query group), REART_XCD=1 (one run of frames per XCD),
+    REART_LONG=1 (the model's long-sequence kernels also where the pose table fits in LDS: tests and A/B timing)."""
     env = os.environ if env is None else env
     geti = lambda k: int(env[k]) if env.get(k, "") != "" else None
     t = {}
@@ -45,6 +47,8 @@ def tuning_from_env(env=None):
         t["tune_cloud"] = max(0, geti("REART_CLOUD"))
     if env.get("REART_XCD") == "1":
         t["tune_xcd"] = 1
+    if env.get("REART_LONG") == "1":
+        t["tune_long"] = 1
     if env.get("REART_SHARE") in ("0", "1"):        # 0: own seeds only; 1: neighbour seeds, every wave all candidates
         t["tune_share"] = -1 if env["REART_SHARE"] == "0" else 1
     return t
@@ -170,6 +174,9 @@ class RelaxEngine:
         self.cano = cano_pc.contiguous()
         self.pc_list = pc_list.contiguous()
         B, N, _ = self.pc_list.shape
+        if B > _lib.MAX_POSE_LEN:
+            raise NotImplementedError(f"a sequence of {B + 1} frames: the relaxation step takes at most "
+                                      f"REART_MAX_POSE_LEN = {_lib.MAX_POSE_LEN} frames beside the canonical one")
         c1, c2 = model.seg_head.model[0], model.seg_head.model[2]
         H, P = c1.weight.shape[0], c2.weight.shape[0]
         self.params = [c1.weight, c1.bias, c2.weight, model.proposal_6d, model.proposal_t]
@@ -399,7 +406,7 @@ class RelaxBatch:
     # shape and switch fields of reart_relax_config that every engine of a batch must share
     SAME = ("N", "P", "B", "H", "M_max", "use_flow", "robust", "euclidean", "flow_k", "use_grid", "use_boxes", "use_assign",
             "search_mode", "tune_slices", "tune_slices_flow", "tune_sparse", "tune_fwd_pts", "tune_bwd_pts", "tune_reorder",
-            "tune_cloud", "tune_xcd", "tune_share")
+            "tune_cloud", "tune_xcd", "tune_share", "tune_long")
 
     def _refresh(self):
         """The argument blocks are VALUES: re-read them from the engines (an engine may have been given new noise, new
