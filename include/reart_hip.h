@@ -488,7 +488,10 @@ int reart_fk_backward(const float *x, const int64_t *part, const float *G, int N
  *   the grouped tensor): row r takes point gather_idx[r] (i64, [B,S,K] flattened) of cloud
  *   r / (S*K); columns = [F (D) | Q - C[r / K]] (xyz_first = 0) or [Q | F] (xyz_first = 1,
  *   C may be NULL); F [B*Npts, D], Q [B*Npts, 3], C [B*S, 3]; Cin must equal D + 3.
- *   Wt [Cin, Cout] (transposed conv weight), bias [Cout] or NULL; pool_k in {0, 32, 64, 128};
+ *   Wt [Cin, Cout] (transposed conv weight), bias [Cout] or NULL; pool_k = 0 (no pooling) or any group size >= 1 that
+ *   divides rows (REART_ERR_INVALID_ARG otherwise): nsample 16, 24, 48 ..., group_all over any point count.  The pooled
+ *   output is the maximum over each group of the rows the un-pooled call writes, bit for bit; 32, 64 and 128 pool inside
+ *   the waves' own rows, every other size through LDS (groups above 128 rows: one workgroup per group);
  *   Y [rows (/pool_k), ldy], written at columns ycol0 .. ycol0 + Cout. */
 int reart_mlp_layer(const float *X, int ldx, const int64_t *gather_idx, int K, int S, int Npts,
                     const float *F, int D, const float *Q, const float *C, int xyz_first,
@@ -518,6 +521,26 @@ int reart_mlp_chain3_wide(const int64_t *gather_idx, int K, int S, int Npts, con
                           const float *C, const float *W1t, const float *b1, int C1, const float *W2t, const float *b2,
                           int C2, const float *W3t, const float *b3, int C3, int rows, float *Y, int ldy, int ycol0,
                           void *workspace, size_t workspace_bytes, void *stream);
+
+/* The fused gathered chain for the shapes the two kernels above are not built for: gathered input [F (D) | Q - C]
+ * (xyz_first = 0) or [Q - C | F] (xyz_first = 1; C may be NULL: absolute xyz; D = 0: F may be NULL) -> C1 -> C2 -> C3 (bias and
+ * ReLU each) -> max over the K rows of a group.  Activations stay in LDS, the weights stream through it as in
+ * reart_mlp_chain3_wide (workspace: 16-byte aligned, reart_mlp_chain_workspace_bytes(D, C1, C2, C3), rewritten by every call).
+ * Bit-identical to three reart_mlp_layer calls.
+ * reart_mlp_chain_serves (host only, no device needed): 1 for D in 0 .. 512, K in {16, 32, 64, 128}, C1 % 32 == 0, C3 % 32 == 0,
+ * C2 % 4 == 0, each <= 256, rows % 128 == 0 -- EXCEPT the shapes reart_mlp_chain3 (D = 3) and reart_mlp_chain3_wide (D % 4 == 0)
+ * are built for with xyz_first = 0, which stay theirs; 0 otherwise.  reart_mlp_chain returns REART_ERR_UNSUPPORTED where the
+ * predicate says 0 (call the layers one by one). */
+int reart_mlp_chain_serves(int D, int K, int C1, int C2, int C3, int rows, int xyz_first);
+size_t reart_mlp_chain_workspace_bytes(int D, int C1, int C2, int C3);
+int reart_mlp_chain(const int64_t *gather_idx, int K, int S, int Npts, const float *F, int D, const float *Q, const float *C,
+                    int xyz_first, const float *W1t, const float *b1, int C1, const float *W2t, const float *b2, int C2,
+                    const float *W3t, const float *b3, int C3, int rows, float *Y, int ldy, int ycol0, void *workspace,
+                    size_t workspace_bytes, void *stream);
+
+/* square_distance of networks/pointnet2_utils.py:30-51 for 3-d points: src [B,N,3], dst [B,M,3] -> out [B,N,M], the matmul
+ * expansion with torch's CPU rounding, d = ((-2*fma(qz,tz,fma(qy,ty,qx*tx))) + |q|^2) + |t|^2 (as in reart_three_nn). */
+int reart_square_distance(const float *src, const float *dst, int B, int N, int M, float *out, void *stream);
 
 /* 3-NN inverse-distance interpolation of PointNetFeaturePropagation
  * (networks/pointnet2_utils.py:326-336): xyz1 [B,N,3], xyz2 [B,S2,3], points2 [B,S2,D] ->

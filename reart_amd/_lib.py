@@ -75,6 +75,11 @@ PROTOTYPES = {
     "reart_mlp_chain3_wide_workspace_bytes": (c_size_t, [c_int] * 4),
     "reart_mlp_chain3_wide": (c_int, [P, c_int, c_int, c_int, P, c_int, P, P, P, P, c_int, P, P, c_int, P, P, c_int, c_int, P, c_int,
                                       c_int, P, c_size_t, P]),
+    "reart_mlp_chain_serves": (c_int, [c_int] * 7),
+    "reart_mlp_chain_workspace_bytes": (c_size_t, [c_int] * 4),
+    "reart_mlp_chain": (c_int, [P, c_int, c_int, c_int, P, c_int, P, P, c_int, P, P, c_int, P, P, c_int, P, P, c_int, c_int, P, c_int,
+                                c_int, P, c_size_t, P]),
+    "reart_square_distance": (c_int, [P, P, c_int, c_int, c_int, P, P]),
     "reart_three_nn": (c_int, [P, P, c_int, c_int, c_int, P, P, P]),
     "reart_three_interpolate_workspace_bytes": (c_size_t, [c_int] * 3),
     "reart_three_interpolate": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P, c_int, c_int, P, c_size_t, P]),

@@ -37,6 +37,7 @@ struct GemmArgs {
     const float *bias;                // [Cout]
     int rows, Cin, Cout, relu, pool_k;
     float *Y; int ldy, ycol0;         // [rows, ldy] or [rows / pool_k, ldy], written at columns ycol0..
+    int tile_rows;                    // ANY-pool kernels only: rows a workgroup owns (whole groups: <= 128, or one group > 128)
 };
 
 // Per-thread description of the A row this thread stages (fixed for the whole K loop): the
@@ -75,15 +76,28 @@ __device__ __forceinline__ float gemm_load_a(const GemmArgs &a, const ARow &w, i
 // NB = number of 32-column accumulators per wave: the workgroup tile is 128 rows x 32 NB columns.  The
 // layers pick the NB that wastes the fewest columns (Cout = 32 -> 1, 64 -> 2, 96 -> 3); wider layers use
 // NB = 2 (NB = 4 reuses the A fragment four times but halves the resident waves: measured slower).
-template <int NB, int BK>
+//
+// ANY = true: max-pool over a group size the wave layout does not divide (pool_k not in {32, 64, 128}).  A workgroup owns
+// whole groups -- floor(128 / pool_k) of them in one 128-row tile (the rest of the tile idles), or ONE group larger than 128
+// rows, which it walks in 128-row chunks with a running maximum.  The rows go through the same K loop (every row's dot
+// product is the un-pooled call's, whatever its place in a tile); only the epilogue differs: each 32 x 32 accumulator tile
+// is laid out row by row in LDS and the groups' maxima are taken from there.  ANY = false is the kernel as it was.
+template <int NB, int BK, bool ANY>
 __global__ __launch_bounds__(256) void mlp_gemm_kernel(GemmArgs a) {
     constexpr int BN = 32 * NB, LDB = BN + 4;
     constexpr int GM_BK = BK, GM_LDA = BK + 1;
     __shared__ float As[GM_BM * GM_LDA];
     __shared__ float Bs[GM_BK * LDB];
     __shared__ float Pm[4][BN];
+    __shared__ float Tm[ANY ? GM_BM * 33 : 1];       // ANY: one accumulator column block of the tile, [row][33]
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int row0 = blockIdx.x * GM_BM, col0 = blockIdx.y * BN;
+    int row0 = ANY ? blockIdx.x * a.tile_rows : blockIdx.x * GM_BM;
+    const int col0 = blockIdx.y * BN;
+    const int row_end = ANY ? min(a.rows, row0 + a.tile_rows) : a.rows;
+    float run[NB];                                    // ANY, pool_k > 128: running maxima of (rows tid / 32 mod 8, column tid % 32)
+#pragma unroll
+    for (int n = 0; n < NB; ++n) run[n] = -INFINITY;
+    do {
     f16v c[NB];
 #pragma unroll
     for (int n = 0; n < NB; ++n)
@@ -158,6 +172,35 @@ __global__ __launch_bounds__(256) void mlp_gemm_kernel(GemmArgs a) {
         __syncthreads();
     }
     // epilogue: C/D layout row = (reg&3) + 8*(reg>>2) + 4*(lane>>5), col = lane & 31
+    if (ANY) {
+        const int live = min(GM_BM, row_end - row0);           // rows of this tile that belong to the workgroup's groups
+#pragma unroll
+        for (int n = 0; n < NB; ++n) {
+            const int cn = col0 + 32 * n + (lane & 31);
+            const float bias = (a.bias && cn < a.Cout) ? a.bias[cn] : 0.f;
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+                float v = c[n][reg] + bias;
+                if (a.relu) v = v > 0.f ? v : 0.f;
+                Tm[(wv * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)) * 33 + (lane & 31)] = v;
+            }
+            __syncthreads();
+            if (a.pool_k <= GM_BM) {                           // whole groups inside the tile
+                const int ng = live / a.pool_k;
+                for (int e = tid; e < ng * 32; e += 256) {
+                    const int g = e >> 5, cc = e & 31;
+                    float m = -INFINITY;
+                    for (int j = 0; j < a.pool_k; ++j) m = fmaxf(m, Tm[(g * a.pool_k + j) * 33 + cc]);
+                    if (col0 + 32 * n + cc < a.Cout) a.Y[(size_t)(row0 / a.pool_k + g) * a.ldy + a.ycol0 + col0 + 32 * n + cc] = m;
+                }
+            } else {                                           // a chunk of the one large group
+                const int part = tid >> 5, cc = tid & 31;
+                for (int j = part * 16; j < part * 16 + 16 && j < live; ++j) run[n] = fmaxf(run[n], Tm[j * 33 + cc]);
+            }
+            __syncthreads();
+        }
+        continue;
+    }
     float mx[NB];
 #pragma unroll
     for (int n = 0; n < NB; ++n) {
@@ -193,6 +236,20 @@ __global__ __launch_bounds__(256) void mlp_gemm_kernel(GemmArgs a) {
         const int prow = (row0 + g * a.pool_k) / a.pool_k;
         if (row0 + g * a.pool_k < a.rows && col0 + cc < a.Cout) a.Y[(size_t)prow * a.ldy + a.ycol0 + col0 + cc] = m;
     }
+    } while (ANY && (row0 += GM_BM) < row_end);
+    if (ANY && a.pool_k > GM_BM) {                             // the eight row parts of every column meet in LDS
+#pragma unroll
+        for (int n = 0; n < NB; ++n) {
+            Tm[tid] = run[n];
+            __syncthreads();
+            if (tid < 32) {
+                float m = Tm[tid];
+                for (int p = 1; p < 8; ++p) m = fmaxf(m, Tm[p * 32 + tid]);
+                if (col0 + 32 * n + tid < a.Cout) a.Y[(size_t)blockIdx.x * a.ldy + a.ycol0 + col0 + 32 * n + tid] = m;
+            }
+            __syncthreads();
+        }
+    }
 }
 
 extern "C" int reart_mlp_layer(const float *X, int ldx, const int64_t *gather_idx, int K, int S, int Npts,
@@ -207,22 +264,25 @@ extern "C" int reart_mlp_layer(const float *X, int ldx, const int64_t *gather_id
     } else if (!X || ldx < Cin) {
         return REART_ERR_INVALID_ARG;
     }
-    if (pool_k && (pool_k != 32 && pool_k != 64 && pool_k != 128)) return REART_ERR_UNSUPPORTED;
-    if (pool_k && rows % pool_k != 0) return REART_ERR_INVALID_ARG;
+    if (pool_k < 0 || (pool_k && rows % pool_k != 0)) return REART_ERR_INVALID_ARG;
+    if (pool_k == 1) pool_k = 0;                       // groups of one row: the un-pooled call
+    const bool any = pool_k && pool_k != 32 && pool_k != 64 && pool_k != 128;
     GemmArgs a = {};
     a.X = X; a.ldx = ldx; a.idx = gather_idx; a.K = K; a.S = S; a.Npts = Npts; a.F = F; a.D = D; a.Q = Q; a.C = C;
     a.xyz_first = xyz_first; a.Wt = Wt; a.bias = bias; a.rows = rows; a.Cin = Cin; a.Cout = Cout; a.relu = relu;
     a.pool_k = pool_k; a.Y = Y; a.ldy = ldy; a.ycol0 = ycol0;
+    a.tile_rows = any ? (pool_k <= GM_BM ? (GM_BM / pool_k) * pool_k : pool_k) : GM_BM;
     // measured: NB = 4 for ALL wide layers is slower (7.5 vs 6.7 ms: half the resident waves), and for the gathered wide-K
     // first layers of sa2 (323 -> 128, whose A tile NB = 2 stages twice) alone as well (5.69 vs 5.57 ms per forward)
     // Cout = 196 (sa2's 128 -> 196): four 64-column blocks compute 256 columns for 196; ONE block of seven 32-column
     // accumulators computes 224 and stages the A tile once
     const int NB = Cout <= 32 ? 1 : (Cout <= 64 ? 2 : (Cout <= 96 ? 3 : ((Cout > 192 && Cout <= 224) ? 7 : 2)));
     const int BK = Cin <= 8 ? 8 : 16;   // measured: 32 for the wide layers is slower (7.76 vs 6.72 ms for the extractor)
-    const dim3 grid(reart_div_up(rows, GM_BM), reart_div_up(Cout, 32 * NB));
+    const dim3 grid(reart_div_up(rows, a.tile_rows), reart_div_up(Cout, 32 * NB));
     hipStream_t st = (hipStream_t)stream;
-#define GM_LAUNCH(NBv, BKv) hipLaunchKernelGGL((mlp_gemm_kernel<NBv, BKv>), grid, dim3(256), 0, st, a)
-#define GM_PICK(NBv) do { if (BK == 8) GM_LAUNCH(NBv, 8); else if (BK == 32) GM_LAUNCH(NBv, 32); else GM_LAUNCH(NBv, 16); } while (0)
+#define GM_LAUNCH(NBv, BKv) do { if (any) hipLaunchKernelGGL((mlp_gemm_kernel<NBv, BKv, true>), grid, dim3(256), 0, st, a); \
+                                 else hipLaunchKernelGGL((mlp_gemm_kernel<NBv, BKv, false>), grid, dim3(256), 0, st, a); } while (0)
+#define GM_PICK(NBv) do { if (BK == 8) GM_LAUNCH(NBv, 8); else GM_LAUNCH(NBv, 16); } while (0)
     switch (NB) {
         case 1: GM_PICK(1); break;
         case 2: GM_PICK(2); break;
@@ -924,6 +984,292 @@ extern "C" int reart_three_interpolate(const float *xyz1, const float *xyz2, con
     const int rc = reart_three_nn(xyz1, xyz2, B, N, S2, dist, idx, stream);
     if (rc != REART_OK) return rc;
     hipLaunchKernelGGL(interp3_kernel, dim3(N, B), dim3(256), 0, st, dist, idx, points2, N, S2, D, out, ldo, col0);
+    REART_CHECK_LAUNCH();
+    return REART_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// reart_mlp_chain: the same fusion for every shape the two kernels above are not built for -- any feature width D (0 and
+// D % 4 != 0 included), either column order, no centre, groups of 16 .. 128 rows and any widths up to 256, all of them
+// run-time values.  A workgroup owns 128 rows; a wave owns 32 of them and at most FOUR 32-column accumulators:
+//   * S = 4 (no layer wider than 128): four waves, each with every column of its rows;
+//   * S = 8 (a layer wider than 128): two waves share 32 rows and take columns 0-127 / 128-255.  While the hidden activations
+//     fit next to the weight slabs all 128 rows are in flight (RW = 128: eight waves); for the widest hidden layers half of
+//     them (RW = 64: four waves, the workgroup walks its 128 rows in two passes).
+// Weights stream in 16-row slabs from the images cw_image_kernel writes (a lane's B fragments next to each other: one 16-byte
+// LDS read per step), double buffered, one barrier per slab.  Layer 1's A slabs are staged from the gather (16-byte loads
+// where a thread's run lies inside an aligned stretch of the feature row), the next slab's loads in flight under the current
+// slab's MFMAs.  The three layers go through ONE slab loop.  The maximum is taken per 16 rows (accumulator registers 0-7 /
+// 8-15 of a wave are its rows 0-15 / 16-31), then over the K / 16 units of a group.
+// Every accumulator sees its k in ascending order through v_mfma_f32_32x32x2_f32 with zeros beyond Cin, as in mlp_gemm_kernel:
+// the bits are those of three reart_mlp_layer calls.
+struct ChainAnyArgs {
+    const int64_t *idx; int K, S, Npts;
+    const float *F; int D;            // features [B*Npts, D] (NULL when D = 0)
+    const float *Q, *C;               // xyz [B*Npts,3], centres [B*S,3] or NULL
+    int xyz_first;
+    const float *W1, *b1, *W2, *b2, *W3, *b3;   // weight IMAGES [Cin][32][S], biases
+    int C1, C2, C3;
+    int lda;                          // stride of the activation tile
+    int rows;                         // % 128 == 0
+    float *Y; int ldy, ycol0;
+};
+#define CA_BK 16
+#define CA_LDAS (CA_BK + 1)
+// the MFMAs of one slab for a wave with NACT column blocks: A of step kk at ap[kk], its B values at bp[kk * KSTR ..]
+template <int NACT, int KSTR>
+__device__ __forceinline__ void ca_slab_mfma(const float *__restrict__ ap, const float *__restrict__ bp, int kn, int kh, f16v (&acc)[4]) {
+#pragma unroll
+    for (int kk = 0; kk < CA_BK; kk += 2) {
+        float av = ap[kk];
+        av = kk + kh < kn ? av : 0.f;
+        const float4 b0 = *(const float4 *)(bp + kk * KSTR);
+        const float b[4] = {b0.x, b0.y, b0.z, b0.w};
+#pragma unroll
+        for (int n = 0; n < NACT; ++n) acc[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, b[n], acc[n], 0, 0, 0);
+    }
+}
+
+template <int S, int RW, int NT>
+__global__ __launch_bounds__(NT, (NT == 256 ? 2 : 1)) void mlp_chain_any_kernel(ChainAnyArgs a) {
+    constexpr int SL = S == 8 ? 12 : 4, KSTR = 32 * SL, SLABF = CA_BK * KSTR;        // LDS stride per (k, lane row), see CwSlab
+    constexpr int NBF = CA_BK * 8 * S, BPT = NBF / NT;                               // float4 of a slab, per thread
+    constexpr int RT = RW / 32, CH = NT / 64 / RT;                                   // row tiles, column halves
+    constexpr int AK = RW * CA_BK / NT, TPR = CA_BK / AK;                            // layer 1 staging: AK consecutive k of one row
+    static_assert(NBF % NT == 0 && (AK == 4 || AK == 8) && (CH == 1 || (CH == 2 && S == 8)), "chain_any: layout");
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int D = a.D, lda = a.lda, K = a.K, C3 = a.C3;
+    float *Bs2 = sm;                                   // [2][SLABF]: weight slabs
+    float *H = Bs2 + 2 * SLABF;                        // [RW][lda]: activation tile; layer 1's gather slabs [2][RW][17] live in it
+    float *Pm = H + RW * lda;                          // [8][C3]: maxima per 16 rows
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, kh = lane >> 5, lr = lane & 31;
+    const int rt = wv % RT, ch = wv / RT;
+    const int ar = tid / TPR, ak = (tid % TPR) * AK;
+    const int foff = a.xyz_first ? 3 : 0, xoff = a.xyz_first ? 0 : D;
+    const int boff = (kh * 32 + lr) * SL + 4 * ch;
+    int buf = 0;
+    f16v acc[4];
+#pragma unroll 1
+    for (int half = 0; half < GM_BM / RW; ++half) {
+        const int row0 = blockIdx.x * GM_BM + half * RW;
+        // this thread's gathered row of layer 1
+        const int r = row0 + ar;
+        const size_t prow = (size_t)(r / (a.S * K)) * a.Npts + (size_t)a.idx[r];
+        const float *q = a.Q + prow * 3;
+        const float *f = D ? a.F + prow * D : q;                       // D = 0: never selected, any valid address
+        float c0 = 0.f, c1 = 0.f, c2 = 0.f;
+        if (a.C) { const float *c = a.C + (size_t)(r / K) * 3; c0 = c[0]; c1 = c[1]; c2 = c[2]; }
+        // xyz - centre as bit patterns: a slab is put together with masks (see mlp_chain_wide_kernel)
+        const int x0 = __float_as_int(q[0] - c0), x1 = __float_as_int(q[1] - c1), x2 = __float_as_int(q[2] - c2);
+        auto load_a = [=](int k0, float (&v)[AK]) __attribute__((always_inline)) {
+            const int k = k0 + ak, kf = k - foff;
+            if (kf >= 0 && kf + AK <= D && ((((size_t)(f + kf)) & 15) == 0)) {
+#pragma unroll
+                for (int u = 0; u < AK; u += 4) {
+                    const float4 p = *(const float4 *)(f + kf + u);
+                    v[u] = p.x; v[u + 1] = p.y; v[u + 2] = p.z; v[u + 3] = p.w;
+                }
+            } else {
+#pragma unroll
+                for (int u = 0; u < AK; ++u) {
+                    const int fi = kf + u, kx = k + u - xoff;
+                    const int fin = fi >= 0 && fi < D;
+                    const int fv = __float_as_int(f[fin ? fi : 0]);
+                    v[u] = __int_as_float((fv & -fin) | (x0 & -(int)(kx == 0)) | (x1 & -(int)(kx == 1)) | (x2 & -(int)(kx == 2)));
+                }
+            }
+        };
+        // the three layers through ONE slab loop: layer 0 stages its A slabs from the gather, layers 1 and 2 read the tile
+#pragma unroll 1
+        for (int layer = 0; layer < 3; ++layer) {
+            const float *img = layer == 0 ? a.W1 : (layer == 1 ? a.W2 : a.W3);
+            const float *bias = layer == 0 ? a.b1 : (layer == 1 ? a.b2 : a.b3);
+            const int Cin = layer == 0 ? D + 3 : (layer == 1 ? a.C1 : a.C2), Cout = layer == 0 ? a.C1 : (layer == 1 ? a.C2 : C3);
+            const int nact = min(max(((Cout + 31) >> 5) - 4 * ch, 0), 4);            // this wave's column blocks (0: it idles)
+#pragma unroll
+            for (int n = 0; n < 4; ++n)
+#pragma unroll
+                for (int g = 0; g < 16; ++g) acc[n][g] = 0.f;
+            float av[AK];
+            float4 bw[BPT];
+            auto load_b = [&](int k0) __attribute__((always_inline)) {
+#pragma unroll
+                for (int h = 0; h < BPT; ++h) {
+                    const int e = tid + NT * h;
+                    const int k = min(k0 + e / (8 * S), Cin - 1), off = e % (8 * S);  // beyond Cin: the last row, against A = 0
+                    const float4 w = *(const float4 *)(img + ((size_t)k * 32 * S + 4 * off));
+                    bw[h] = w;
+                }
+            };
+            if (layer == 0) load_a(0, av);
+            load_b(0);
+            for (int k0 = 0; k0 < Cin; k0 += CA_BK, buf ^= 1) {
+                float *As = H + buf * (RW * CA_LDAS), *Bs = Bs2 + buf * SLABF;
+                if (layer == 0) {
+#pragma unroll
+                    for (int u = 0; u < AK; ++u) As[ar * CA_LDAS + ak + u] = av[u];
+                }
+#pragma unroll
+                for (int h = 0; h < BPT; ++h) {
+                    const int e = tid + NT * h, k = e / (8 * S), rem = e % (8 * S), blr = rem / (S / 4), bq = rem % (S / 4);
+                    *(float4 *)(Bs + (k * 32 + blr) * SL + 4 * bq) = bw[h];
+                }
+                __syncthreads();
+                if (k0 + CA_BK < Cin) {
+                    if (layer == 0) load_a(k0 + CA_BK, av);
+                    load_b(k0 + CA_BK);
+                }
+                const float *ap = layer == 0 ? As + (rt * 32 + lr) * CA_LDAS + kh : H + (rt * 32 + lr) * lda + k0 + kh;
+                const int kn = min(CA_BK, Cin - k0);
+                switch (nact) {
+                    case 0: break;
+                    case 1: ca_slab_mfma<1, KSTR>(ap, Bs + boff, kn, kh, acc); break;
+                    case 2: ca_slab_mfma<2, KSTR>(ap, Bs + boff, kn, kh, acc); break;
+                    case 3: ca_slab_mfma<3, KSTR>(ap, Bs + boff, kn, kh, acc); break;
+                    default: ca_slab_mfma<4, KSTR>(ap, Bs + boff, kn, kh, acc); break;
+                }
+            }
+            __syncthreads();           // every wave has read the layer's input (two waves share a row tile; the gather slabs alias it)
+            if (layer < 2) {           // bias + ReLU into the tile, columns < Cout
+                float *Ht = H + rt * 32 * lda;
+#pragma unroll
+                for (int n = 0; n < 4; ++n) {
+                    const int cn = 32 * (4 * ch + n) + lr;
+                    if (n < nact && cn < Cout) {
+                        const float bv = bias[cn];
+#pragma unroll
+                        for (int reg = 0; reg < 16; ++reg) {
+                            const float v = acc[n][reg] + bv;
+                            Ht[((reg & 3) + 8 * (reg >> 2) + 4 * kh) * lda + cn] = v > 0.f ? v : 0.f;
+                        }
+                    }
+                }
+            } else {                   // bias + ReLU + max over each 16 rows
+                const int unit = (half * RW + rt * 32) >> 4;
+#pragma unroll
+                for (int n = 0; n < 4; ++n) {
+                    if (n < nact) {
+                        const int cn = 32 * (4 * ch + n) + lr;
+                        const float bv = bias[cn];
+                        float lo = -INFINITY, hi = -INFINITY;
+#pragma unroll
+                        for (int reg = 0; reg < 8; ++reg) {
+                            const float v = acc[n][reg] + bv, w = acc[n][reg + 8] + bv;
+                            lo = fmaxf(lo, v > 0.f ? v : 0.f);
+                            hi = fmaxf(hi, w > 0.f ? w : 0.f);
+                        }
+                        lo = fmaxf(lo, __shfl_xor(lo, 32, 64));
+                        hi = fmaxf(hi, __shfl_xor(hi, 32, 64));
+                        if (lane < 32) { Pm[unit * C3 + cn] = lo; Pm[(unit + 1) * C3 + cn] = hi; }
+                    }
+                }
+            }
+        }
+        __syncthreads();                               // Pm complete; the tile is free for the next pass
+    }
+    const int ng = GM_BM / K, upg = K >> 4;            // groups of the workgroup's 128 rows, 16-row units per group
+    for (int e = tid; e < ng * C3; e += NT) {
+        const int g = e / C3, cc = e % C3;
+        float m = -INFINITY;
+        for (int u = 0; u < upg; ++u) m = fmaxf(m, Pm[(g * upg + u) * C3 + cc]);
+        a.Y[((size_t)blockIdx.x * ng + g) * a.ldy + a.ycol0 + cc] = m;
+    }
+}
+
+// LDS plan of a shape: image width S, rows in flight rw (128 while slabs + tile + maxima fit the 152 KiB the other chain
+// kernels ask for, else 64), tile stride
+static size_t ca_plan(int C1, int C2, int C3, int &S, int &rw, int &lda) {
+    lda = chain_lda(C1 > C2 ? C1 : C2);
+    S = (C1 > 128 || C2 > 128 || C3 > 128) ? 8 : 4;
+    const size_t slabf = (size_t)CA_BK * 32 * (S == 8 ? 12 : 4);
+    rw = 128;
+    size_t lds = sizeof(float) * (2 * slabf + (size_t)rw * lda + 8 * (size_t)C3);
+    if (lds > 152 * 1024) { rw = 64; lds = sizeof(float) * (2 * slabf + (size_t)rw * lda + 8 * (size_t)C3); }
+    return lds;
+}
+static size_t ca_image_floats(int Cin, int S) { return reart_align_up((size_t)Cin * 32 * S, 64); }
+
+extern "C" int reart_mlp_chain_serves(int D, int K, int C1, int C2, int C3, int rows, int xyz_first) {
+    if (D < 0 || D > 512 || (xyz_first != 0 && xyz_first != 1)) return 0;
+    if (K != 16 && K != 32 && K != 64 && K != 128) return 0;
+    if (C1 < 32 || C1 > 256 || C1 % 32 != 0 || C3 < 32 || C3 > 256 || C3 % 32 != 0 || C2 < 4 || C2 > 256 || C2 % 4 != 0) return 0;
+    if (rows < GM_BM || rows % GM_BM != 0) return 0;
+    if (!xyz_first) {                                  // the extractor's own scales stay with the kernels built for them
+        const bool sa1 = (C1 == 32 && C2 == 32 && C3 == 64 && K == 32) || (C1 == 64 && C2 == 64 && C3 == 128 && K == 64) ||
+                         (C1 == 64 && C2 == 96 && C3 == 128 && K == 128);
+        const bool sa2 = (C1 == 128 && C2 == 128 && C3 == 256 && K == 64) || (C1 == 128 && C2 == 196 && C3 == 256 && K == 128);
+        if (D == 3 && sa1) return 0;
+        if (D >= 4 && D % 4 == 0 && sa2) return 0;
+    }
+    return 1;
+}
+
+extern "C" size_t reart_mlp_chain_workspace_bytes(int D, int C1, int C2, int C3) {
+    if (D < 0 || C1 < 1 || C2 < 1 || C3 < 1 || C1 > 256 || C2 > 256 || C3 > 256) return 0;
+    const int S = (C1 > 128 || C2 > 128 || C3 > 128) ? 8 : 4;
+    return sizeof(float) * (ca_image_floats(D + 3, S) + ca_image_floats(C1, S) + ca_image_floats(C2, S));
+}
+
+template <int S, int RW, int NT>
+static int chain_any_launch(const ChainAnyArgs &a, size_t lds, hipStream_t st) {
+    if (lds > REART_LDS_DEFAULT_CAP &&
+        hipFuncSetAttribute((const void *)mlp_chain_any_kernel<S, RW, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024) != hipSuccess)
+        return REART_ERR_LAUNCH;
+    hipLaunchKernelGGL((mlp_chain_any_kernel<S, RW, NT>), dim3(a.rows / GM_BM), dim3(NT), lds, st, a);
+    REART_CHECK_LAUNCH();
+    return REART_OK;
+}
+
+extern "C" int reart_mlp_chain(const int64_t *gather_idx, int K, int S, int Npts, const float *F, int D, const float *Q, const float *C,
+                               int xyz_first, const float *W1t, const float *b1, int C1, const float *W2t, const float *b2, int C2,
+                               const float *W3t, const float *b3, int C3, int rows, float *Y, int ldy, int ycol0, void *workspace,
+                               size_t workspace_bytes, void *stream) {
+    if (rows < 0 || K < 1 || S < 1 || Npts < 1 || D < 0 || C1 < 1 || C2 < 1 || C3 < 1) return REART_ERR_INVALID_ARG;
+    if (rows == 0) return REART_OK;
+    if (!gather_idx || !Q || (D > 0 && !F) || !W1t || !b1 || !W2t || !b2 || !W3t || !b3 || !Y) return REART_ERR_INVALID_ARG;
+    if (ycol0 < 0 || ldy < ycol0 + C3 || rows % K != 0) return REART_ERR_INVALID_ARG;
+    if (!reart_mlp_chain_serves(D, K, C1, C2, C3, rows, xyz_first)) return REART_ERR_UNSUPPORTED;
+    if (!workspace || (((size_t)workspace) & 15) != 0 || workspace_bytes < reart_mlp_chain_workspace_bytes(D, C1, C2, C3)) return REART_ERR_INVALID_ARG;
+    ChainAnyArgs a = {};
+    a.idx = gather_idx; a.K = K; a.S = S; a.Npts = Npts; a.F = F; a.D = D; a.Q = Q; a.C = C; a.xyz_first = xyz_first;
+    a.b1 = b1; a.b2 = b2; a.b3 = b3; a.C1 = C1; a.C2 = C2; a.C3 = C3;
+    a.rows = rows; a.Y = Y; a.ldy = ldy; a.ycol0 = ycol0;
+    int Sw, rw;
+    const size_t lds = ca_plan(C1, C2, C3, Sw, rw, a.lda);
+    hipStream_t st = (hipStream_t)stream;
+    float *img1 = (float *)workspace, *img2 = img1 + ca_image_floats(D + 3, Sw), *img3 = img2 + ca_image_floats(C1, Sw);
+    hipLaunchKernelGGL(cw_image_kernel, dim3(64, 3), dim3(256), 0, st, W1t, D + 3, C1, Sw, img1, W2t, C1, C2, Sw, img2, W3t, C2, C3, Sw, img3);
+    REART_CHECK_LAUNCH();
+    a.W1 = img1; a.W2 = img2; a.W3 = img3;
+    if (Sw == 4) return chain_any_launch<4, 128, 256>(a, lds, st);
+    if (rw == 128) return chain_any_launch<8, 128, 512>(a, lds, st);
+    return chain_any_launch<8, 64, 256>(a, lds, st);
+}
+
+// ---------------------------------------------------------------------------------------
+// square_distance of networks/pointnet2_utils.py:30-51 for 3-d points: the matmul expansion with torch's CPU rounding, the
+// expression three_nn_expanded_kernel pins -- d = ((-2 * fma(qz, tz, fma(qy, ty, qx * tx))) + |q|^2) + |t|^2.
+__global__ __launch_bounds__(256) void square_distance_kernel(const float *__restrict__ src, const float *__restrict__ dst, int N, int M,
+                                                              size_t total, float *__restrict__ out) {
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
+        const size_t bn = e / M;
+        const int m = (int)(e % M);
+        const float *q = src + bn * 3, *t = dst + ((bn / N) * M + m) * 3;
+        const float qx = q[0], qy = q[1], qz = q[2], tx = t[0], ty = t[1], tz = t[2];
+        const float sq = (qx * qx + qy * qy) + qz * qz, st = (tx * tx + ty * ty) + tz * tz;
+        const float mm = fmaf(qz, tz, fmaf(qy, ty, qx * tx));
+        out[e] = ((-2.0f * mm) + sq) + st;
+    }
+}
+
+extern "C" int reart_square_distance(const float *src, const float *dst, int B, int N, int M, float *out, void *stream) {
+    if (B < 0 || N < 0 || M < 0) return REART_ERR_INVALID_ARG;
+    if (B == 0 || N == 0 || M == 0) return REART_OK;
+    if (!src || !dst || !out) return REART_ERR_INVALID_ARG;
+    const size_t total = (size_t)B * N * M;
+    const size_t blocks = (total + 255) / 256;
+    hipLaunchKernelGGL(square_distance_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, (hipStream_t)stream,
+                       src, dst, N, M, total, out);
     REART_CHECK_LAUNCH();
     return REART_OK;
 }

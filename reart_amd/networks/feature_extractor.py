@@ -12,7 +12,6 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from .pointnet2_utils import farthest_point_sample, index_points, query_ball_point
 
 
 def _fold(conv, bn):
@@ -121,132 +120,77 @@ def three_interpolate(xyz1, xyz2, points2, out, out_col):
     _lib.check(rc, "reart_three_interpolate")
 
 
-class _SAMsg(nn.Module):
-    """Parameter container + forward of PointNetSetAbstractionMsg (networks/pointnet2_utils.py:238-295)."""
-
-    def __init__(self, npoint, radius_list, nsample_list, in_channel, mlp_list):
-        super().__init__()
-        self.npoint, self.radius_list, self.nsample_list = npoint, radius_list, nsample_list
-        self.conv_blocks, self.bn_blocks = nn.ModuleList(), nn.ModuleList()
-        for mlp in mlp_list:
-            convs, bns, last = nn.ModuleList(), nn.ModuleList(), in_channel + 3
-            for out in mlp:
-                convs.append(nn.Conv2d(last, out, 1))
-                bns.append(nn.BatchNorm2d(out))
-                last = out
-            self.conv_blocks.append(convs)
-            self.bn_blocks.append(bns)
-        self.out_channels = sum(m[-1] for m in mlp_list)
-
-    def sample(self, xyz, start=None, cuda_mode=None):
-        """The part of the level that depends on COORDINATES only: farthest point sampling and the ball queries of every
-        scale -> (new_xyz [B,S,3], [idx [B,S,K] per scale]).  The caller may run it ahead of the previous level's
-        feature stacks (another stream)."""
-        fps = farthest_point_sample(xyz, self.npoint, start=start, cuda_mode=cuda_mode)
-        new_xyz = index_points(xyz, fps).contiguous()
-        return new_xyz, [query_ball_point(radius, K, xyz, new_xyz, cuda_mode=cuda_mode)
-                         for radius, K in zip(self.radius_list, self.nsample_list)]
-
-    def run(self, xyz, feats, start=None, cuda_mode=None, sampled=None):
-        """xyz [B,N,3], feats [B,N,D] (channel-last) -> new_xyz [B,S,3], new_feats [B,S,sum C]."""
-        B, N, _ = xyz.shape
-        S = self.npoint
-        new_xyz, idx_list = sampled if sampled is not None else self.sample(xyz, start=start, cuda_mode=cuda_mode)
-        out = torch.empty((B * S, self.out_channels), dtype=torch.float32, device=xyz.device)
-        col = 0
-        Q = xyz.reshape(B * N, 3)
-        F = feats.reshape(B * N, -1).contiguous()
-        for i, (radius, K) in enumerate(zip(self.radius_list, self.nsample_list)):
-            idx = idx_list[i]
-            h = None
-            n_layers = len(self.conv_blocks[i])
-            widths = tuple(c.weight.shape[0] for c in self.conv_blocks[i])
-            if FUSE_CHAIN and n_layers == 3 and F.shape[1] == 3 and widths + (K,) in CHAIN3:
-                # sa1: the activations between the three layers stay in LDS (one launch per scale instead of three)
-                folded = [_fold(conv, bn) for conv, bn in zip(self.conv_blocks[i], self.bn_blocks[i])]
-                mlp_chain3(folded, dict(idx=idx, F=F, Q=Q, C=new_xyz.reshape(B * S, 3), Npts=N), out, col)
-                col += widths[-1]
-                continue
-            if (FUSE_CHAIN and n_layers == 3 and widths + (K,) in CHAIN3_WIDE and F.shape[1] % 4 == 0 and (B * S * K) % 128 == 0
-                    and F.data_ptr() % 16 == 0):
-                # sa2: the same with the weights streamed through LDS
-                folded = [_fold(conv, bn) for conv, bn in zip(self.conv_blocks[i], self.bn_blocks[i])]
-                mlp_chain3_wide(folded, dict(idx=idx, F=F, Q=Q, C=new_xyz.reshape(B * S, 3), Npts=N), out, col)
-                col += widths[-1]
-                continue
-            for j, (conv, bn) in enumerate(zip(self.conv_blocks[i], self.bn_blocks[i])):
-                Wt, b = _fold(conv, bn)
-                last = j == n_layers - 1
-                if j == 0:  # grouped [features | xyz - centre], features first (:277-281)
-                    h = mlp_layer(None, Wt, b, gather=dict(idx=idx, F=F, Q=Q, C=new_xyz.reshape(B * S, 3), Npts=N,
-                                                           xyz_first=0),
-                                  pool_k=K if last else 0, out=out if last else None, out_col=col if last else 0)
-                else:
-                    h = mlp_layer(h, Wt, b, pool_k=K if last else 0, out=out if last else None,
-                                  out_col=col if last else 0)
-            col += self.conv_blocks[i][-1].weight.shape[0]
-        return new_xyz, out.reshape(B, S, self.out_channels)
+def mlp_chain(folded, gather, out, out_col):
+    """The fused chain for every other shape ``reart_mlp_chain_serves`` accepts (reart_mlp_chain): any D (``F`` None: D = 0),
+    either column order (``gather["xyz_first"]``), centres optional."""
+    L = _lib.lib()
+    (W1, b1), (W2, b2), (W3, b3) = folded
+    B, S, K = gather["idx"].shape
+    F = gather.get("F")
+    D = 0 if F is None else F.shape[1]
+    ws = _lib.workspace(L.reart_mlp_chain_workspace_bytes(D, W1.shape[1], W2.shape[1], W3.shape[1]), W1.device)
+    rc = L.reart_mlp_chain(_lib.ptr(gather["idx"]), K, S, gather["Npts"], _lib.ptr(F), D, _lib.ptr(gather["Q"]), _lib.ptr(gather.get("C")),
+                           int(gather.get("xyz_first", 0)), _lib.ptr(W1), _lib.ptr(b1), W1.shape[1], _lib.ptr(W2), _lib.ptr(b2), W2.shape[1],
+                           _lib.ptr(W3), _lib.ptr(b3), W3.shape[1], B * S * K, _lib.ptr(out), out.shape[1], out_col,
+                           _lib.ptr(ws), ws.numel(), _lib.stream())
+    _lib.check(rc, "reart_mlp_chain")
+    return out
 
 
-class _SAAll(nn.Module):
-    """PointNetSetAbstraction with group_all=True (networks/pointnet2_utils.py:194-235, 174-191)."""
-
-    def __init__(self, in_channel, mlp):
-        super().__init__()
-        self.mlp_convs, self.mlp_bns = nn.ModuleList(), nn.ModuleList()
-        last = in_channel
-        for out in mlp:
-            self.mlp_convs.append(nn.Conv2d(last, out, 1))
-            self.mlp_bns.append(nn.BatchNorm2d(out))
-            last = out
-
-    def run(self, xyz, feats):
-        B, N, _ = xyz.shape
-        if N not in (32, 64, 128):
-            raise NotImplementedError("group_all pooling is built for 32/64/128 points (the extractor has 128)")
-        idx = torch.arange(N, device=xyz.device, dtype=torch.int64).expand(B, 1, N).contiguous()
-        h, n_layers = None, len(self.mlp_convs)
-        for j, (conv, bn) in enumerate(zip(self.mlp_convs, self.mlp_bns)):
-            Wt, b = _fold(conv, bn)
-            last = j == n_layers - 1
-            if j == 0:  # [xyz | features], xyz first (sample_and_group_all :186-188)
-                h = mlp_layer(None, Wt, b, gather=dict(idx=idx, F=feats.reshape(B * N, -1).contiguous(),
-                                                       Q=xyz.reshape(B * N, 3), C=None, Npts=N, xyz_first=1),
-                              pool_k=N if last else 0)
-            else:
-                h = mlp_layer(h, Wt, b, pool_k=N if last else 0)
-        return h  # [B, C]
+def chain_serves(D, K, widths, rows, xyz_first):
+    """``reart_mlp_chain_serves``: the one predicate the launcher and this layer both ask."""
+    return len(widths) == 3 and bool(_lib.lib().reart_mlp_chain_serves(D, K, widths[0], widths[1], widths[2], rows, int(xyz_first)))
 
 
-class _FP(nn.Module):
-    """PointNetFeaturePropagation (networks/pointnet2_utils.py:298-348)."""
+def grouped_mlp(convs, bns, gather, out, col):
+    """The 1x1-conv + BatchNorm + ReLU stack of one scale over the gathered rows of ``gather`` (see ``mlp_layer``) and the max over
+    each group of K rows, written into out[:, col:col + C_last].  Three-layer stacks run as ONE launch where a fused kernel
+    serves the shape (the extractor's scales: reart_mlp_chain3 / _wide; whatever ``reart_mlp_chain_serves`` accepts:
+    reart_mlp_chain), everything else layer by layer -- the same bits either way."""
+    idx, F = gather["idx"], gather.get("F")
+    B, S, K = idx.shape
+    D = 0 if F is None else F.shape[1]
+    xyz_first = int(gather.get("xyz_first", 0))
+    n_layers = len(convs)
+    widths = tuple(c.weight.shape[0] for c in convs)
+    if FUSE_CHAIN and n_layers == 3:
+        folded = None
+        if not xyz_first and D == 3 and widths + (K,) in CHAIN3:
+            # sa1: the activations between the three layers stay in LDS (one launch per scale instead of three)
+            folded = [_fold(conv, bn) for conv, bn in zip(convs, bns)]
+            mlp_chain3(folded, gather, out, col)
+        elif (not xyz_first and widths + (K,) in CHAIN3_WIDE and D >= 4 and D % 4 == 0 and (B * S * K) % 128 == 0
+              and F.data_ptr() % 16 == 0):
+            # sa2: the same with the weights streamed through LDS
+            folded = [_fold(conv, bn) for conv, bn in zip(convs, bns)]
+            mlp_chain3_wide(folded, gather, out, col)
+        elif chain_serves(D, K, widths, B * S * K, xyz_first):
+            folded = [_fold(conv, bn) for conv, bn in zip(convs, bns)]
+            mlp_chain(folded, gather, out, col)
+        if folded is not None:
+            return out
+    h = None
+    for j, (conv, bn) in enumerate(zip(convs, bns)):
+        Wt, b = _fold(conv, bn)
+        last = j == n_layers - 1
+        h = mlp_layer(h, Wt, b, gather=gather if j == 0 else None, pool_k=K if last else 0, out=out if last else None,
+                      out_col=col if last else 0)
+    return out
+
+
+from .pointnet2_utils import (PointNetFeaturePropagation, PointNetSetAbstraction,  # noqa: E402  (they use the helpers above)
+                              PointNetSetAbstractionMsg)
+
+# the names these layers had while they were private to the extractor
+_SAMsg = PointNetSetAbstractionMsg
+_FP = PointNetFeaturePropagation
+
+
+class _SAAll(PointNetSetAbstraction):
+    """PointNetSetAbstraction with group_all=True under its former constructor."""
 
     def __init__(self, in_channel, mlp):
-        super().__init__()
-        self.mlp_convs, self.mlp_bns = nn.ModuleList(), nn.ModuleList()
-        last = in_channel
-        for out in mlp:
-            self.mlp_convs.append(nn.Conv1d(last, out, 1))
-            self.mlp_bns.append(nn.BatchNorm1d(out))
-            last = out
-
-    def run(self, xyz1, xyz2, points1, points2):
-        """xyz1 [B,N,3], xyz2 [B,S,3], points1 [B,N,D1] or None, points2 [B,S,D2] -> [B,N,C]."""
-        B, N, _ = xyz1.shape
-        S, D2 = points2.shape[1], points2.shape[2]
-        D1 = 0 if points1 is None else points1.shape[2]
-        X = torch.empty((B * N, D1 + D2), dtype=torch.float32, device=xyz1.device)
-        if D1:
-            X[:, :D1] = points1.reshape(B * N, D1)
-        if S == 1:
-            X[:, D1:] = points2.expand(B, N, D2).reshape(B * N, D2)
-        else:
-            three_interpolate(xyz1.contiguous(), xyz2.contiguous(), points2.contiguous(), X, D1)
-        h = X
-        for conv, bn in zip(self.mlp_convs, self.mlp_bns):
-            Wt, b = _fold(conv, bn)
-            h = mlp_layer(h, Wt, b)
-        return h.reshape(B, N, -1)
+        super().__init__(None, None, None, in_channel, mlp, True)
 
 
 class PointNet2Msg2(nn.Module):
@@ -254,15 +198,15 @@ class PointNet2Msg2(nn.Module):
 
     def __init__(self, out_dim, normal_channel=False):
         super().__init__()
-        if normal_channel:
-            raise NotImplementedError("the reference builds the extractor with normal_channel=False (:63)")
+        extra = 3 if normal_channel else 0          # normals ride along as three more input features (:13-16)
         self.out_dim, self.normal_channel = out_dim, normal_channel
-        self.sa1 = _SAMsg(512, [0.05, 0.1, 0.2], [32, 64, 128], 3, [[32, 32, 64], [64, 64, 128], [64, 96, 128]])
-        self.sa2 = _SAMsg(128, [0.2, 0.4], [64, 128], 128 + 128 + 64, [[128, 128, 256], [128, 196, 256]])
-        self.sa3 = _SAAll(512 + 3, [256, 512, 1024])
-        self.fp3 = _FP(1536, [256, 256])
-        self.fp2 = _FP(576, [256, 128])
-        self.fp1 = _FP(134, [128, 128])
+        self.sa1 = PointNetSetAbstractionMsg(512, [0.05, 0.1, 0.2], [32, 64, 128], 3 + extra,
+                                             [[32, 32, 64], [64, 64, 128], [64, 96, 128]])
+        self.sa2 = PointNetSetAbstractionMsg(128, [0.2, 0.4], [64, 128], 128 + 128 + 64, [[128, 128, 256], [128, 196, 256]])
+        self.sa3 = PointNetSetAbstraction(None, None, None, 512 + 3, [256, 512, 1024], True)
+        self.fp3 = PointNetFeaturePropagation(1536, [256, 256])
+        self.fp2 = PointNetFeaturePropagation(576, [256, 128])
+        self.fp1 = PointNetFeaturePropagation(134 + extra, [128, 128])
         self.conv1 = nn.Conv1d(128, out_dim, 1)
         self.bn1 = nn.BatchNorm1d(out_dim)
 
@@ -294,7 +238,12 @@ class PointNet2Msg2(nn.Module):
             raise RuntimeError("PointNet2Msg2 is inference-only here (call .eval()); the reference freezes it")
         _lib.require_gpu(xyz)
         B, _, N = xyz.shape
-        pts = xyz.permute(0, 2, 1).contiguous().float()  # [B,N,3]
+        if xyz.shape[1] != (6 if self.normal_channel else 3):
+            raise ValueError(f"PointNet2Msg2(normal_channel={self.normal_channel}) takes [B,{6 if self.normal_channel else 3},N] input")
+        pts = xyz.permute(0, 2, 1).contiguous().float()  # [B,N,3] (with normals: [B,N,6] = xyz | normal)
+        feats0 = pts                                     # level-0 features: the input itself (:34-39)
+        if self.normal_channel:
+            pts = feats0[:, :, :3].contiguous()
         s1, s2 = fps_start if fps_start is not None else (None, None)
         samp1 = self.sa1.sample(pts, start=s1, cuda_mode=cuda_mode)
         samp2 = None
@@ -307,17 +256,27 @@ class PointNet2Msg2(nn.Module):
                 samp2 = self.sa2.sample(samp1[0], start=s2, cuda_mode=cuda_mode)
                 for t_ in (samp2[0], *samp2[1]):
                     t_.record_stream(main)           # allocated on the side stream, consumed on the main one
-        l1_xyz, l1 = self.sa1.run(pts, pts, sampled=samp1)                           # [B,512,3], [B,512,320]
+        l1_xyz, l1 = self.sa1.run(pts, feats0, sampled=samp1)                         # [B,512,3], [B,512,320]
         if samp2 is not None:
             main.wait_stream(side)
         l2_xyz, l2 = self.sa2.run(l1_xyz, l1, start=s2, cuda_mode=cuda_mode, sampled=samp2)   # [B,128,3], [B,128,512]
-        l3 = self.sa3.run(l2_xyz, l2)                                                # [B,1024]
+        l3 = self.sa3.pool_all(l2_xyz, l2)                                           # [B,1024]
         l2n = self.fp3.run(l2_xyz, l2_xyz[:, :1], l2, l3[:, None, :])                # [B,128,256]
         l1n = self.fp2.run(l1_xyz, l2_xyz, l1, l2n)                                  # [B,512,128]
-        l0n = self.fp1.run(pts, l1_xyz, torch.cat([pts, pts], dim=2), l1n)           # [B,N,128]
+        l0n = self.fp1.run(pts, l1_xyz, torch.cat([pts, feats0], dim=2), l1n)           # [B,N,128]
         Wt, b = _fold(self.conv1, self.bn1)
         feat = mlp_layer(l0n.reshape(B * N, -1), Wt, b)                              # [B*N,64]
         return feat.reshape(B, N, self.out_dim).permute(0, 2, 1).contiguous()
+
+
+def rec_freeze(model):
+    """feature_extractor.py:52-59: BatchNorm momentum 0 and no parameter of any descendant trainable."""
+    for m in model.modules():
+        if isinstance(m, nn.modules.batchnorm._BatchNorm):
+            m.momentum = 0
+    for child in model.children():           # the parameters of every descendant; the root's own, if any, stay as they are
+        for p in child.parameters():
+            p.requires_grad = False
 
 
 def get_extractor(args):
