@@ -66,6 +66,41 @@ def under_launcher(env=None):
     return "RANK" in env and "WORLD_SIZE" in env
 
 
+DEVICES_ENV = "REART_LOCAL_DEVICES"
+
+
+def parse_devices(text, nproc):
+    """``"0,0,1"`` -> [0, 0, 1]: the GPU ordinal of every local rank, one entry per rank.  Raises SystemExit (the message a user
+    of the command line reads) on a wrong count, a negative entry or an entry that is no integer."""
+    out = []
+    for item in str(text).split(","):
+        try:
+            v = int(item.strip())
+        except ValueError:
+            raise SystemExit(f"device map {text!r}: {item.strip()!r} is not a GPU ordinal (expected integers, e.g. 0,0)")
+        if v < 0:
+            raise SystemExit(f"device map {text!r}: a GPU ordinal cannot be negative ({v})")
+        out.append(v)
+    if len(out) != int(nproc):
+        raise SystemExit(f"device map {text!r} names {len(out)} device(s) for {int(nproc)} local rank(s): one entry per rank")
+    return out
+
+
+def local_device(local_rank, devices=None, env=None):
+    """The GPU ordinal local rank ``local_rank`` binds to.  ``devices`` (a list of ordinals, or the comma-separated text of
+    ``--devices``) wins over the environment variable REART_LOCAL_DEVICES; with neither, rank r takes GPU r."""
+    env = os.environ if env is None else env
+    if devices is None:
+        devices = env.get(DEVICES_ENV) or None
+    if devices is None:
+        return int(local_rank)
+    if isinstance(devices, str):
+        devices = parse_devices(devices, len(devices.split(",")))
+    if not 0 <= int(local_rank) < len(devices):
+        raise SystemExit(f"local rank {local_rank} has no entry in the device map {list(devices)}")
+    return int(devices[int(local_rank)])
+
+
 def torchrun_command(script, argv, nproc, port=None, module=False):
     """The exact command the round driver uses for N > 1 (and the one this module spawns).  ``module=True``: ``script`` is
     a module name (``-m``)."""

@@ -650,6 +650,46 @@ def build_kinematic_from_base(result, cano_pc, pc_list, args):
                           knn=KNN(k=1, transpose_mode=True), **kin_kwargs)
 
 
+def project_from_base(args, sample, result, device, save_dir, dataset=None):
+    """The projection of a base result onto a kinematic model (README.md:125, run_robot.py:101-124 + the loop + the end of the
+    run), as ONE function for ``main`` (``--model kinematic --base_result_path``) and for the sweep's second stage: seeds,
+    KinematicModel from ``result`` (the dict of a base run's result.pkl), ``args.n_iter`` iterations of the projection loop
+    with the snapshots, ``finish`` (prints + result.pkl / model.pth.tar / result.txt under ``save_dir``).
+    -> dict: the energy terms, cd_err, parts, joint_connection, assign_refreshes, lap_fallbacks, iterations, model."""
+    torch.cuda.manual_seed_all(args.manual_seed)
+    torch.manual_seed(args.manual_seed)
+    np.random.seed(args.manual_seed)
+    random.seed(args.manual_seed)
+    from reart_amd.utils import lap as _lap
+
+    _lap.CANONICAL_TIES = bool(getattr(args, "deterministic", True))
+    assert args.cano_idx == result["cano_idx"]
+    cano_pc = torch.from_numpy(sample["cano_pc"]).float().to(device)
+    pc_list = torch.from_numpy(sample["pc_list"]).float().to(device)
+    os.makedirs(save_dir, exist_ok=True)
+    pc_ref_list = flow_ref_list = None
+    if args.use_flow_loss:
+        pc_ref_list, flow_ref_list = flow_references(args, sample, device, args.seq_path)
+    tau_func = functools.partial(tau_cosine, max_iter=args.n_iter, end_temp=args.end_tau, start_temp=args.start_tau)
+    model = build_kinematic_from_base(result, cano_pc, pc_list, args)
+    model.to(device)
+    snapshot = SnapshotPrinter(args, model, cano_pc, pc_list, None if args.synthetic and "gt_flow_list" not in sample else sample, tau_func)
+    n_iter = args.n_iter
+    loop = make_projection_loop(args, model, cano_pc, pc_list, pc_ref_list, flow_ref_list, tau_func)
+    i = 0
+    while i < n_iter:
+        losses = loop.iteration(i)
+        if i % args.snapshot_gap == 0 or i == n_iter - 1:
+            snapshot(i, losses)
+        i += 1
+    lap_report = None       # assignment problems solved in the loop / how many of them went to the host solver
+    if args.use_assign_loss:
+        lap_report = {"assign_refreshes": loop.lap_solves, "lap_fallbacks": loop.lap_fallbacks}
+    out = finish(args, model, cano_pc, pc_list, sample, save_dir, tau_func(cur_iter=n_iter), dataset, lap_report)
+    out.update(lap_report or {"assign_refreshes": 0, "lap_fallbacks": 0}, iterations=i, model=model)
+    return out
+
+
 def main(args):
     torch.cuda.manual_seed_all(args.manual_seed)
     torch.manual_seed(args.manual_seed)
@@ -678,6 +718,15 @@ def main(args):
                             else (os.path.basename(args.seq_path.rstrip("/")) or "sequence"))
     os.makedirs(save_dir, exist_ok=True)
 
+    if args.model == "kinematic" and args.resume is None:  # run_robot.py:101-124: joint tree from a base result
+        assert args.base_result_path is not None, "--model kinematic needs --base_result_path or --resume"
+        with open(args.base_result_path, "rb") as f:
+            result = pickle.load(f)
+        print(f"load base result from {args.base_result_path}")
+        model = project_from_base(args, sample, result, device, save_dir, dataset)["model"]
+        print("all done!")
+        return model
+
     pc_ref_list = flow_ref_list = None
     if args.use_flow_loss:
         pc_ref_list, flow_ref_list = flow_references(args, sample, device, args.seq_path)
@@ -693,20 +742,12 @@ def main(args):
             tau_func = lambda cur_iter: fixed_tau
             assert args.cano_idx == ckpt.get("cano_idx", args.cano_idx)
     else:
-        if args.resume is None:  # run_robot.py:101-124: joint tree from a base result
-            assert args.base_result_path is not None, "--model kinematic needs --base_result_path or --resume"
-            with open(args.base_result_path, "rb") as f:
-                result = pickle.load(f)
-            print(f"load base result from {args.base_result_path}")
-            assert args.cano_idx == result["cano_idx"]
-            model = build_kinematic_from_base(result, cano_pc, pc_list, args)
-        else:
-            ckpt = torch.load(args.resume[0], map_location=device, weights_only=False)
-            model = KinematicModel(pose_len=pc_list.shape[0], seg_part=ckpt["seg_part"].to(device),
-                                   cano_pc=ckpt["cano_pc"].to(device), knn=KNN(k=1, transpose_mode=True),
-                                   edge_index=ckpt["edge_index"], paths_to_base=ckpt["paths_to_base"],
-                                   reverse_topo=ckpt["reverse_topo"])
-            model.load_state_dict(ckpt["state_dict"], strict=True)
+        ckpt = torch.load(args.resume[0], map_location=device, weights_only=False)      # (without --resume: project_from_base, above)
+        model = KinematicModel(pose_len=pc_list.shape[0], seg_part=ckpt["seg_part"].to(device),
+                               cano_pc=ckpt["cano_pc"].to(device), knn=KNN(k=1, transpose_mode=True),
+                               edge_index=ckpt["edge_index"], paths_to_base=ckpt["paths_to_base"],
+                               reverse_topo=ckpt["reverse_topo"])
+        model.load_state_dict(ckpt["state_dict"], strict=True)
     model.to(device)
     chamfer_dist = ChamferDistance()
     knn_flow = KNN(k=3, transpose_mode=True)
@@ -760,7 +801,8 @@ def main(args):
 
 
 def finish(args, model, cano_pc, pc_list, sample, save_dir, tau, dataset=None, lap_report=None):
-    """run_robot.py:227-356: structure, energies, result files (the reference's file names and keys)."""
+    """run_robot.py:227-356: structure, energies, result files (the reference's file names and keys).
+    -> dict of what was printed: parts, joint_connection, cd_err and (not under --evaluate) the energy terms."""
     from reart_amd import tail
     from reart_amd.utils.kinematic_utils import edge_index2edges
     from reart_amd.utils.model_utils import compute_pc_transform
@@ -791,6 +833,8 @@ def finish(args, model, cano_pc, pc_list, sample, save_dir, tau, dataset=None, l
         print(f"Seg eval: RI: {metrics['ri']:.3f}")
     if "recon_err" in metrics:
         print(f"Recon eval: recon: {metrics['recon_err']:.3f}")
+    report = {"parts": int(trans_list.shape[1]), "joint_connection": conn_list,
+              "cd_err": float(metrics["cd_err"]) if "cd_err" in metrics else None}
     retarget_err = 9999      # run_robot.py:287-291: retargeting to the sequence's novel poses (kinematic model only)
     if isinstance(model, KinematicModel) and dataset is not None and len(dataset.novel_pose_list):
         from reart_amd.utils.kinematic_utils import ik
@@ -804,6 +848,7 @@ def finish(args, model, cano_pc, pc_list, sample, save_dir, tau, dataset=None, l
                 f_result.write(f"{k}: {metrics[k]:.3f}\n")
         if not args.evaluate:
             energy = tail.energy_terms(cano_pc, pc_list, seg_part, trans_list, conn, args.cano_idx)
+            report.update({k: float(energy[k]) for k in ("ass_err", "screw_err", "group_err", "total_err")})
             print(f"Energy eval: total: {energy['total_err']:.3f}")
             for k in ("ass_err", "screw_err", "group_err", "total_err"):
                 print(f"{k}: {energy[k]:.3f}")
@@ -813,7 +858,7 @@ def finish(args, model, cano_pc, pc_list, sample, save_dir, tau, dataset=None, l
             for k in ("assign_refreshes", "lap_fallbacks"):
                 f_result.write(f"{k}: {lap_report[k]}\n")
     if args.evaluate:
-        return
+        return report
     save_dict = {"pred_cano_part": seg_part.cpu().numpy(), "pred_pose_list": trans_list.cpu().numpy(),
                  "cano_idx": args.cano_idx, "joint_connection": conn_list}
     save_dict.update(sample)
@@ -825,6 +870,7 @@ def finish(args, model, cano_pc, pc_list, sample, save_dir, tau, dataset=None, l
                           paths_to_base=model.paths_to_base, reverse_topo=model.reverse_topo)
     torch.save(model_dict, os.path.join(save_dir, "model.pth.tar"))
     print("saved", os.path.join(save_dir, "result.pkl"), "and", os.path.join(save_dir, "model.pth.tar"))
+    return report
 
 
 def build_parser():

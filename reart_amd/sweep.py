@@ -6,7 +6,9 @@ One optimisation *instance* = (sequence, cano_idx, seed); instances share nothin
 ``cano_idx`` x sequences.  Ranks own whole instances (static round-robin, no data-path
 collective); the only exchange is one ``all_gather`` of a fixed-size float record per instance
 (RCCL over xGMI when the backend is "nccl"; latency-bound: 64 B per instance), after which every
-rank can take the arg-min.
+rank can take the arg-min.  With ``--project`` the job goes on to the reference's third step (README.md:125): every
+sequence's winner is projected onto a kinematic model (``run_robot.project_from_base``), the sequences dealt to the ranks like
+the instances (``run_projections``).
 """
 import contextlib
 import os
@@ -142,7 +144,7 @@ def owner_of(plan):
 
 def gather_records(local, n_instances, device, plan=None):
     """local: {instance id: 1-D float tensor [RECORD]} of this rank -> [n_instances, RECORD] on every
-    rank, ordered by instance id.  Uses all_gather on padded per-rank blocks (equal message size).  ``plan``: the deal
+    rank, ordered by instance id.  Uses all_gather on padded per-rank blocks (equal message size; under gloo through host memory).  ``plan``: the deal
     (``deal``) the ranks ran under; round-robin when omitted."""
     world = dist.get_world_size() if dist.is_initialized() else 1
     rank = dist.get_rank() if dist.is_initialized() else 0
@@ -152,7 +154,14 @@ def gather_records(local, n_instances, device, plan=None):
     block = torch.full((per, RECORD), float("nan"), dtype=torch.float32, device=device)
     for slot, inst in enumerate(plan[rank]):
         block[slot] = local[inst].to(device=device, dtype=torch.float32)
-    if world > 1:
+    if world > 1 and dist.get_backend() == "gloo":
+        # gloo does not all-gather device tensors (ranks that share one GPU run under it: RCCL refuses two ranks per device):
+        # the padded blocks travel through host memory
+        host = block.cpu()
+        blocks = [torch.empty_like(host) for _ in range(world)]
+        dist.all_gather(blocks, host)
+        blocks = [b.to(device) for b in blocks]
+    elif world > 1:
         blocks = [torch.empty_like(block) for _ in range(world)]
         dist.all_gather(blocks, block)
     else:
@@ -588,6 +597,18 @@ def build_cli():
     p.add_argument("--energy", action="store_true", help="end every instance with structure extraction + energy (run_robot.py:224-321)")
     p.add_argument("--save_root", default="exp/sweep")
     p.add_argument("--backend", default=None, help="torch.distributed backend (default nccl = RCCL)")
+    p.add_argument("--devices", default=None, metavar="0,0",
+                   help="GPU ordinal of every local rank, comma-separated (default: rank r on GPU r; the environment variable "
+                        "REART_LOCAL_DEVICES says the same).  Ranks may share a GPU under --backend gloo only: RCCL refuses it")
+    p.add_argument("--launch_timeout", default=None, type=float, metavar="SECONDS",
+                   help="--gpus > 1: take the ranks down and exit with status 124 after this many seconds (default: no limit)")
+    p.add_argument("--project", action="store_true",
+                   help="stage two: project every sequence's winner onto a kinematic model (README.md:125: --model kinematic "
+                        "--base_result_path <winner> --assign_iter 0), the sequences dealt to the ranks by --shard; the files go to "
+                        "<save_root>/<seq>/kinematic/.  The loss switches, learning rates, seed and --deterministic are the sweep's own")
+    p.add_argument("--project_iter", default=15000, type=int, help="iterations of a projection")
+    p.add_argument("--project_downsample", default=2, type=int, help="--downsample of a projection (README.md:125)")
+    p.add_argument("--project_assign_gap", default=1, type=int, help="--assign_gap of a projection (README.md:125)")
     p.add_argument("--shard", choices=("round_robin", "lpt"), default="round_robin",
                    help="how instances are dealt to ranks: round_robin (instance i on rank i %% world) or lpt = longest first by "
                         "frames x points^2 onto the least loaded rank (sequence sets of unequal length)")
@@ -686,9 +707,116 @@ def save_instance(save_root, spec, result, sample=None, model=None, tau=None):
     return d
 
 
-def main(argv=None, runner=None):
+PROJECTION_FIELDS = ("iterations", "parts", "joint_connection", "total_err", "ass_err", "screw_err", "group_err", "cd_err",
+                     "assign_refreshes", "lap_fallbacks")
+
+
+def projection_args(args, spec):
+    """The ``run_robot`` arguments of one projection: README.md:125 (``--model kinematic --assign_iter 0 --assign_gap 1
+    --downsample 2``; the last two and the iteration count have their --project_* overrides), the loss switches, weights,
+    learning rates, seed and --deterministic of the sweep itself, everything else at ``run_robot``'s defaults."""
+    from . import run_robot as rr
+
+    kin = rr.build_parser().parse_args([])
+    for k in ("manual_seed", "deterministic", "use_flow_loss", "use_assign_loss", "use_robust_loss", "seg_lr", "trans_lr",
+              "weight_decay", "lambda_flow", "lambda_assign", "num_points", "normalize_file", "corr_model_path"):
+        setattr(kin, k, getattr(args, k))
+    kin.model, kin.cano_idx, kin.n_iter = "kinematic", int(spec["cano_idx"]), int(args.project_iter)
+    kin.assign_iter, kin.assign_gap, kin.downsample = 0, int(args.project_assign_gap), int(args.project_downsample)
+    kin.save_root = args.save_root
+    kin.synthetic = spec.get("synthetic") is not None
+    if kin.synthetic:
+        kin.synthetic_frames = int(spec["frames"])
+    else:
+        kin.seq_path = spec["seq_path"]
+    return kin
+
+
+def projection_dir(save_root, spec):
+    return os.path.join(save_root, spec["seq"], "kinematic")
+
+
+def _projector(args, device):
+    """projector(spec, base_result) for stage two: ``run_robot.project_from_base`` on this rank's GPU, on the sample the
+    relaxation of that instance used (a generated sequence is generated again from its seed)."""
+    import sys
+
+    from . import run_robot as rr
+
+    def project(spec, result):
+        kin = projection_args(args, spec)
+        dataset = None
+        if kin.synthetic:
+            sample = rr.synthetic_sequence(args.num_points, spec["cano_idx"], spec["frames"], args.use_flow_loss, seed=spec["synthetic"])
+        else:
+            from .dataset import Sequence
+
+            dataset = Sequence(spec["seq_path"], num_points=args.num_points, cano_idx=spec["cano_idx"])
+            sample = dataset[0]
+        with contextlib.redirect_stdout(sys.stderr):       # the snapshots and the final print: stdout keeps the one JSON line
+            return rr.project_from_base(kin, sample, result, device, projection_dir(args.save_root, spec), dataset)
+
+    return project
+
+
+def run_projections(instances, win, project, save_root, rank, world, device, policy="round_robin"):
+    """Stage two of the job.  ``win``: {sequence: winning instance id or None} (``winners``; the same on every rank); the
+    sequences that have a winner are dealt to the ranks (``deal`` on the winners' specs) and every rank runs its own, one after
+    another: ``project(spec, base_result)`` with the winner's result.pkl from the winner's instance directory (written by the
+    rank that ran it -- the caller has passed a barrier since).  A projection that raises is reported (``failed`` 1), it does
+    not end the job.  -> {sequence: report} on every rank (one all_gather_object)."""
+    import pickle
+    import sys
+    import time
+
+    specs = [instances[w] for w in win.values() if w is not None]
+    plan = deal(specs, world, policy)
+    mine = {}
+    for k in plan[rank]:
+        spec = specs[k]
+        entry = {"rank": rank, "device": str(device), "cano_idx": int(spec["cano_idx"]), "failed": 0}
+        entry.update({f: None for f in PROJECTION_FIELDS})
+        t0 = time.perf_counter()
+        try:
+            with open(os.path.join(instance_dir(save_root, spec), "result.pkl"), "rb") as f:
+                base = pickle.load(f)
+            out = project(spec, base)
+            entry.update({f: out.get(f) for f in PROJECTION_FIELDS})
+        except Exception as exc:
+            print(f"sweep: projection of {spec['seq']} (cano_idx {spec['cano_idx']}) failed: {type(exc).__name__}: {exc}", file=sys.stderr)
+            entry["failed"] = 1
+        entry["wall_s"] = round(time.perf_counter() - t0, 3)
+        mine[spec["seq"]] = entry
+    if dist.is_initialized():
+        parts = [None] * world
+        dist.all_gather_object(parts, mine)
+    else:
+        parts = [mine]
+    merged = {name: entry for part in parts for name, entry in part.items()}
+    return {spec["seq"]: merged[spec["seq"]] for spec in specs}
+
+
+def check_device_map(args, env=None):
+    """The parent's (and every rank's) check of --devices / REART_LOCAL_DEVICES, before anything is spawned and before any GPU
+    call -> the list of ordinals, or None for the default map.  Ranks that share a GPU need gloo."""
+    from . import launch
+
+    env = os.environ if env is None else env
+    text = args.devices if args.devices is not None else (env.get(launch.DEVICES_ENV) or None)
+    if text is None:
+        return None
+    nproc = int(env["LOCAL_WORLD_SIZE"]) if launch.under_launcher(env) and "LOCAL_WORLD_SIZE" in env else int(args.gpus)
+    devices = launch.parse_devices(text, nproc)
+    if len(set(devices)) < len(devices) and args.backend != "gloo":
+        raise SystemExit(f"device map {text!r} puts several ranks on one GPU: RCCL (the default backend, nccl) refuses that -- "
+                         f"add --backend gloo")
+    return devices
+
+
+def main(argv=None, runner=None, projector=None):
     """The sweep job.  ``runner(spec) -> dict`` replaces the GPU engine per instance (tests run the CPU oracle through it
-    under gloo); the product path (``runner is None``) needs a GPU per rank and raises without one."""
+    under gloo); the product path (``runner is None``) needs a GPU per rank and raises without one.
+    ``projector(spec, base_result) -> dict`` replaces the GPU projection of stage two (--project) the same way."""
     import json
     import shutil
     import sys
@@ -699,19 +827,24 @@ def main(argv=None, runner=None):
 
     t_start = time.perf_counter()
     args = build_cli().parse_args(argv)
+    if args.project and runner is not None and projector is None:
+        raise SystemExit("--project with a runner needs a projector too: the GPU projection cannot take a stand-in's results")
+    devices = check_device_map(args)
     if args.gpus > 1 and not launch.under_launcher():
         # N ranks of this module, started before anything here has touched the GPU
-        return launch.self_launch("reart_amd.sweep", list(sys.argv[1:] if argv is None else argv), args.gpus, module=True)
+        return launch.self_launch("reart_amd.sweep", list(sys.argv[1:] if argv is None else argv), args.gpus, module=True,
+                                  timeout=args.launch_timeout)
     world = launch.check_world(args.gpus) if launch.under_launcher() else 1
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if runner is None:
         if not torch.cuda.is_available():
             raise SystemExit("reart_amd.sweep needs an MI355X per rank: the HIP path has no CPU fallback")
-        if local_rank >= torch.cuda.device_count():
-            raise SystemExit(f"rank {rank}: no GPU {local_rank} on this node ({torch.cuda.device_count()} visible)")
-        torch.cuda.set_device(local_rank)
-        device = torch.device("cuda", local_rank)
+        ordinal = launch.local_device(local_rank, devices)
+        if ordinal >= torch.cuda.device_count():
+            raise SystemExit(f"rank {rank}: no GPU {ordinal} on this node ({torch.cuda.device_count()} visible)")
+        torch.cuda.set_device(ordinal)
+        device = torch.device("cuda", ordinal)
         from .utils import lap as _lap
 
         _lap.CANONICAL_TIES = bool(args.deterministic)
@@ -804,18 +937,40 @@ def main(argv=None, runner=None):
                         shutil.copyfile(mp, os.path.join(args.save_root, name, "model.pth.tar"))
         wall = time.perf_counter() - t_start          # this rank's wall clock from argument parsing to the winners (after the gather)
         rate = len(instances) * args.n_iter / wall
+    projections = None
+    if args.project:
+        # ---- stage two: the winners onto kinematic models (README.md:125), the sequences dealt to the ranks like the instances
+        if runner is None:
+            samples.clear()
+            del make_engine, on_finish                   # the relaxation engines are gone with run_sweep_engines; their memory
+            import gc                                     # goes back to the device before the projections allocate
+
+            gc.collect()
+            torch.cuda.empty_cache()
+        if projector is None:
+            projector = _projector(args, device)
+        t_project = time.perf_counter()
+        projections = run_projections(instances, win, projector, args.save_root, rank, world, device, args.shard)
+        project_wall = time.perf_counter() - t_project
+    if rank == 0:
+        if projections is not None:
+            for name, entry in projections.items():
+                table[name]["projection"] = entry
+        extra = {} if projections is None else {"project_wall_s": round(project_wall, 3),
+                                                "total_wall_s": round(time.perf_counter() - t_start, 3)}
         with open(os.path.join(args.save_root, "sweep.json"), "w") as f:
             json.dump({"world_size": world, "rccl_world": dist.get_world_size() if dist.is_initialized() else 1,
                        "backend": backend, "shard": args.shard, "ranks": ranks_info,
                        "n_instances": len(instances), "n_iter": args.n_iter, "energy": bool(args.energy),
                        "wall_s": round(wall, 3), "iterations_per_s": round(rate, 1),
-                       "rank0_stages": getattr(run_sweep_engines, "last_stages", None), "sequences": table}, f, indent=1)
+                       "rank0_stages": getattr(run_sweep_engines, "last_stages", None), "sequences": table, **extra}, f, indent=1)
         print(json.dumps({"sweep": os.path.join(args.save_root, "sweep.json"), "n_gpus": world,
                           "rccl_world": dist.get_world_size() if dist.is_initialized() else 1, "backend": backend,
                           "shard": args.shard, "ranks": ranks_info, "instances": len(instances),
                           "wall_s": round(wall, 3), "iterations_per_s": round(rate, 1),
                           "rank0_stages": getattr(run_sweep_engines, "last_stages", None),
-                          "winners": {k: v["winner_cano_idx"] for k, v in table.items()}}))
+                          "winners": {k: v["winner_cano_idx"] for k, v in table.items()},
+                          **({} if projections is None else {"projected": {k: v["rank"] for k, v in projections.items()}, **extra})}))
     if dist.is_initialized():
         dist.barrier()
         dist.destroy_process_group()
