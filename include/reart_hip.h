@@ -457,7 +457,7 @@ int reart_pn2_three_interpolate_grad(const float *grad_out, const int32_t *idx, 
  *   parent[c] (-1 = root), edge_of_part[c] (index of edge "c_parent" in edge_index),
  *   order = reverse_topo (parts from root to leaf), all i32 [P];
  *   axis, moment [E,3]; theta [B,E]; distance [B,E] or NULL (= 1e-6, :176);
- *   trans [B,P,4,4] out. */
+ *   trans [B,P,4,4] out.  P <= 64, the limit of reart_fk_backward (REART_ERR_INVALID_ARG above it). */
 int reart_fk_forward(const int32_t *parent, const int32_t *edge_of_part, const int32_t *order,
                      int P, const float *axis, const float *moment, const float *theta,
                      const float *distance, int B, int E, float *trans, void *stream);

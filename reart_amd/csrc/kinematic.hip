@@ -156,8 +156,8 @@ __global__ __launch_bounds__(64) void fk_fwd_kernel(const int *__restrict__ pare
 extern "C" int reart_fk_forward(const int32_t *parent, const int32_t *edge_of_part, const int32_t *order,
                                 int P, const float *axis, const float *moment, const float *theta,
                                 const float *distance, int B, int E, float *trans, void *stream) {
-    if (P < 1 || B < 0 || E < 0) return REART_ERR_INVALID_ARG;
-    if (B == 0) return REART_OK;
+    if (P < 1 || P > FK_MAXP || B < 0 || E < 0) return REART_ERR_INVALID_ARG;      // the limit of reart_fk_backward: a model is refused
+    if (B == 0) return REART_OK;                                                  // before its first forward, not at its first backward
     if (!parent || !edge_of_part || !order || !axis || !moment || !theta || !trans) return REART_ERR_INVALID_ARG;
     hipLaunchKernelGGL(fk_fwd_kernel, dim3(reart_div_up(B, 64)), dim3(64), 0, (hipStream_t)stream, parent,
                        edge_of_part, order, P, axis, moment, theta, distance, B, E, trans);
