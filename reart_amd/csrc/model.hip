@@ -75,7 +75,11 @@ void base_fwd_kernel(Batched<BaseFwdArgs> ab) {
     PHASE_TS(0, 0);
     const int P = (PP > 0) ? PP : a.P;
     // Prologue loads: the first batch of every group (pose parameters, W1|b1, one W2 column per thread) is
-    // issued before anything is stored to LDS, so the prologue is one memory round trip deep
+    // issued before anything is stored to LDS.  That is one memory round trip where the block covers B*P and 4*H
+    // (640 threads); at 320 threads the pose tail (wave 0), the W1|b1 tail (waves 0-2) and then the point, the
+    // temperature and the noise / iteration counter each wait behind the batch before: three to five round trips
+    // by the emitted code.  One batch for all of them (clamped per-thread slots) was built and timed: prologue
+    // 2.60 -> 2.69 us, workgroup 8.73 -> 8.55 us, not told from the run-to-run spread; dropped
     const int nRT = a.B * a.P;
     auto put_rt = [&](int e, const float (&d6)[6], const float (&tv)[3]) {
         float R[9];
@@ -757,38 +761,59 @@ __global__ __launch_bounds__(64 * BW_WAVES) void base_bwd_block_kernel(Batched<B
 // (2) sum the chunk partials in ascending chunk order; Gram-Schmidt backward for the
 // 6-vectors; optionally the Adam update of the very parameter this thread reduced.
 
-__device__ __forceinline__ void adam_update(float *p, float g, float *m, float *v, float lr,
+// One Adam step of one parameter from values ALREADY in registers: the caller loads p, m and v next to the partial rows
+// (none of them depends on the gradient), so behind the sums there is arithmetic and three stores, no memory round trip.
+struct AdamLoaded { float p, m, v; };
+__device__ __forceinline__ AdamLoaded adam_load(const float *p, const float *m, const float *v) {
+    AdamLoaded r;
+    r.p = *p; r.m = *m; r.v = *v;
+    return r;
+}
+__device__ __forceinline__ void adam_update(float *p, float g, float *m, float *v, const AdamLoaded &ld, float lr,
                                             float step_size_base, float bc2s, float beta1, float beta2,
                                             float eps, float weight_decay = 0.f) {
     (void)lr;
-    if (weight_decay != 0.f) g = g + weight_decay * (*p);   // torch.optim.Adam: grad.add(param, alpha=weight_decay)
-    float mm = *m, vv = *v;
+    if (weight_decay != 0.f) g = g + weight_decay * ld.p;   // torch.optim.Adam: grad.add(param, alpha=weight_decay)
+    float mm = ld.m, vv = ld.v;
     mm = mm + (g - mm) * (1.0f - beta1);
     vv = vv * beta2 + ((1.0f - beta2) * g) * g;
     const float denom = sqrtf(vv) / bc2s + eps;
     *m = mm; *v = vv;
-    *p = *p - step_size_base * (mm / denom);
+    *p = ld.p - step_size_base * (mm / denom);
 }
 
 __device__ __forceinline__ void base_bwd_finalize_body(const BaseBwdArgs &a, const FinalizeAdam &ad) {
     // Every output is summed over the partial rows by FOUR lanes, a quarter of the rows each (one batch of loads in
     // flight per lane at 128 rows instead of four dependent batches), combined in a fixed order by two xor-shuffles.
+    // Everything else a lane needs from memory -- the bias corrections of this step, the parameter it updates with its
+    // two moments, the 6-vector of the Gram-Schmidt backward -- is independent of the gradient and is loaded IN FRONT of
+    // the partial rows, so the whole body is one memory round trip deep; the divisions of the bias corrections stand
+    // behind the sums (in front of them they delayed the first partial load by a scalar round trip).
     const int og = blockIdx.x * 256 + threadIdx.x;
     const int nWr = a.P * a.H + 4 * a.H;                 // real weight entries
     const int nW = (4 * nWr + 63) & ~63;                 // four lanes per weight; pose groups start wave-aligned
     const int RQ = (a.nchunk + 3) >> 2;                  // rows per quarter
     const int o = og >> 2;                               // weight entry of this lane (first branch)
     const int no = n_out(a.P, a.H, a.B);
-    float ss_seg = 0.f, ss_tr = 0.f, bc2s = 1.f;
-    if (ad.enabled) {
-        // bias corrections of THIS step, written by the previous bookkeeping kernel / prepare
-        const double bc1 = ad.bias_corr[0];
-        ss_seg = (float)((double)ad.seg_lr / bc1);
-        ss_tr = (float)((double)ad.trans_lr / bc1);
-        bc2s = (float)ad.bias_corr[1];
-    }
+    // bias corrections of THIS step, written by the previous bookkeeping kernel / prepare
+    double bc1 = 1.0, bc2 = 1.0;
+    if (ad.enabled) { bc1 = ad.bias_corr[0]; bc2 = ad.bias_corr[1]; }
     if (og < nW) {
         if (o >= nWr) return;                            // whole quads leave together
+        // partial-row order is W2 | W1 | b1; moment order is W1 | b1 | W2
+        const int nW2 = a.P * a.H, nW1 = 3 * a.H;
+        const int kind = o < nW2 ? 0 : (o < nW2 + nW1 ? 1 : 2);
+        const int q = kind == 0 ? o : (kind == 1 ? o - nW2 : o - nW2 - nW1);          // entry inside its tensor
+        const int mo = kind == 0 ? nW1 + a.H + q : (kind == 1 ? q : nW1 + q);         // entry inside the moments
+        // (a branch per tensor, not a per-lane choice between the three pointers: that the compiler turns into a per-lane
+        // LOAD of the chosen pointer from the argument block, a round trip in front of the load it is for)
+        AdamLoaded ld = {0.f, 0.f, 0.f};
+        if (ad.enabled) {                                // all four lanes of the quad: one address
+            if (kind == 0) ld.p = ad.W2[q];
+            else if (kind == 1) ld.p = ad.W1[q];
+            else ld.p = ad.b1[q];
+            ld.m = ad.m[mo]; ld.v = ad.v[mo];
+        }
         float acc = 0.f;
         int c = (og & 3) * RQ;
         const int cend = c + RQ < a.nchunk ? c + RQ : a.nchunk;
@@ -810,30 +835,33 @@ __device__ __forceinline__ void base_bwd_finalize_body(const BaseBwdArgs &a, con
         acc = acc + __shfl_xor(acc, 1, 64);              // (q0 + q1), (q2 + q3): commutative, every lane of the quad agrees
         acc = acc + __shfl_xor(acc, 2, 64);
         if (og & 3) return;
-        // partial-row order is W2 | W1 | b1; moment order is W1 | b1 | W2
-        const int nW2 = a.P * a.H, nW1 = 3 * a.H;
-        if (o < nW2) {
-            a.gW2[o] = acc;
-            if (ad.enabled)
-                adam_update(ad.W2 + o, acc, ad.m + nW1 + a.H + o, ad.v + nW1 + a.H + o, ad.seg_lr, ss_seg, bc2s,
-                            ad.beta1, ad.beta2, ad.eps, ad.weight_decay);
-        } else if (o < nW2 + nW1) {
-            const int q = o - nW2;
+        const float ss_seg = (float)((double)ad.seg_lr / bc1), bc2s = (float)bc2;
+        if (kind == 0) {
+            a.gW2[q] = acc;
+            if (ad.enabled) adam_update(ad.W2 + q, acc, ad.m + mo, ad.v + mo, ld, ad.seg_lr, ss_seg, bc2s, ad.beta1, ad.beta2, ad.eps, ad.weight_decay);
+        } else if (kind == 1) {
             a.gW1[q] = acc;
-            if (ad.enabled)
-                adam_update(ad.W1 + q, acc, ad.m + q, ad.v + q, ad.seg_lr, ss_seg, bc2s, ad.beta1, ad.beta2, ad.eps, ad.weight_decay);
+            if (ad.enabled) adam_update(ad.W1 + q, acc, ad.m + mo, ad.v + mo, ld, ad.seg_lr, ss_seg, bc2s, ad.beta1, ad.beta2, ad.eps, ad.weight_decay);
         } else {
-            const int q = o - nW2 - nW1;
             a.gb1[q] = acc;
-            if (ad.enabled)
-                adam_update(ad.b1 + q, acc, ad.m + nW1 + q, ad.v + nW1 + q, ad.seg_lr, ss_seg, bc2s, ad.beta1,
-                            ad.beta2, ad.eps, ad.weight_decay);
+            if (ad.enabled) adam_update(ad.b1 + q, acc, ad.m + mo, ad.v + mo, ld, ad.seg_lr, ss_seg, bc2s, ad.beta1, ad.beta2, ad.eps, ad.weight_decay);
         }
     } else if (og < nW + 64 * a.B * a.P) {
         // one wave per (frame, part): 4 row quarters x 16 lanes; lane c < 12 of a quarter sums one entry of dL/d[R|t]
         // over its rows (all its loads in flight at once), the quarters meet through two xor-shuffles, then every
         // 16-lane group holds the 12 sums and runs the Gram-Schmidt backward; the first group updates the parameters
         const int q = og - nW, e = q >> 6, tq = (q >> 4) & 3, c = q & 15;
+        // lane c < 6 owns rotation entry c, lanes 6..8 the translation entries (the others repeat lane 8's addresses:
+        // loaded, never stored)
+        const int base6 = 3 * a.H + a.H + a.P * a.H, baset = base6 + 6 * a.B * a.P;
+        const int k = c < 6 ? c : (c < 9 ? c - 6 : 2);
+        const int mo = c < 6 ? base6 + 6 * e + k : baset + 3 * e + k;
+        float *const pp = c < 6 ? ad.p6d + 6 * (size_t)e + k : ad.pt + 3 * (size_t)e + k;
+        float d6[6];
+#pragma unroll
+        for (int u = 0; u < 6; ++u) d6[u] = a.p6d[6 * (size_t)e + u];
+        AdamLoaded ld = {0.f, 0.f, 0.f};
+        if (ad.enabled) ld = adam_load(pp, ad.m + mo, ad.v + mo);
         float acc = 0.f;
         if (c < 12) {
             const float *pr = a.partial + off_gRt(a.P, a.H) + 12 * (size_t)e + c;
@@ -853,30 +881,25 @@ __device__ __forceinline__ void base_bwd_finalize_body(const BaseBwdArgs &a, con
         float gRt[12];
         const int lane0 = (threadIdx.x & 63) & ~15;
 #pragma unroll
-        for (int k = 0; k < 12; ++k) gRt[k] = __shfl(acc, lane0 + k, 64);
+        for (int u = 0; u < 12; ++u) gRt[u] = __shfl(acc, lane0 + u, 64);
         // every lane of the group runs the (cheap) Gram-Schmidt backward; lane c < 6 then owns rotation
         // entry c and lanes 6..8 the translation entries: nine independent Adam updates instead of a
         // chain of nine on one lane
         if (c >= 9 || tq != 0) return;
         float g6[6];
-        r6d_backward(a.p6d + 6 * (size_t)e, gRt, g6);
-        const int base6 = 3 * a.H + a.H + a.P * a.H, baset = base6 + 6 * a.B * a.P;
+        r6d_backward(d6, gRt, g6);
+        const float ss_tr = (float)((double)ad.trans_lr / bc1), bc2s = (float)bc2;
+        float g;
         if (c < 6) {
-            float g = g6[0];
+            g = g6[0];
 #pragma unroll
-            for (int k = 1; k < 6; ++k) g = (c == k) ? g6[k] : g;
+            for (int u = 1; u < 6; ++u) g = (c == u) ? g6[u] : g;
             a.g6d[6 * (size_t)e + c] = g;
-            if (ad.enabled)
-                adam_update(ad.p6d + 6 * (size_t)e + c, g, ad.m + base6 + 6 * e + c, ad.v + base6 + 6 * e + c,
-                            ad.trans_lr, ss_tr, bc2s, ad.beta1, ad.beta2, ad.eps, ad.weight_decay);
         } else {
-            const int k = c - 6;
-            const float g = k == 0 ? gRt[9] : (k == 1 ? gRt[10] : gRt[11]);
+            g = k == 0 ? gRt[9] : (k == 1 ? gRt[10] : gRt[11]);
             a.gt[3 * (size_t)e + k] = g;
-            if (ad.enabled)
-                adam_update(ad.pt + 3 * (size_t)e + k, g, ad.m + baset + 3 * e + k, ad.v + baset + 3 * e + k,
-                            ad.trans_lr, ss_tr, bc2s, ad.beta1, ad.beta2, ad.eps, ad.weight_decay);
         }
+        if (ad.enabled) adam_update(pp, g, ad.m + mo, ad.v + mo, ld, ad.trans_lr, ss_tr, bc2s, ad.beta1, ad.beta2, ad.eps, ad.weight_decay);
     }
 }
 

@@ -43,7 +43,7 @@ static size_t take(size_t &off, size_t bytes) {
     return o;
 }
 
-#define FLOW_BS 256    // stand-alone flow_blend_kernel; inside post_kernel the blend uses CG_BS threads
+#define FLOW_BS 256    // stand-alone flow_blend_kernel; inside post_kernel the blend uses POST_FBS of the CG_BS threads
 #define CG_BS 1024
 // points (= live threads) of a flow-blend workgroup inside post_kernel.  Same-box A/B of the headline (tools/ab_headline.sh),
 // 1024 / 512 / 256: 12 560 / 12 950 / 12 520 it/s -- at 256 the blend workgroup lives 6.1 us instead of 10, but the 304 of them
@@ -280,14 +280,19 @@ __device__ __forceinline__ float huber1s_grad(float x) {
     return fabsf(x) <= 1.0f ? x : (x > 0.f ? 1.0f : -1.0f);
 }
 
-template <bool ONE, int FBS>   // ONE: S <= 4 -- every partial of a query is loaded before the first compare
+// SL: partial lists per query the instantiation is written for -- 1: exactly one (a.S == 1: every pruned path), its
+// record is loaded once; 4: up to four, every partial of a query is loaded before the first compare (clamped slices
+// repeat a record); 0: any number, in batches of four
+template <int SL, int FBS>
 __device__ __forceinline__ void flow_blend_body(const FlowArgs &a, const int bx, const int f, const int nbx) {
     __shared__ double s_red[FBS / REART_WAVE];
     const int n = bx * FBS + threadIdx.x;
     double term = 0.0;
     if (n < a.N) {
         // the kernel is a chain of dependent gathers (partials -> blocks -> reference flows): every
-        // stage issues all of its loads first and then reduces them without branches
+        // stage issues all of its loads first and then reduces them without branches; what no gather depends on (the
+        // point in both frames, the pair's offset into the reference flows) is requested with the first stage
+        constexpr int NU = SL == 1 ? 1 : 4;   // records per batch
         float kd[3] = {INFINITY, INFINITY, INFINITY};
         int ki[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff};
         const size_t stride = (size_t)a.B * a.N * 3, o0 = ((size_t)f * a.N + n) * 3;
@@ -295,11 +300,12 @@ __device__ __forceinline__ void flow_blend_body(const FlowArgs &a, const int bx,
         const float *c0 = complete_frame(a, f) + 3 * (size_t)n;
         const float *c1 = complete_frame(a, f + 1) + 3 * (size_t)n;
         const float c0v[3] = {c0[0], c0[1], c0[2]}, c1v[3] = {c1[0], c1[1], c1[2]};
-        for (int s0 = 0; s0 < (ONE ? 1 : a.S); s0 += 4) {
-            float e[4][3];
-            int q[4][3];
+        const int roff = a.ref_off[f];
+        for (int s0 = 0; s0 < (SL ? 1 : a.S); s0 += 4) {
+            float e[NU][3];
+            int q[NU][3];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
+            for (int u = 0; u < NU; ++u) {
                 const bool ok = s0 + u < a.S;
                 const size_t o = o0 + (size_t)(ok ? s0 + u : 0) * stride;
 #pragma unroll
@@ -307,7 +313,7 @@ __device__ __forceinline__ void flow_blend_body(const FlowArgs &a, const int bx,
                 if (!ok) { e[u][0] = INFINITY; e[u][1] = INFINITY; e[u][2] = INFINITY; }
             }
 #pragma unroll
-            for (int u = 0; u < 4; ++u)
+            for (int u = 0; u < NU; ++u)
 #pragma unroll
                 for (int k = 0; k < 3; ++k)   // (INF, x) never enters: INF < INF is false and ids of real entries are smaller
                     reart_top3_insert(kd, ki, e[u][k], e[u][k] < INFINITY ? q[u][k] : 0x7fffffff);
@@ -330,6 +336,9 @@ __device__ __forceinline__ void flow_blend_body(const FlowArgs &a, const int bx,
                     Z[cb][h] = *(const float4 *)(tz + blk + 4 * h);
                 }
             }
+            // all 18 loads are in flight before the first compare: left to itself the scheduler sinks the loads of a
+            // block into the insert code of the block before it (fewer live registers), one exposed round trip per group
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int k = 0; k < 3; ++k) { kd[k] = INFINITY; ki[k] = 0x7fffffff; }
 #pragma unroll
@@ -353,7 +362,7 @@ __device__ __forceinline__ void flow_blend_body(const FlowArgs &a, const int bx,
             int *so = a.seed_out + 3 * ((size_t)f * a.N + n);
             so[0] = ki[0]; so[1] = ki[1]; so[2] = ki[2];
         }
-        const float *rf = a.ref_flow + 3 * (size_t)a.ref_off[f];
+        const float *rf = a.ref_flow + 3 * (size_t)roff;
         float rfl[3][3];
 #pragma unroll
         for (int k = 0; k < 3; ++k)
@@ -440,20 +449,23 @@ struct CGradArgs {
 // Smallest (distance, index) key over the S slice partials of one query.  All loads of a batch of
 // four slices are issued before the first compare, and the compare is branch-free: the partial lists
 // come straight from the search kernel, so this is a chain of L2 round trips if written naively.
-template <bool ONE>   // ONE: S <= 4, a single batch (no loop: independent merges interleave)
+// SL (as in flow_blend_body): 1: S == 1, the one record is loaded once and compared once -- the same compare, so the
+// same result as four copies of it; 4: S <= 4, a single batch (no loop: independent merges interleave); 0: any S
+template <int SL>
 __device__ __forceinline__ void merge_slices(const float *__restrict__ pd, const int *__restrict__ pi, int S,
                                              size_t stride, size_t o0, int nmax, float &d, int &j) {
     d = INFINITY; j = 0x7fffffff;
-    for (int s0 = 0; s0 < (ONE ? 1 : S); s0 += 4) {
-        float e[4];
-        int q[4];
+    constexpr int NU = SL == 1 ? 1 : 4;
+    for (int s0 = 0; s0 < (SL ? 1 : S); s0 += 4) {
+        float e[NU];
+        int q[NU];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
+        for (int u = 0; u < NU; ++u) {
             const size_t o = o0 + (size_t)(s0 + u < S ? s0 + u : S - 1) * stride;   // duplicates change nothing
             e[u] = pd[o]; q[u] = pi[o];
         }
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
+        for (int u = 0; u < NU; ++u) {
             const bool l = (e[u] < d) | ((e[u] == d) & (q[u] < j));
             d = l ? e[u] : d; j = l ? q[u] : j;
         }
@@ -461,7 +473,7 @@ __device__ __forceinline__ void merge_slices(const float *__restrict__ pd, const
     j = j < 0 ? 0 : (j >= nmax ? nmax - 1 : j);   // in range whatever the inputs (NaN clouds)
 }
 
-template <bool ONE>
+template <int SL>
 __device__ __forceinline__ void chamfer_grad_body(const CGradArgs &a, const int bx, const int b, const int nbx) {
     __shared__ unsigned long long s_acc[CG_RANGE * 3];
     __shared__ double s_red[CG_BS / REART_WAVE];
@@ -470,18 +482,18 @@ __device__ __forceinline__ void chamfer_grad_body(const CGradArgs &a, const int 
     const float *x = a.X + (size_t)b * N * 3, *y = a.Y + (size_t)b * N * 3;
     const size_t stride = (size_t)a.B * N, ob = (size_t)b * N;
     for (int e = tid; e < CG_RANGE * 3; e += CG_BS) s_acc[e] = 0ull;
+    // own target: x -> y partials (loads issued before the barrier).  Without a branch (a thread beyond N repeats the last
+    // target and uses nothing of it), so that the scale of the fixed-point sums -- needed only by the sums below -- is
+    // requested in the same batch as the records and not loaded and waited for in front of them
+    const int io = r0 + tid, ioc = io < N ? io : N - 1;
+    float d0;
+    int j0;
+    merge_slices<SL>(a.pd0, a.pi0, a.S0, stride, ob + ioc, N, d0, j0);
     const int sbits = a.fx_bits[0];
-    // own target: x -> y partials (loads issued before the barrier)
-    const int io = r0 + tid;
-    float d0 = INFINITY;
-    int j0 = 0;
-    if (io < N) merge_slices<ONE>(a.pd0, a.pi0, a.S0, stride, ob + io, N, d0, j0);
     // the gathers of the own target are issued now: they complete under the walk over the observed points
-    float yn[3] = {0.f, 0.f, 0.f}, xo[3] = {0.f, 0.f, 0.f};
-    if (io < N) {
+    float yn[3], xo[3];
 #pragma unroll
-        for (int k = 0; k < 3; ++k) { yn[k] = y[3 * j0 + k]; xo[k] = x[3 * io + k]; }
-    }
+    for (int k = 0; k < 3; ++k) { yn[k] = y[3 * j0 + k]; xo[k] = x[3 * ioc + k]; }
     __syncthreads();
     float d1own = 0.f;
     constexpr int IL = 4;   // observed points in flight per thread
@@ -491,7 +503,7 @@ __device__ __forceinline__ void chamfer_grad_body(const CGradArgs &a, const int 
 #pragma unroll
         for (int u = 0; u < IL; ++u) {
             const int i = ib + u * CG_BS;
-            merge_slices<ONE>(a.pd1, a.pi1, a.S1, stride, ob + (i < N ? i : N - 1), N, d1[u], j1[u]);   // no branch: 4 merges in flight
+            merge_slices<SL>(a.pd1, a.pi1, a.S1, stride, ob + (i < N ? i : N - 1), N, d1[u], j1[u]);   // no branch: 4 merges in flight
         }
         float df[IL][3];
 #pragma unroll
@@ -541,13 +553,13 @@ __device__ __forceinline__ void chamfer_grad_body(const CGradArgs &a, const int 
 }
 
 // the stand-alone consumers; BATCH: K instances in one launch, instance k on the grid's plane z = k
-template <bool ONE, bool BATCH>
+template <int SL, bool BATCH>
 __global__ __launch_bounds__(CG_BS) void chamfer_grad_kernel(Batched<CGradArgs> ab) {
-    chamfer_grad_body<ONE>(ab.a[BATCH ? blockIdx.z : 0], blockIdx.x, blockIdx.y, gridDim.x);
+    chamfer_grad_body<SL>(ab.a[BATCH ? blockIdx.z : 0], blockIdx.x, blockIdx.y, gridDim.x);
 }
-template <bool ONE, bool BATCH>
+template <int SL, bool BATCH>
 __global__ __launch_bounds__(FLOW_BS) void flow_blend_kernel(Batched<FlowArgs> ab) {
-    flow_blend_body<ONE, FLOW_BS>(ab.a[BATCH ? blockIdx.z : 0], blockIdx.x, blockIdx.y, gridDim.x);
+    flow_blend_body<SL, FLOW_BS>(ab.a[BATCH ? blockIdx.z : 0], blockIdx.x, blockIdx.y, gridDim.x);
 }
 // Both consumers of the searches in ONE launch (same reason as knn_pruned_pair_kernel): workgroups
 // [0, nflow) blend the flow of (frame pair, 1024 points), the rest reduce the Chamfer gradient.
@@ -633,7 +645,8 @@ __device__ __forceinline__ void prof_body(const OrderArgs &o) {
         o.prof_acc[0] += 1ull; o.prof_acc[1] += hi - lo; o.prof_acc[2] += sum; o.prof_acc[3] += busy;
     }
 }
-struct PostArgs { FlowArgs fl; CGradArgs cg; OrderArgs od; int nfx, nflow, ncx, nwork, norder; };
+// the words that decide a workgroup's role come first: one scalar load, then only the role's own block
+struct PostArgs { int nfx, nflow, ncx, nwork, norder; FlowArgs fl; CGradArgs cg; OrderArgs od; };
 #ifdef REART_PHASE_CLOCK   // diagnostic build only (make stats; tools/phase_clock.py): lifetimes of one workgroup of every kind
 __device__ unsigned long long g_post_ts[8];      // flow blend | Chamfer gradient | launch order | profile: (start, end) each
 extern "C" int reart_debug_post_clock(unsigned long long *out) {
@@ -643,18 +656,19 @@ extern "C" int reart_debug_post_clock(unsigned long long *out) {
 #else
 #define POST_TS(k) do { } while (0)
 #endif
-template <bool ONE, bool BATCH>
+// Only the merged (pruned) step launches it, and that step's searches leave ONE record per query: the single-record forms
+template <bool BATCH>
 __global__ __launch_bounds__(CG_BS) void post_kernel(Batched<PostArgs> ab) {
     const PostArgs &a = ab.a[BATCH ? blockIdx.y : 0];
     const int w = blockIdx.x;
     if (w < a.nflow) {
         if (threadIdx.x >= POST_FBS) return;
         if (w == 1) POST_TS(0);
-        flow_blend_body<ONE, POST_FBS>(a.fl, w % a.nfx, w / a.nfx, a.nfx);
+        flow_blend_body<1, POST_FBS>(a.fl, w % a.nfx, w / a.nfx, a.nfx);
         if (w == 1) POST_TS(1);
     } else if (w < a.nwork) {
         if (w == a.nflow + 1) POST_TS(2);
-        chamfer_grad_body<ONE>(a.cg, (w - a.nflow) % a.ncx, (w - a.nflow) / a.ncx, a.ncx);
+        chamfer_grad_body<1>(a.cg, (w - a.nflow) % a.ncx, (w - a.nflow) / a.ncx, a.ncx);
         if (w == a.nflow + 1) POST_TS(3);
     } else if (w < a.nwork + a.norder) {
         if (w == a.nwork) POST_TS(4);
@@ -726,7 +740,7 @@ struct StepGeom {
     int has_search;              // pruned: there is a search launch (none for the assignment loss without flow) ...
     int static_order;            // ... in its cloud-resident form, whose items keep their launch order
     int has_fl, has_aa, has_cg;  // stand-alone consumers: flow blend, assignment loss, Chamfer gradient
-    int fl_one, cg_one;          // at most four partial lists per query for that consumer (its ONE instantiation)
+    int fl_sl, cg_sl;          // partial lists per query that consumer's instantiation serves: 1 | 4 (up to four) | 0 (any number)
     int fgx, fgy, ncg, post_blocks, N, B;
     int long_model;              // tune_long: the model's long path also where the pose table fits in LDS
 };
@@ -873,7 +887,7 @@ static int step_describe(const reart_relax_config *cfg, const reart_relax_buffer
         // four waves spread them over four times the compute units
         g.fgx = reart_div_up(N, merged ? POST_FBS : FLOW_BS); g.fgy = B;
         nfp = g.fgx * g.fgy;
-        g.has_fl = merged ? 0 : 1; g.fl_one = fl.S <= 4;
+        g.has_fl = merged ? 0 : 1; g.fl_sl = fl.S == 1 ? 1 : (fl.S <= 4 ? 4 : 0);
     }
     g.ncg = reart_div_up(N, CG_RANGE);
     if (c.use_assign) {
@@ -891,7 +905,7 @@ static int step_describe(const reart_relax_config *cfg, const reart_relax_buffer
         cg.fx_bits = (const int *)(ws + p.o_fx);
         cg.N = N; cg.B = B; cg.S0 = S0; cg.S1 = p.S1; cg.G = G;
         cg.loss_part = (double *)(ws + p.o_floss);
-        g.has_cg = merged ? 0 : 1; g.cg_one = cg.S0 <= 4 && cg.S1 <= 4;
+        g.has_cg = merged ? 0 : 1; g.cg_sl = (cg.S0 == 1 && cg.S1 == 1) ? 1 : ((cg.S0 <= 4 && cg.S1 <= 4) ? 4 : 0);
         if (merged) {
             PostArgs &pa = L.pa;
             pa.fl = fl; pa.cg = cg; pa.nfx = g.fgx; pa.nflow = pa.nfx * B; pa.ncx = g.ncg;
@@ -944,9 +958,10 @@ static int step_describe(const reart_relax_config *cfg, const reart_relax_buffer
 }
 
 // What reart_relax_step_batch takes (for any K) and what step_launch takes for K > 1: the box-pruned paths with the search
-// in its group form, and consumers that merge at most four partial lists per query
+// in its group form.  Their searches leave one record per query (step_plan: S = 1), so the consumers run in their
+// single-record forms, merged into post_kernel or on their own.
 static bool step_batchable(const StepGeom &g) {
-    return g.pruned && !g.static_order && (!g.has_fl || g.fl_one) && (!g.has_cg || g.cg_one);
+    return g.pruned && !g.static_order;
 }
 
 // member m of L[0..K): the argument of a batched kernel or launcher
@@ -1000,9 +1015,10 @@ static int step_launch(const StepLaunch *L, int K, hipStream_t st, hipEvent_t *e
     if (g.has_fl) {
         const dim3 fg(g.fgx, g.fgy, K);
         const Batched<FlowArgs> fb = gather(L, K, &StepLaunch::fl);
-        if (K > 1) hipLaunchKernelGGL((flow_blend_kernel<true, true>), fg, dim3(FLOW_BS), 0, fst, fb);
-        else if (g.fl_one) hipLaunchKernelGGL((flow_blend_kernel<true, false>), fg, dim3(FLOW_BS), 0, fst, fb);
-        else hipLaunchKernelGGL((flow_blend_kernel<false, false>), fg, dim3(FLOW_BS), 0, fst, fb);
+        if (K > 1) hipLaunchKernelGGL((flow_blend_kernel<1, true>), fg, dim3(FLOW_BS), 0, fst, fb);
+        else if (g.fl_sl == 1) hipLaunchKernelGGL((flow_blend_kernel<1, false>), fg, dim3(FLOW_BS), 0, fst, fb);
+        else if (g.fl_sl) hipLaunchKernelGGL((flow_blend_kernel<4, false>), fg, dim3(FLOW_BS), 0, fst, fb);
+        else hipLaunchKernelGGL((flow_blend_kernel<0, false>), fg, dim3(FLOW_BS), 0, fst, fb);
         REART_CHECK_LAUNCH();
     }
     if (forked && hipEventRecord((hipEvent_t)L[0].ev_join, fst) != hipSuccess) return REART_ERR_LAUNCH;
@@ -1029,14 +1045,15 @@ static int step_launch(const StepLaunch *L, int K, hipStream_t st, hipEvent_t *e
         // merge + recon loss + direct gradient term + fixed-point scatter; merged: with the flow consumer in one launch
         if (g.merged) {
             const Batched<PostArgs> pb = gather(L, K, &StepLaunch::pa);
-            if (K > 1) hipLaunchKernelGGL((post_kernel<true, true>), dim3(g.post_blocks, K), dim3(CG_BS), 0, st, pb);
-            else hipLaunchKernelGGL((post_kernel<true, false>), dim3(g.post_blocks), dim3(CG_BS), 0, st, pb);
+            if (K > 1) hipLaunchKernelGGL((post_kernel<true>), dim3(g.post_blocks, K), dim3(CG_BS), 0, st, pb);
+            else hipLaunchKernelGGL((post_kernel<false>), dim3(g.post_blocks), dim3(CG_BS), 0, st, pb);
         } else {
             const dim3 cgd(g.ncg, g.B, K);
             const Batched<CGradArgs> cb = gather(L, K, &StepLaunch::cg);
-            if (K > 1) hipLaunchKernelGGL((chamfer_grad_kernel<true, true>), cgd, dim3(CG_BS), 0, st, cb);
-            else if (g.cg_one) hipLaunchKernelGGL((chamfer_grad_kernel<true, false>), cgd, dim3(CG_BS), 0, st, cb);
-            else hipLaunchKernelGGL((chamfer_grad_kernel<false, false>), cgd, dim3(CG_BS), 0, st, cb);
+            if (K > 1) hipLaunchKernelGGL((chamfer_grad_kernel<1, true>), cgd, dim3(CG_BS), 0, st, cb);
+            else if (g.cg_sl == 1) hipLaunchKernelGGL((chamfer_grad_kernel<1, false>), cgd, dim3(CG_BS), 0, st, cb);
+            else if (g.cg_sl) hipLaunchKernelGGL((chamfer_grad_kernel<4, false>), cgd, dim3(CG_BS), 0, st, cb);
+            else hipLaunchKernelGGL((chamfer_grad_kernel<0, false>), cgd, dim3(CG_BS), 0, st, cb);
         }
     }
     REART_CHECK_LAUNCH();
