@@ -474,6 +474,25 @@ int reart_fk_backward(const float *x, const int64_t *part, const float *G, int N
                       float *g_axis, float *g_moment, float *g_theta, float *g_distance,
                       void *workspace, size_t workspace_bytes, void *stream);
 
+/* Retargeting: replaces the optimisation loop of ik (utils/kinematic_utils.py:200-266) for a kinematic model without
+ * distance_list, joint types or root motion: per novel pose m, n_iter steps of
+ *   pc = rigid_apply(fk(theta[m]), src, part);  loss = sum |pc - tgt[m]|^2;  Adam(amsgrad, no weight decay) on theta[m]
+ * with the gradient of fk and the apply as reart_fk_backward computes it.  All M poses in ONE launch, one workgroup
+ * per pose, the whole loop inside the kernel: no workspace, no host synchronisation, capturable; pose m's result does
+ * not depend on M, and two runs are bit-identical.
+ *   parent, edge_of_part, order, axis, moment: the tree as for reart_fk_forward, E = P - 1, distance = 1e-6 (:176);
+ *   src [n,3] sparse canonical points, part [n] i64 their parts (a label outside [0,P): the point is skipped);
+ *   tgt [M,n,3] where those points are in each novel pose;
+ *   theta_init [M,E] or NULL = 1e-6 everywhere (:230); the optimiser state starts at zero;
+ *   theta [M,E] out; loss [M, n_iter+1] out or NULL: loss[m,i] at the parameters before step i, loss[m,n_iter] at the
+ *   returned theta (n_iter = 0: theta = theta_init and its loss).
+ * P > 64 or E != P - 1: REART_ERR_INVALID_ARG; n > REART_IK_MAX_POINTS: REART_ERR_UNSUPPORTED; M = 0: REART_OK. */
+#define REART_IK_MAX_POINTS 1024
+int reart_ik_fit(const int32_t *parent, const int32_t *edge_of_part, const int32_t *order, int P,
+                 const float *axis, const float *moment, int E, const float *src, const int64_t *part, int n,
+                 const float *tgt, int M, const float *theta_init, int n_iter, float lr, float beta1, float beta2,
+                 float eps, float *theta, float *loss, void *stream);
+
 /* ------------------------------------------------------------------------ */
 /* PointNet++ correspondence extractor: dense layers and interpolation       */
 /* ------------------------------------------------------------------------ */

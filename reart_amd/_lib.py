@@ -21,6 +21,7 @@ MAX_K = 16               # REART_MAX_K: K-NN list in registers
 MAX_K_LIST = 1024        # REART_MAX_K_LIST: K-NN list in LDS, the largest K of any search
 MAX_D = 256              # REART_MAX_D: point dimension of the K-NN searches and their backward
 MAX_POSE_LEN = 1024      # REART_MAX_POSE_LEN: frames T - 1 of the relaxation model and the fused step
+IK_MAX_POINTS = 1024     # REART_IK_MAX_POINTS: sparse points of reart_ik_fit, held in LDS
 FPS_MAX_N_LDS = 12288    # REART_FPS_MAX_N_LDS: reart_fps, cloud staged in LDS
 FPS_MAX_N = 1 << 21      # REART_FPS_MAX_N: reart_fps_temp, 21-bit index in the tie key
 
@@ -69,6 +70,7 @@ PROTOTYPES = {
     "reart_fk_backward_workspace_bytes": (c_size_t, [c_int] * 3),
     "reart_fk_backward": (c_int, [P, P, P, c_int, P, P, P, c_int, P, P, P, P, c_int, c_int, P, P, P, P, P, P,
                                   c_size_t, P]),
+    "reart_ik_fit": (c_int, [P, P, P, c_int, P, P, c_int, P, P, c_int, P, c_int, P, c_int, c_float, c_float, c_float, c_float, P, P, P]),
     "reart_mlp_layer": (c_int, [P, c_int, P, c_int, c_int, c_int, P, c_int, P, P, c_int, P, P, c_int, c_int, c_int,
                                 c_int, c_int, P, c_int, c_int, P]),
     "reart_mlp_chain3": (c_int, [P, c_int, c_int, c_int, P, P, P, P, P, c_int, P, P, c_int, P, P, c_int, c_int, P, c_int, c_int, P]),

@@ -635,6 +635,7 @@ def build_cli():
     p.add_argument("--deterministic", dest="deterministic", action="store_true", default=True,
                    help="(default) assignment refreshes settle tied optima canonically (run_robot.py --deterministic): a sweep repeats run to run")
     p.add_argument("--no_deterministic", dest="deterministic", action="store_false")
+    p.add_argument("--fused_ik", action="store_true", help="--project: run_robot.py --fused_ik, the retarget error in one launch")
     return p
 
 
@@ -724,6 +725,7 @@ def projection_args(args, spec):
     kin.model, kin.cano_idx, kin.n_iter = "kinematic", int(spec["cano_idx"]), int(args.project_iter)
     kin.assign_iter, kin.assign_gap, kin.downsample = 0, int(args.project_assign_gap), int(args.project_downsample)
     kin.save_root = args.save_root
+    kin.fused_ik = bool(getattr(args, "fused_ik", False))
     kin.synthetic = spec.get("synthetic") is not None
     if kin.synthetic:
         kin.synthetic_frames = int(spec["frames"])

@@ -238,24 +238,95 @@ def edge_index2edges(edge_index):
     return [[int(v) for v in name.split("_")] for name in edge_index.keys()]
 
 
-def ik(dataset, model, device, verbose=True, vis=True, save_dir=None, **ikargs):
+def ik(dataset, model, device, verbose=True, vis=True, save_dir=None, fused=False, **ikargs):
     """Retargeting error (utils/kinematic_utils.py:200-266): for every novel pose of the sequence fit the model's
     free motion parameters (one ``theta`` row for a KinematicModel, one 6D / translation proposal per part for a
     BaseModel) to ONE point per ground-truth part with Adam(amsgrad, lr 0.1, 200 iterations), then measure how far
     the whole canonical cloud lands from its ground-truth novel position (mean Euclidean distance, x100).
     ``dataset``: an object with ``[0]`` -> sample, ``pose_list``, ``cano_idx``, ``novel_pose_list`` (the mirror
-    ``reart_amd.dataset.Sequence`` or the reference's).  ``vis`` / ``save_dir`` are accepted; nothing is drawn."""
+    ``reart_amd.dataset.Sequence`` or the reference's).  ``vis`` / ``save_dir`` are accepted; nothing is drawn.
+    ``fused=True`` (KinematicModel only): all novel poses in one launch, ``ik_batch``; the same optimum, not the same bits."""
     from ..networks.model import BaseModel
     from .dataset_utils import sparse_sample_novel_state
 
+    if fused and isinstance(model, BaseModel):
+        raise NotImplementedError("ik(fused=True) fits the angles of a KinematicModel; a BaseModel is retargeted by ik_single "
+                                  "(fused=False)")
     sample = dataset[0]
     cano_pose = dataset.pose_list[dataset.cano_idx]
     cano_pc = torch.from_numpy(sample["cano_pc"]).to(device)
+    if fused:
+        novels = [sparse_sample_novel_state(sample["cano_pc"], sample["gt_cano_part"], cano_pose, novel_pose, 1)
+                  for novel_pose in dataset.novel_pose_list]
+        errs, _ = ik_batch(model, cano_pc, novels, device, **{k: v for k, v in ikargs.items() if k == "n_iter"})
+        if verbose:
+            for err in errs:
+                print(f"Novel retarget err: {err:.3f}")
+        return errs.mean()
     errs = []
     for novel_pose in dataset.novel_pose_list:
         novel = sparse_sample_novel_state(sample["cano_pc"], sample["gt_cano_part"], cano_pose, novel_pose, 1)
         errs.append(ik_single(model, cano_pc, novel, device, verbose=verbose, **ikargs)[0])
     return np.array(errs).mean()
+
+
+def ik_fit(model, src_pc, tgt_pc, n_iter=200, lr=1e-1, theta_init=None, return_loss=False, part=None):
+    """The optimisation loop of ``ik_single`` for M novel poses at once, inside one kernel (reart_ik_fit): the angles
+    ``theta`` [M,E] that carry the sparse canonical points ``src_pc`` [n,3] onto ``tgt_pc`` [M,n,3] (or [n,3]: M = 1), by
+    ``n_iter`` steps of Adam(amsgrad, ``lr``, torch's betas and eps) from ``theta_init`` [M,E] (default 1e-6 everywhere, as
+    the reference starts) on the summed squared distances.  Tensors in, tensors out, on the current stream, no
+    synchronisation: the call can be captured in a graph.  ``return_loss``: also the loss history [M, n_iter + 1] (entry i
+    before step i, the last one at the returned angles).  ``part`` [n]: the labels of ``src_pc`` where the caller has them
+    (default: ``model.seg_forward(src_pc)``, once); the call is then the one kernel.
+    For a KinematicModel of revolute joints without root motion (every model ``run_robot`` produces); ``ik_single`` takes
+    the others.  At most P = 64 parts and n = ``_lib.IK_MAX_POINTS`` points."""
+    if hasattr(model, "distance_list") or model.joint_type_list is not None or hasattr(model, "root_6d"):
+        raise NotImplementedError("ik_fit fits revolute joints without root motion; a model with distance_list, joint types "
+                                  "or root motion is retargeted by ik_single")
+    if tgt_pc.dim() == 2:
+        tgt_pc = tgt_pc[None]
+    n = src_pc.shape[0]
+    assert src_pc.shape == (n, 3) and tgt_pc.shape[1:] == (n, 3), (tuple(src_pc.shape), tuple(tgt_pc.shape))
+    if n > _lib.IK_MAX_POINTS:
+        raise NotImplementedError(f"{n} sparse points: reart_ik_fit takes at most REART_IK_MAX_POINTS = {_lib.IK_MAX_POINTS}")
+    _lib.require_gpu(src_pc, tgt_pc, theta_init, model.axis_list)
+    src, tgt = src_pc.detach().contiguous().float(), tgt_pc.detach().contiguous().float()
+    M, E = tgt.shape[0], model.axis_list.shape[0]
+    if part is None:
+        with torch.no_grad():
+            part = model.seg_forward(src)
+    _lib.require_gpu(part)
+    part = part.contiguous().long()
+    assert part.shape == (n,), tuple(part.shape)
+    axis, moment = model.axis_list.detach().contiguous().float(), model.moment_list.detach().contiguous().float()
+    init = None
+    if theta_init is not None:
+        init = theta_init.detach().contiguous().float()
+        assert init.shape == (M, E), (tuple(init.shape), (M, E))
+    parent, edge_of, order = model._tree(src.device)
+    theta = torch.empty((M, E), dtype=torch.float32, device=src.device)
+    loss = torch.empty((M, n_iter + 1), dtype=torch.float32, device=src.device) if return_loss else None
+    rc = _lib.lib().reart_ik_fit(_lib.ptr(parent), _lib.ptr(edge_of), _lib.ptr(order), parent.shape[0], _lib.ptr(axis),
+                                 _lib.ptr(moment), E, _lib.ptr(src), _lib.ptr(part), n, _lib.ptr(tgt), M, _lib.ptr(init),
+                                 int(n_iter), float(lr), 0.9, 0.999, 1e-8, _lib.ptr(theta), _lib.ptr(loss), _lib.stream())
+    _lib.check(rc, "reart_ik_fit")
+    return (theta, loss) if return_loss else theta
+
+
+def ik_batch(model, cano_pc, novel_samples, device, n_iter=200):
+    """``ik_single`` for a list of novel samples (``sparse_sample_novel_state``) of one canonical cloud in one ``ik_fit``
+    and one forward of all poses -> (retarget errors x100 ndarray [M], theta [M,E]); one device-to-host copy."""
+    src_np = np.asarray(novel_samples[0]["sparse_cano_pc"])
+    for s in novel_samples[1:]:
+        assert np.array_equal(np.asarray(s["sparse_cano_pc"]), src_np), "the novel samples must share their sparse canonical points"
+    src = torch.from_numpy(src_np).float().to(device)
+    tgt = torch.from_numpy(np.stack([np.asarray(s["sparse_novel_pc"]) for s in novel_samples])).float().to(device)
+    gt = torch.from_numpy(np.stack([np.asarray(s["novel_pc"]) for s in novel_samples])).float().to(device)
+    theta = ik_fit(model, src, tgt, n_iter=n_iter)
+    with torch.no_grad():
+        pc_trans, _, _ = model(cano_pc.float(), theta_list=theta)
+        errs = 100 * (pc_trans - gt).pow(2).sum(-1).sqrt().mean(-1)
+    return errs.cpu().numpy().astype(np.float64), theta
 
 
 def ik_single(model, cano_pc, novel_sample, device, n_iter=200, verbose=False, **ikargs):
