@@ -80,6 +80,9 @@ void base_fwd_kernel(Batched<BaseFwdArgs> ab) {
     // temperature and the noise / iteration counter each wait behind the batch before: three to five round trips
     // by the emitted code.  One batch for all of them (clamped per-thread slots) was built and timed: prologue
     // 2.60 -> 2.69 us, workgroup 8.73 -> 8.55 us, not told from the run-to-run spread; dropped
+    // Also built and timed against this form, none told from the run-to-run spread, all dropped: W2 in
+    // 16-byte pieces over all threads (a part pair's four j: two loads, two 16-byte LDS stores) with the pose and W1|b1
+    // tails moved from wave 0 to waves 1-3, and the logits loop below unrolled 4 and 8 deep (6 -> 12 / 24 LDS reads in flight).
     const int nRT = a.B * a.P;
     auto put_rt = [&](int e, const float (&d6)[6], const float (&tv)[3]) {
         float R[9];
@@ -425,13 +428,160 @@ __global__ __launch_bounds__(256) void rt_table_kernel(const float *__restrict__
 #define PHASE_TS_WAVE(which, k, wave) do { } while (0)
 #endif
 
+// Tile staging of the block kernel: global memory -> the LDS tiles, in pieces of V consecutive words of a row: one 16-byte
+// load (V = 4: 16-byte rows, see the call) or one dword load (V = 1: any N, H and any 4-byte-aligned pointer).
+//   * Only the workgroup's own cw = a.cpts columns of the h / G / y tiles are loaded and stored (the tiles keep their
+//     64-point layout).  Who reads a column >= cn of a tile, all of them covered by [0, cw) or by what phase a writes:
+//       s_h   the gW2 tiles (c1) up to cn16; dp (b') at nn < a.cpts, where nn >= cn yields 0 whatever it reads;
+//       s_G   dw (a) and the gR|gt tiles (c2) up to cn16;
+//       s_y   phase b, rows p < P, at its lane's column (a lane >= cn16 reads column 0 instead);
+//       s_ds  phase b likewise: dw is written by phase a up to cn16; gW2 and dp up to cn16;   s_dp  gW1 / gb1 (c3) up to cn16.
+//     A short last chunk loads nothing for the columns cn..cw and stores zeros there.
+//   * Every load of the first batch of every group is issued before the first LDS store, G (written by the previous
+//     kernel on other XCDs) first; no load is a clamped repeat: a piece outside its tile is not loaded at all.
+//   * The groups are dealt to different threads (G from thread 0 up, W2 from thread 384 up, y from the last thread down),
+//     W2 over P * H / V threads with the part running fastest: conflict-free LDS stores, no 20-deep chain on two waves.
+//   * FAST: the template's shape (P = PP, H = 128, B = 19, 32 points, full chunk) with every count a constant, so a group
+//     is one range test of the thread index.  Emitted code of that path, <20, false>: eight 16-byte loads plus wave 0's
+//     point (one 12-byte, one dword load) before the first wait, five exec-mask blocks in the store section (one per group
+//     that does not cover all threads), about 250 instructions (145 VALU) from the path's entry to the barrier -- against
+//     about 50 dword loads, 45 blocks and 1 560 instructions (840 VALU) of the clamped 64-column form before.
+template <int V> struct BwPiece { float v[V]; };
+template <int V> __device__ __forceinline__ BwPiece<V> bw_load(const float *p) {
+    BwPiece<V> r;
+    if constexpr (V == 4) {
+        const float4 q = *(const float4 *)p;
+        r.v[0] = q.x; r.v[1] = q.y; r.v[2] = q.z; r.v[3] = q.w;
+    } else {
+        r.v[0] = *p;
+    }
+    return r;
+}
+template <int PP, int V, bool FAST, class LoadPoint>
+__device__ __forceinline__ void bwd_stage_tiles(const BaseBwdArgs &a, int n0, int cn, float *s_h, float *s_G, float *s_w2T,
+                                                float *s_rt, float *s_y, LoadPoint load_point) {
+    typedef BwPiece<V> Pc;
+    constexpr int PMAX = (PP > 0) ? PP : 32, BS = 64 * BW_WAVES;
+    const int P = (PP > 0) ? PP : a.P;
+    const int H = FAST ? 128 : a.H, B = FAST ? 19 : a.B, cw = FAST ? 32 : a.cpts;
+    const int rsh = (cw == 64 ? 6 : (cw == 32 ? 5 : 4)) - (V == 4 ? 2 : 0);   // log2 of the pieces per tile row
+    const int rp = 1 << rsh, gpc = 3 * rp;                                       // pieces per row of h / y, per frame of G
+    const int nH = H << rsh, nY = P << rsh, nG = B * gpc, nR = B * P * 12 / V, nW = P * (H / V);
+    // first batch of every group: H = 128, B = 19, P = 20 at 64 points fit (FAST: at 32 points, exactly)
+    constexpr int UH = FAST ? 1 : 128 * RED_CHUNK / V / BS, UG = FAST ? 1 : (19 * RED_CHUNK * 3 / V + BS - 1) / BS,
+                  UY = FAST ? 1 : (PMAX * RED_CHUNK / V + BS - 1) / BS, UR = (19 * 20 * 12 / V + BS - 1) / BS,
+                  UW = FAST ? 1 : (PMAX * 128 / V + BS - 1) / BS;
+    const int tid = threadIdx.x, tw = (tid + BS - 384) & (BS - 1), ty = BS - 1 - tid;
+    const bool flow = a.gpf != nullptr;   // uniform
+    // upstream gradient tile; the fused step adds the flow-loss terms of the two adjacent pairs
+    // (complete frame fc = t or t + 1: + d/d pred_flow of pair fc - 1, - d/d pred_flow of pair fc)
+    auto load_g = [&](int e, Pc &g, Pc &gh, Pc &gl) {
+        const int t = (e >> rsh) / 3, r = (e - t * gpc) * V;
+        if (e < nG && (FAST || r < 3 * cn)) {   // a piece that is not loaded stays unset: its store tests the same conditions
+            g = bw_load<V>(a.G + 3 * ((size_t)t * a.N + n0) + r);
+            if (flow) {
+                const int fc = t < a.cano_idx ? t : t + 1;   // complete-sequence index of frame t
+                const int fh = fc - 1 >= 0 ? fc - 1 : 0, fl = fc <= B - 1 ? fc : B - 1;
+                gh = bw_load<V>(a.gpf + 3 * ((size_t)fh * a.N + n0) + r);
+                gl = bw_load<V>(a.gpf + 3 * ((size_t)fl * a.N + n0) + r);
+            }
+        }
+    };
+    auto store_g = [&](int e, const Pc &g, const Pc &gh, const Pc &gl) {
+        if (e < nG) {
+            const int t = (e >> rsh) / 3, r = (e - t * gpc) * V;
+            const int fc = t < a.cano_idx ? t : t + 1;
+            const bool ah = flow && fc - 1 >= 0, al = flow && fc <= B - 1, in = FAST || r < 3 * cn;
+#pragma unroll
+            for (int k = 0; k < V; ++k) {
+                float v = in ? g.v[k] : 0.f;
+                if (in && ah) v += gh.v[k];       // operation order: (G + gh) - gl
+                if (in && al) v -= gl.v[k];
+                s_G[t * (RED_CHUNK * 3) + r + k] = v;
+            }
+        }
+    };
+    // a [rows][N] matrix -> a [rows][BW_LD] tile (hT, yT)
+    auto load_t = [&](const float *src, int e, int n) {
+        Pc v;
+        const int j = e >> rsh, i = (e & (rp - 1)) * V;
+        if (e < n && (FAST || i < cn)) v = bw_load<V>(src + (size_t)j * a.N + n0 + i);
+        return v;
+    };
+    auto store_t = [&](float *dst, int e, int n, const Pc &v) {
+        if (e < n) {
+            const int j = e >> rsh, i = (e & (rp - 1)) * V;
+#pragma unroll
+            for (int k = 0; k < V; ++k) dst[j * BW_LD + i + k] = (FAST || i < cn) ? v.v[k] : 0.f;
+        }
+    };
+    auto load_r = [&](int e) {
+        Pc v;
+        if (e < nR) v = bw_load<V>(a.rt_table + V * (size_t)e);
+        return v;
+    };
+    auto store_r = [&](int e, const Pc &v) {
+        if (e < nR) {
+#pragma unroll
+            for (int k = 0; k < V; ++k) s_rt[V * e + k] = v.v[k];
+        }
+    };
+    // W2 [P][H] -> s_w2T [H][PMAX]: piece e = (j / V, p), the part running fastest
+    auto load_w = [&](int e) {
+        Pc v;
+        const int jq = (unsigned)e / (unsigned)P, p = e - jq * P;
+        if (e < nW) v = bw_load<V>(a.W2 + (size_t)p * H + V * jq);
+        return v;
+    };
+    auto store_w = [&](int e, const Pc &v) {
+        if (e < nW) {
+            const int jq = (unsigned)e / (unsigned)P, p = e - jq * P;
+#pragma unroll
+            for (int k = 0; k < V; ++k) s_w2T[(V * jq + k) * PMAX + p] = v.v[k];
+        }
+    };
+    Pc vg[UG], vgh[UG], vgl[UG], vh[UH], vr[UR], vw[UW], vy[UY];
+#pragma unroll
+    for (int u = 0; u < UG; ++u) load_g(tid + u * BS, vg[u], vgh[u], vgl[u]);
+#pragma unroll
+    for (int u = 0; u < UH; ++u) vh[u] = load_t(a.hT, tid + u * BS, nH);
+#pragma unroll
+    for (int u = 0; u < UR; ++u) vr[u] = load_r(tid + u * BS);
+#pragma unroll
+    for (int u = 0; u < UW; ++u) vw[u] = load_w(tw + u * BS);
+#pragma unroll
+    for (int u = 0; u < UY; ++u) vy[u] = load_t(a.yT, ty + u * BS, nY);
+    load_point();
+    PHASE_TS(1, 9);
+#ifdef REART_PHASE_CLOCK
+    __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): the stamp behind it is "loads returned" (diagnostic build only)
+#endif
+    PHASE_TS(1, 10);
+#pragma unroll
+    for (int u = 0; u < UG; ++u) store_g(tid + u * BS, vg[u], vgh[u], vgl[u]);
+#pragma unroll
+    for (int u = 0; u < UH; ++u) store_t(s_h, tid + u * BS, nH, vh[u]);
+#pragma unroll
+    for (int u = 0; u < UR; ++u) store_r(tid + u * BS, vr[u]);
+#pragma unroll
+    for (int u = 0; u < UW; ++u) store_w(tw + u * BS, vw[u]);
+#pragma unroll
+    for (int u = 0; u < UY; ++u) store_t(s_y, ty + u * BS, nY, vy[u]);
+    if (!FAST) {   // what a larger shape has beyond the first batches
+        for (int e = tid + UG * BS; e < nG; e += BS) { load_g(e, vg[0], vgh[0], vgl[0]); store_g(e, vg[0], vgh[0], vgl[0]); }
+        for (int e = tid + UH * BS; e < nH; e += BS) store_t(s_h, e, nH, load_t(a.hT, e, nH));
+        for (int e = tid + UR * BS; e < nR; e += BS) store_r(e, load_r(e));
+        for (int e = tw + UW * BS; e < nW; e += BS) store_w(e, load_w(e));
+        for (int e = ty + UY * BS; e < nY; e += BS) store_t(s_y, e, nY, load_t(a.yT, e, nY));
+    }
+}
+
 template <int PP, bool BATCH>
 __global__ __launch_bounds__(64 * BW_WAVES) void base_bwd_block_kernel(Batched<BaseBwdArgs> ab) {
     const BaseBwdArgs &a = ab.a[BATCH ? blockIdx.y : 0];
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int PMAX = (PP > 0) ? PP : 32;
     constexpr int W = BW_WAVES;
-    constexpr int BS = 64 * W;
     static_assert(2 * W >= PMAX, "phase b: one wave per part pair");
     const int P = (PP > 0) ? PP : a.P;
     float *s_h = smem;                               // [H][BW_LD]  hT tile (a.dp_sep == 0: later the dp tile)
@@ -446,120 +596,41 @@ __global__ __launch_bounds__(64 * BW_WAVES) void base_bwd_block_kernel(Batched<B
     const int dp_ld = a.dp_sep ? a.cpts + 1 : BW_LD;
     float *s_dp = a.dp_sep ? s_y + (size_t)PMAX * BW_LD : s_h;   // [H][dp_ld]  hidden gradient
     const int tid = threadIdx.x, lane = tid & 63, grp = tid >> 6, chunk = blockIdx.x;
-    // a workgroup owns a.cpts (64, 32 or 16) points; the tiles keep their 64-point layout (columns >= cn are zero), the
-    // matrix-core loops stop at cn: with 32 points twice as many workgroups each run half the reductions
+    // a workgroup owns a.cpts (64, 32 or 16) points; the tiles keep their 64-point layout (columns cn..a.cpts are zero, those
+    // beyond are never written nor read), the matrix-core loops stop at cn16: with 32 points twice as many workgroups each run
+    // half the reductions
     const int n0 = chunk * a.cpts;
     const int cn = (a.N - n0) < a.cpts ? (a.N - n0) : a.cpts;
     const int cn16 = (cn + 15) & ~15;   // tile columns beyond cn are zero: whole blocks of 16 points keep the loops unrolled
     float *prow = a.partial + (size_t)chunk * n_out(a.P, a.H, a.B);
     PHASE_TS(1, 0);
 
-    // Tile loads.  Every group issues a batch of unconditional loads (clamped addresses, masked
-    // afterwards), and the first batch of EVERY group is in flight before anything is stored to LDS:
-    // written as plain guarded loops the compiler serialises the loads and the prologue becomes a
-    // chain of a dozen L2 / HBM round trips (measured 25 k cycles, now one round trip deep).  The yT tile and
-    // hard_idx are part of that batch: y_k and phase b's y[p] are LDS reads, no second global round trip.
-    constexpr int UH = (128 * RED_CHUNK + BS - 1) / BS, UG = (19 * RED_CHUNK * 3 + BS - 1) / BS,
-                  UR = (19 * 20 * 12 + BS - 1) / BS, UY = (PMAX * RED_CHUNK + BS - 1) / BS;   // H = 128, B = 19, P = 20: one batch each
-    const int ilast = cn - 1, nH = a.H * RED_CHUNK, nG = a.B * RED_CHUNK * 3, rlast = 3 * cn - 1, nR = a.B * a.P * 12;
+    // Tile loads: bwd_stage_tiles above (one batch of loads, then the stores).  The 16-byte form needs 16-byte rows: N and H
+    // multiples of 4 and every base pointer 16-byte aligned (chosen here, uniformly); anything else takes the dword form.
+    // The point coordinates and hard_idx (wave 0, one point per lane) ride in the same batch.
     const bool live = lane < cn;
     const int n = live ? n0 + lane : n0;
-    auto load_h = [&](int e0, float (&v)[UH]) {
-#pragma unroll
-        for (int u = 0; u < UH; ++u) {
-            const int e = e0 + u * BS;
-            const int ec = e < nH ? e : lane;
-            const int j = ec >> 6, i = ec & 63;            // RED_CHUNK == 64
-            v[u] = a.hT[(size_t)j * a.N + n0 + (i < cn ? i : ilast)];
-        }
-    };
-    auto store_h = [&](int e0, const float (&v)[UH]) {
-#pragma unroll
-        for (int u = 0; u < UH; ++u) {
-            const int e = e0 + u * BS;
-            if (e < nH) s_h[(e >> 6) * BW_LD + (e & 63)] = ((e & 63) < cn) ? v[u] : 0.f;
-        }
-    };
-    // upstream gradient tile; the fused step adds the flow-loss terms of the two adjacent pairs
-    // (complete frame fc = t or t + 1: + d/d pred_flow of pair fc - 1, - d/d pred_flow of pair fc)
-    auto load_g = [&](int e0, float (&g)[UG], float (&gh)[UG], float (&gl)[UG]) {
-#pragma unroll
-        for (int u = 0; u < UG; ++u) {
-            const int e = e0 + u * BS;
-            const int ec = e < nG ? e : lane;
-            const int t = ec / (RED_CHUNK * 3), r0_ = ec - t * (RED_CHUNK * 3);
-            const int r = r0_ < 3 * cn ? r0_ : rlast;
-            g[u] = a.G[3 * ((size_t)t * a.N + n0) + r];
-            gh[u] = 0.f; gl[u] = 0.f;
-            if (a.gpf) {   // uniform
-                const int fc = t < a.cano_idx ? t : t + 1;   // complete-sequence index of frame t
-                const int fh = fc - 1 >= 0 ? fc - 1 : 0, fl = fc <= a.B - 1 ? fc : a.B - 1;
-                gh[u] = a.gpf[3 * ((size_t)fh * a.N + n0) + r];
-                gl[u] = a.gpf[3 * ((size_t)fl * a.N + n0) + r];
-            }
-        }
-    };
-    auto store_g = [&](int e0, const float (&g)[UG], const float (&gh)[UG], const float (&gl)[UG]) {
-#pragma unroll
-        for (int u = 0; u < UG; ++u) {
-            const int e = e0 + u * BS;
-            if (e < nG) {
-                const int t = e / (RED_CHUNK * 3), r0_ = e - t * (RED_CHUNK * 3);
-                float v = g[u];
-                if (a.gpf) {
-                    const int fc = t < a.cano_idx ? t : t + 1;
-                    if (fc - 1 >= 0) v += gh[u];       // operation order: (G + gh) - gl
-                    if (fc <= a.B - 1) v -= gl[u];
-                }
-                s_G[e] = r0_ < 3 * cn ? v : 0.f;
-            }
-        }
-    };
-    auto load_r = [&](int e0, float (&v)[UR]) {
-#pragma unroll
-        for (int u = 0; u < UR; ++u) v[u] = a.rt_table[e0 + u * BS < nR ? e0 + u * BS : 0];
-    };
-    auto store_r = [&](int e0, const float (&v)[UR]) {
-#pragma unroll
-        for (int u = 0; u < UR; ++u)
-            if (e0 + u * BS < nR) s_rt[e0 + u * BS] = v[u];
-    };
-    float vh[UH], vg[UG], vgh[UG], vgl[UG], vr[UR], vw[PMAX], vy[UY];
-    load_g(tid, vg, vgh, vgl);     // produced by the previous kernels on other XCDs: the longest latency first
-    load_h(tid, vh);
-    load_r(tid, vr);
-    const int jw = tid < a.H ? tid : 0;
-#pragma unroll
-    for (int p = 0; p < PMAX; ++p) vw[p] = a.W2[(size_t)(p < P ? p : 0) * a.H + jw];
-#pragma unroll
-    for (int u = 0; u < UY; ++u) {   // rows >= P and columns >= cn repeat real entries: finite, never part of a result
-        const int e = tid + u * BS, p = e >> 6, i = e & 63;
-        vy[u] = a.yT[(size_t)(p < P ? p : 0) * a.N + n0 + (i < cn ? i : ilast)];
-    }
-    const float x0 = a.cano[3 * (size_t)n], x1 = a.cano[3 * (size_t)n + 1], x2 = a.cano[3 * (size_t)n + 2];
+    const bool vec = ((a.N | a.H) & 3) == 0 &&
+                     (((uintptr_t)a.hT | (uintptr_t)a.yT | (uintptr_t)a.G | (uintptr_t)a.gpf | (uintptr_t)a.rt_table | (uintptr_t)a.W2) & 15) == 0;
+    float x0 = 0.f, x1 = 0.f, x2 = 0.f;
     int kn = -1;
-    if (grp == 0) kn = live ? a.hard_idx[n] : -1;
-    store_g(tid, vg, vgh, vgl);
-    store_h(tid, vh);
-    store_r(tid, vr);
-    if (tid < a.H) {
-#pragma unroll
-        for (int p = 0; p < PMAX; ++p) s_w2T[tid * PMAX + p] = vw[p];
-    }
-#pragma unroll
-    for (int u = 0; u < UY; ++u) {
-        const int e = tid + u * BS;
-        if (e < PMAX * RED_CHUNK) s_y[(e >> 6) * BW_LD + (e & 63)] = vy[u];
-    }
-    for (int e0 = tid + UG * BS; e0 < nG; e0 += UG * BS) { load_g(e0, vg, vgh, vgl); store_g(e0, vg, vgh, vgl); }
-    for (int e0 = tid + UH * BS; e0 < nH; e0 += UH * BS) { load_h(e0, vh); store_h(e0, vh); }
-    for (int e0 = tid + UR * BS; e0 < nR; e0 += UR * BS) { load_r(e0, vr); store_r(e0, vr); }
-    for (int j = tid + BS; j < a.H; j += BS)
-        for (int p = 0; p < P; ++p) s_w2T[j * PMAX + p] = a.W2[(size_t)p * a.H + j];
+    auto load_point = [&]() {
+        if (grp == 0) {
+            x0 = a.cano[3 * (size_t)n]; x1 = a.cano[3 * (size_t)n + 1]; x2 = a.cano[3 * (size_t)n + 2];
+            kn = live ? a.hard_idx[n] : -1;
+        }
+    };
+    if (PP == 20 && vec && a.H == 128 && a.B == 19 && a.cpts == 32 && cn == 32)
+        bwd_stage_tiles<PP, 4, true>(a, n0, cn, s_h, s_G, s_w2T, s_rt, s_y, load_point);
+    else if (vec)
+        bwd_stage_tiles<PP, 4, false>(a, n0, cn, s_h, s_G, s_w2T, s_rt, s_y, load_point);
+    else
+        bwd_stage_tiles<PP, 1, false>(a, n0, cn, s_h, s_G, s_w2T, s_rt, s_y, load_point);
     if (grp == 0) {
         s_x[3 * lane] = live ? x0 : 0.f; s_x[3 * lane + 1] = live ? x1 : 0.f; s_x[3 * lane + 2] = live ? x2 : 0.f;
         s_kn[lane] = kn;
     }
+    PHASE_TS(1, 11);
     // a. dw[n,p] = sum_t G[t,n] . (R[t,p] x_n + t[t,p]) as ONE matrix product on the matrix cores:
     //      dw = A Bm,   A[n][(t,r,c)] = G[t,n,r] * (c < 3 ? x_n[c] : 1),   Bm[(t,r,c)][p] = [R|t][t,p][r][c]
     //    (K = 12 B, ascending (t, r, c): a fixed summation order, deterministic).  v_mfma_f32_16x16x4_f32:
@@ -613,21 +684,22 @@ __global__ __launch_bounds__(64 * BW_WAVES) void base_bwd_block_kernel(Batched<B
     __syncthreads();
     PHASE_TS(1, 2);
     // b. softmax backward: dot over all parts in ascending order, ds for this wave's parts
+    const int bl = lane < cn16 ? lane : 0;   // a lane beyond the tile's written columns reads column 0: its results are dropped (live)
     if (grp == 0) {
-        const float yk = s_y[(kn < 0 ? 0 : kn) * BW_LD + lane];
+        const float yk = s_y[(kn < 0 ? 0 : kn) * BW_LD + bl];
         s_w[lane] = (1.0f - yk) + yk;
     }
     float ds0 = 0.f, ds1 = 0.f;
     if (has0) {
-        const float dw0 = s_ds[p0 * BW_LD + lane];
-        const float dw1 = has1 ? s_ds[(p0 + 1) * BW_LD + lane] : 0.f;
+        const float dw0 = s_ds[p0 * BW_LD + bl];
+        const float dw1 = has1 ? s_ds[(p0 + 1) * BW_LD + bl] : 0.f;
         const float tau = a.tau_ptr ? a.tau_ptr[0] : a.tau;
         float dot = 0.f;
 #pragma unroll
         for (int p = 0; p < PMAX; ++p)
-            if (PP > 0 || p < P) dot = fmaf(s_y[p * BW_LD + lane], s_ds[p * BW_LD + lane], dot);
-        ds0 = (s_y[p0 * BW_LD + lane] * (dw0 - dot)) / tau;
-        if (has1) ds1 = (s_y[(p0 + 1) * BW_LD + lane] * (dw1 - dot)) / tau;
+            if (PP > 0 || p < P) dot = fmaf(s_y[p * BW_LD + bl], s_ds[p * BW_LD + bl], dot);
+        ds0 = (s_y[p0 * BW_LD + bl] * (dw0 - dot)) / tau;
+        if (has1) ds1 = (s_y[(p0 + 1) * BW_LD + bl] * (dw1 - dot)) / tau;
     }
     __syncthreads();  // every wave has read dw before it is overwritten by ds
     if (has0) s_ds[p0 * BW_LD + lane] = live ? ds0 : 0.f;

@@ -29,6 +29,12 @@ for rep in range(3):
             print(f"bwd_block (us): tile loads {us(0, 1):.2f} | a. dw {us(1, 2):.2f} | b. ds {us(2, 3):.2f} | roles side by side from stamp 3: "
                   f"gR|gt tile ends +{us(3, 4):.2f}, gW2 tile ends +{us(3, 5):.2f}, dp ends +{us(3, 6):.2f}, gW1/gb1 end +{us(3, 7):.2f}, "
                   f"all waves done +{us(3, 8):.2f} | total {us(0, 8):.2f} us: the lifetime of ONE workgroup (block 1)")
+            if v[16 + 9] and v[16 + 11]:
+                # inside "tile loads" (thread 0): 9 all loads issued, 10 loads returned (the diagnostic build waits there), 11 LDS stores issued
+                pt = v[16:32]
+                d = lambda k0, k1: (pt[k1] - pt[k0]) * TICK_US
+                print(f"bwd_block tile loads (us): loads issued {d(0, 9):.2f} | loads returned {d(9, 10):.2f} | stores done {d(10, 11):.2f} | "
+                      f"barrier {d(11, 1):.2f}")
             continue
         print(name, "deltas (s_memtime ticks):", [ts[i + 1] - ts[i] for i in range(n - 1)], "total", ts[n - 1] - ts[0],
               f"= {(ts[n - 1] - ts[0]) * TICK_US:.2f} us: the lifetime of ONE workgroup (block 1)")
