@@ -651,6 +651,22 @@ int reart_lap_auction_race_warm(const float *cost, const float *src, const float
                                 const int32_t *col4row_in, const double *price_in, int32_t *col4row, int32_t *certified,
                                 double *price_out, void *workspace, size_t workspace_bytes, void *stream);
 
+/* The cold solve for matrices of up to 8192 columns: the same epsilon-scaling auction, augmenting searches and fp64
+ * certificate as reart_lap_auction, in an instance of its kernel that keeps prices, owners and the assignment in LDS (16 B per
+ * column) and the bids of a round in the workspace.  One workgroup per matrix, not raced: the result is a function of the
+ * matrix.  Accepts every 1 <= n <= REART_LAP_LARGE_MAX_N (the Python wrapper sends it n > 4096 only; below, the entries
+ * above are faster).  src / tgt: both NULL, or both given with cost == reart_cdist(src, tgt) -- accepted so that a caller
+ * passes the same arguments at every size; this form reads its rows from the matrix throughout.  price_out [B,n] f64
+ * (required) receives the potentials.  The certificate takes at most 256 rounds (each a pass of one compute unit over the
+ * matrix); a matrix that needs more comes back with certified[b] = 0, for the host solver like any other uncertified one.
+ * workspace: reart_lap_large_workspace_bytes (0 unless B >= 0 and 1 <= n <= REART_LAP_LARGE_MAX_N); diagnostics [B][4]
+ * (phases, rounds, bids, certificate rounds) at the same offset as in reart_lap_workspace_bytes' layout. */
+#define REART_LAP_LARGE_MAX_N 8192
+size_t reart_lap_large_workspace_bytes(int B, int n);
+int reart_lap_auction_large(const float *cost, const float *src, const float *tgt, int B, int n,
+                            int32_t *col4row, int32_t *certified, double *price_out,
+                            void *workspace, size_t workspace_bytes, void *stream);
+
 /* The same solve warm-started from an earlier solve of a similar batch (the loop re-solves every assign_gap
  * iterations): on entry col4row holds that solve's assignment and price_in (required) its potentials; pairs that are
  * still epsilon-tight under the new costs are kept.  Certified like a cold solve.  Use when the costs move smoothly

@@ -20,6 +20,7 @@
 #include "internal.h"
 #include "lap_dev.h"
 #include <math.h>
+#include <type_traits>
 
 #define LAP_BS 1024
 // lap_auction_kernel: from phase LAP_SEARCH_PHASE on, the last LAP_SEARCH_NU free rows of a phase get one augmenting-path
@@ -74,6 +75,7 @@ __constant__ double c_lap_race_warm[LAP_RACE_WARM][3] = {{1e-2, 6.0, 2.0}, {1e-3
 // smallest (value, column) and second smallest value of row i under prices p over the columns [jb, je); all lanes
 // get the result (an empty range gives +inf).  Exact selections only, so any split of a row into ranges followed by
 // lap_merge_top2 gives the same triple as one scan of the whole row.
+template <int U = 8>
 __device__ __forceinline__ void lap_row_top2_range(const float *__restrict__ row, const double *__restrict__ p, int jb, int je,
                                                    int lane, double &v1, int &j1, double &v2) {
     v1 = INFINITY; v2 = INFINITY; j1 = 0x7fffffff;
@@ -81,12 +83,12 @@ __device__ __forceinline__ void lap_row_top2_range(const float *__restrict__ row
         // 16-byte loads, up to 8 per lane in flight (2048 columns per pass): the scan is a dependent global read and
         // its latency, not its bandwidth, is what a bid costs.  Each lane still meets its columns in ascending order.
         const int je4 = jb + ((je - jb) & ~3);
-        for (int j0 = jb + 4 * lane; j0 < je4; j0 += 256 * 8) {
-            float4 r[8];
+        for (int j0 = jb + 4 * lane; j0 < je4; j0 += 256 * U) {
+            float4 r[U];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) r[u] = *(const float4 *)(row + (j0 + 256 * u < je4 ? j0 + 256 * u : jb));
+            for (int u = 0; u < U; ++u) r[u] = *(const float4 *)(row + (j0 + 256 * u < je4 ? j0 + 256 * u : jb));
 #pragma unroll
-            for (int u = 0; u < 8; ++u) {
+            for (int u = 0; u < U; ++u) {
                 const int j = j0 + 256 * u;
                 if (j < je4) {
                     const float rr[4] = {r[u].x, r[u].y, r[u].z, r[u].w};
@@ -99,12 +101,12 @@ __device__ __forceinline__ void lap_row_top2_range(const float *__restrict__ row
         }
         jb = je4;     // a tail of at most three columns follows
     }
-    for (int j0 = jb + lane; j0 < je; j0 += 64 * 8) {
-        float r[8];
+    for (int j0 = jb + lane; j0 < je; j0 += 64 * U) {
+        float r[U];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) r[u] = row[j0 + 64 * u < je ? j0 + 64 * u : jb];
+        for (int u = 0; u < U; ++u) r[u] = row[j0 + 64 * u < je ? j0 + 64 * u : jb];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) {
+        for (int u = 0; u < U; ++u) {
             const int j = j0 + 64 * u;
             if (j < je) {
                 lap_top2_push((double)r[u] + p[j], j, v1, j1, v2);
@@ -117,17 +119,18 @@ __device__ __forceinline__ void lap_row_top2_range(const float *__restrict__ row
 
 // the row's minimum of c_ik + p_k alone (the certificate needs nothing else): a third of the instructions of the
 // (min, arg-min, second-min) scan, which bound the one-workgroup pass (10 VALU instructions per element)
+template <int U = 8>
 __device__ __forceinline__ double lap_row_min(const float *__restrict__ row, const double *__restrict__ p, int n, int lane) {
     double m = INFINITY;
     int jb = 0;
     if ((((uintptr_t)row) & 15) == 0) {
         const int n4 = n & ~3;
-        for (int j0 = 4 * lane; j0 < n4; j0 += 256 * 8) {
-            float4 r[8];
+        for (int j0 = 4 * lane; j0 < n4; j0 += 256 * U) {
+            float4 r[U];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) r[u] = *(const float4 *)(row + (j0 + 256 * u < n4 ? j0 + 256 * u : 0));
+            for (int u = 0; u < U; ++u) r[u] = *(const float4 *)(row + (j0 + 256 * u < n4 ? j0 + 256 * u : 0));
 #pragma unroll
-            for (int u = 0; u < 8; ++u) {
+            for (int u = 0; u < U; ++u) {
                 const int j = j0 + 256 * u;
                 if (j < n4) {
                     m = fmin(m, fmin(fmin((double)r[u].x + p[j], (double)r[u].y + p[j + 1]),
@@ -141,9 +144,10 @@ __device__ __forceinline__ double lap_row_min(const float *__restrict__ row, con
     return lap_wave_min_d(m);
 }
 
+template <int U = 8>
 __device__ __forceinline__ void lap_row_top2(const float *__restrict__ row, const double *__restrict__ p, int n, int lane,
                                              double &v1, int &j1, double &v2) {
-    lap_row_top2_range(row, p, 0, n, lane, v1, j1, v2);
+    lap_row_top2_range<U>(row, p, 0, n, lane, v1, j1, v2);
 }
 
 __device__ __forceinline__ void lap_merge_top2(double ov1, int oj1, double ov2, double &v1, int &j1, double &v2) {
@@ -216,18 +220,43 @@ extern "C" int reart_debug_auction_trace(int *out) {
 #define JPH_HIST(steps_) do { } while (0)
 #endif
 
+// what another thread of the workgroup wrote to a bid array, possibly with an atomic: an LDS word as it is; a word of the
+// workspace (the large instance) by a device-scope load, which is served where the atomics are performed
+template <bool GLOBAL, typename T>
+__device__ __forceinline__ T lap_bid_load(const T *p) {
+    if constexpr (GLOBAL) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else return *p;
+}
+
+// CAP = LAP_NMAX: up to 4096 columns, the whole state of a matrix in LDS (the rows' bids in the workspace above LAP_NLDS).
+// CAP = REART_LAP_LARGE_MAX_N (reart_lap_auction_large): up to 8192 columns.  LDS keeps what every row scan and every link of
+// a chain reads -- prices, owners, assignment: 16 B per column --; the arrays a bidding ROUND touches once per bidder or column
+// (bids, winners, the bidder list) live in the workspace, where the bids meet through the same integer atomics; a thread
+// holds twice the columns of a path search; unraced and cold only (no `done`, no price_in), and the single-bidder chains
+// always read their rows from the matrix.
+template <int CAP>
 __global__ __launch_bounds__(LAP_BS) void lap_auction_kernel(LapArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lsm[];
-    const int n = a.n, b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    constexpr bool LARGE = CAP > LAP_NMAX;
+    const int n = a.n, b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    // (the large instance: the wave's number, and with it the rows' addresses of its scans, in scalar registers)
+    const int wv = LARGE ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
     constexpr int NW = LAP_BS / 64;
+    constexpr int RU = LARGE ? 4 : 8;           // 16-byte loads a lane keeps in flight in a row scan (eight: 28 B of scratch in the large instance)
     double *price = (double *)lsm;                                  // [n] column prices
-    unsigned long long *bidval = (unsigned long long *)(price + n); // [n] highest bid (ordered key)
-    const bool bids_in_lds = n <= LAP_NLDS;
-    const int racer = blockIdx.y;                                   // 0 unless this is a race
+    unsigned long long *bidval;                                     // [n] highest bid (ordered key)
+    if constexpr (LARGE) bidval = (unsigned long long *)(a.pbval_ws + (size_t)a.B * n) + (size_t)b * n;
+    else bidval = (unsigned long long *)(price + n);
+    const bool bids_in_lds = !LARGE && n <= LAP_NLDS;
+    const int racer = LARGE ? 0 : blockIdx.y;                       // 0 unless this is a race
     double *pbval = bids_in_lds ? (double *)(bidval + n) : a.pbval_ws + ((size_t)racer * a.B + b) * n;   // [n] row's bid
-    int *owner = (int *)(bidval + n + (bids_in_lds ? n : 0));       // [n] column -> row
+    int *owner;                                                     // [n] column -> row
+    if constexpr (LARGE) owner = (int *)(price + n);
+    else owner = (int *)(bidval + n + (bids_in_lds ? n : 0));
     int *assigned = owner + n;                                      // [n] row -> column
-    int *bidder = assigned + n;                                     // [n] winning row of the round
+    int *bidder;                                                    // [n] winning row of the round
+    if constexpr (LARGE) bidder = (int *)(a.pbval_ws + 2 * (size_t)a.B * n) + 3 * (size_t)b * n;
+    else bidder = assigned + n;
     int *pbobj = bidder + n;                                        // [n] row's bid column
     int *ulist = pbobj + n;                                         // [n] unassigned rows
     __shared__ int s_cnt, s_flag, s_next, s_abort;
@@ -241,8 +270,8 @@ __global__ __launch_bounds__(LAP_BS) void lap_auction_kernel(LapArgs a) {
     const float *C = a.cost + (size_t)b * n * n;
     JPH_DECL;
     // a race is over for this workgroup once another racer has published the matrix (device-scope atomic load: the flag lives in L2)
-    auto lost = [&]() -> int { return a.done ? __hip_atomic_load(a.done + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0; };
-    const bool race = a.done != nullptr && gridDim.y > 1;
+    auto lost = [&]() -> int { return !LARGE && a.done ? __hip_atomic_load(a.done + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0; };
+    const bool race = !LARGE && a.done != nullptr && gridDim.y > 1;
     if (tid == 0) { s_abort = 0; s_abp[0] = 0; s_abp[1] = 0; }
 
     // largest cost
@@ -252,7 +281,7 @@ __global__ __launch_bounds__(LAP_BS) void lap_auction_kernel(LapArgs a) {
     if (lane == 0) s_red[wv] = mx;
     // warm start: potentials of an earlier problem, shifted to be non-negative (bids are ordered as unsigned keys)
     const int warm_slot = (int)blockIdx.y - ((int)gridDim.y - a.warm_racers);          // >= 0: this racer starts warm
-    const int warm_mode = a.done ? (warm_slot >= 0 ? (int)c_lap_race_warm[warm_slot][2] : 0) : (a.price_in ? (a.warm_assign ? 2 : 1) : 0);
+    const int warm_mode = LARGE ? 0 : a.done ? (warm_slot >= 0 ? (int)c_lap_race_warm[warm_slot][2] : 0) : (a.price_in ? (a.warm_assign ? 2 : 1) : 0);
     const double *price_in = warm_mode ? a.price_in : nullptr;
     double pmin = 0.0;
     if (price_in) {
@@ -303,13 +332,17 @@ __global__ __launch_bounds__(LAP_BS) void lap_auction_kernel(LapArgs a) {
     // afterwards (each row's new column is its exact arg-min), which is all the next phase and the certificate rely on.
     // Thread t holds the labels of the columns t, t + 1024, ... in registers; a step is one coalesced row read and one
     // workgroup arg-min (the same loop as lap_jv_kernel's, with the eps offset).
-    constexpr int CPT = LAP_NMAX / LAP_BS;
+    constexpr int CPT = CAP / LAP_BS;
     __shared__ double s_rv[2][NW];
     __shared__ int s_rj[2][NW];
     __shared__ double s_cv1[2][NW], s_cv2[2][NW];
     __shared__ int s_cj1[2][NW], s_ci0[2][NW];
     auto eps_search = [&](int i0, double eps) -> int {
-        int *pred = pbobj;                       // a row's bid column: only live inside a bidding round
+        // a row's bid column: only live inside a bidding round.  (The large instance: 16-bit rows in LDS behind the assignment.)
+        using pred_t = typename std::conditional<LARGE, unsigned short, int>::type;
+        pred_t *pred;
+        if constexpr (LARGE) pred = (pred_t *)(assigned + n);
+        else pred = pbobj;
         double d[CPT];
         unsigned scanned = 0u, freecol = 0u;
         {
@@ -400,7 +433,7 @@ __global__ __launch_bounds__(LAP_BS) void lap_auction_kernel(LapArgs a) {
             for (int i = wv; i < n; i += NW) {
                 double v1, v2;
                 int j1;
-                lap_row_top2(C + (size_t)i * n, price, n, lane, v1, j1, v2);
+                lap_row_top2<RU>(C + (size_t)i * n, price, n, lane, v1, j1, v2);
                 if (lane == 0) {
                     const int j = assigned[i];
                     if (j < 0 || (double)C[(size_t)i * n + j] + price[j] > v1 + eps) {
@@ -460,7 +493,7 @@ __global__ __launch_bounds__(LAP_BS) void lap_auction_kernel(LapArgs a) {
                 // of a phase is mostly such chains; every link is one row scan, a dependent read.
                 int i = ulist[0];
                 [[maybe_unused]] const int st_bids0 = st_bids;
-                if (a.src && a.tgt && wmax > 1) {       // n >= 2048; below, one wave walks the chain without any barrier (faster: measured)
+                if constexpr (!LARGE) if (a.src && a.tgt && wmax > 1) {       // n >= 2048; below, one wave walks the chain without any barrier (faster: measured)
                     // Points form: the chain's rows are recomputed, not read.  Every link of the matrix form is a dependent
                     // row read (3.2 us at n = 4096; a phase's last row walks thousands of links).  Here the source points
                     // are staged once per chain into LDS arrays that are idle between rounds (pbobj | ulist | bidder);
@@ -542,7 +575,7 @@ __global__ __launch_bounds__(LAP_BS) void lap_auction_kernel(LapArgs a) {
                         for (;;) {
                             double v1, v2;
                             int j1;
-                            lap_row_top2(C + (size_t)i * n, price, n, lane, v1, j1, v2);
+                            lap_row_top2<RU>(C + (size_t)i * n, price, n, lane, v1, j1, v2);
                             if (!(v2 < INFINITY)) v2 = v1;
                             const int prev = owner[j1];
                             if (lane == 0) {
@@ -568,7 +601,7 @@ __global__ __launch_bounds__(LAP_BS) void lap_auction_kernel(LapArgs a) {
                     double v1, v2;
                     int j1;
                     if (wv < wmax) {
-                        lap_row_top2_range(C + (size_t)i * n, price, min(n, wv * len), min(n, (wv + 1) * len), lane, v1, j1, v2);
+                        lap_row_top2_range<RU>(C + (size_t)i * n, price, min(n, wv * len), min(n, (wv + 1) * len), lane, v1, j1, v2);
                         if (lane == 0) { s_pv1[wv] = v1; s_pv2[wv] = v2; s_pj1[wv] = j1; }
                     }
                     __syncthreads();
@@ -608,7 +641,7 @@ __global__ __launch_bounds__(LAP_BS) void lap_auction_kernel(LapArgs a) {
                 if (g < nu) {
                     double v1, v2;
                     int j1;
-                    lap_row_top2_range(C + (size_t)ulist[g] * n, price, min(n, seg * len), min(n, (seg + 1) * len), lane, v1, j1, v2);
+                    lap_row_top2_range<RU>(C + (size_t)ulist[g] * n, price, min(n, seg * len), min(n, (seg + 1) * len), lane, v1, j1, v2);
                     if (lane == 0) { s_pv1[wv] = v1; s_pv2[wv] = v2; s_pj1[wv] = j1; }
                 }
                 __syncthreads();
@@ -628,7 +661,7 @@ __global__ __launch_bounds__(LAP_BS) void lap_auction_kernel(LapArgs a) {
                 const int i = ulist[u];
                 double v1, v2;
                 int j1;
-                lap_row_top2(C + (size_t)i * n, price, n, lane, v1, j1, v2);
+                lap_row_top2<RU>(C + (size_t)i * n, price, n, lane, v1, j1, v2);
                 if (lane == 0) {
                     if (!(v2 < INFINITY)) v2 = v1;                  // n == 1
                     const double bid = price[j1] + (v2 - v1) + eps;
@@ -641,16 +674,16 @@ __global__ __launch_bounds__(LAP_BS) void lap_auction_kernel(LapArgs a) {
             JPH(3);
             for (int u = tid; u < nu; u += LAP_BS) {
                 const int i = ulist[u], j = pbobj[i];
-                if (lap_key(pbval[i]) == bidval[j]) atomicMin(&bidder[j], i);
+                if (lap_key(pbval[i]) == lap_bid_load<LARGE>(&bidval[j])) atomicMin(&bidder[j], i);
             }
             __syncthreads();
             for (int j = tid; j < n; j += LAP_BS) {
-                const int w = bidder[j];
+                const int w = lap_bid_load<LARGE>(&bidder[j]);
                 if (w != 0x7fffffff) {
                     const int prev = owner[j];
                     if (prev >= 0) assigned[prev] = -1;
                     owner[j] = w; assigned[w] = j;
-                    price[j] = __longlong_as_double((long long)bidval[j]);
+                    price[j] = __longlong_as_double((long long)lap_bid_load<LARGE>(&bidval[j]));
                     bidder[j] = 0x7fffffff;
                 }
                 bidval[j] = 0ull;
@@ -676,7 +709,7 @@ __global__ __launch_bounds__(LAP_BS) void lap_auction_kernel(LapArgs a) {
         if (s_abort) return;
         // Jacobi round: m_i = min_k (c_ik + d_k) with the old d; new d_sigma(i) = m_i - c_i,sigma(i)
         for (int i = wv; i < n; i += NW) {
-            const double v1 = lap_row_min(C + (size_t)i * n, d, n, lane);
+            const double v1 = lap_row_min<RU>(C + (size_t)i * n, d, n, lane);
             if (lane == 0) {
                 const int j = assigned[i];
                 const double cur = (double)C[(size_t)i * n + j] + d[j];
@@ -749,7 +782,7 @@ static int lap_launch(const float *cost, int B, int n, int32_t *col4row, int32_t
     a.pbval_ws = (double *)((char *)a.stats + reart_align_up(sizeof(int) * 4 * (size_t)B, 256));
     const size_t lds = (size_t)n * ((n <= LAP_NLDS ? 3 : 2) * 8 + 5 * 4);
     if (lds > REART_LDS_DEFAULT_CAP &&
-        hipFuncSetAttribute((const void *)lap_auction_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024) != hipSuccess)
+        hipFuncSetAttribute((const void *)lap_auction_kernel<LAP_NMAX>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024) != hipSuccess)
         return REART_ERR_LAUNCH;
     if (racers > 1) {
         if (racers > LAP_RACE_MAX) return REART_ERR_INVALID_ARG;
@@ -767,7 +800,50 @@ static int lap_launch(const float *cost, int B, int n, int32_t *col4row, int32_t
             hipMemsetAsync(certified, 0, sizeof(int32_t) * (size_t)B, (hipStream_t)stream) != hipSuccess)
             return REART_ERR_LAUNCH;
     }
-    hipLaunchKernelGGL(lap_auction_kernel, dim3(B, racers), dim3(LAP_BS), lds, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(lap_auction_kernel<LAP_NMAX>, dim3(B, racers), dim3(LAP_BS), lds, (hipStream_t)stream, a);
+    REART_CHECK_LAUNCH();
+    return REART_OK;
+}
+
+// ---- the large instance: 1 <= n <= REART_LAP_LARGE_MAX_N, cold, one workgroup per matrix (lap_auction_kernel<8192>)
+static_assert(REART_LAP_LARGE_MAX_N == 2 * LAP_NMAX && REART_LAP_LARGE_MAX_N % LAP_BS == 0, "the large instance holds twice the columns per thread");
+static_assert((size_t)REART_LAP_LARGE_MAX_N * 18 <= 152 * 1024 - 4096 && REART_LAP_LARGE_MAX_N <= 65536,
+              "prices, owners, assignment and the searches' 16-bit predecessor rows of the large instance stay in LDS");
+// Certificate rounds of the large form.  A round is one pass of ONE compute unit over the matrix (268 MB at n = 8192), and
+// the 4 n rounds the small form allows would be minutes inside one launch.  The cold solves report 19-36 rounds on the
+// 4096^2 energy problems (stats[b][3]) and 16-42 on 19 x {4097, 6144, 8192}^2 (profiles/lap_large_bench.json); 256 is six
+// times the largest of them.  A whole 8192^2 solve there, up to 40 rounds included, takes 1.1 s: a round costs less than
+// 28 ms, so the cap holds a launch within 7 s of a normal solve.  A matrix that needs more rounds is reported uncertified
+// and solved by the caller on the host, like any other whose certificate does not close.
+#define LAP_LARGE_CERT_ROUNDS 256
+
+// potentials [B][n] f64 | diagnostics [B][4] (both where reart_lap_workspace_bytes has them) | rows' bids [B][n] f64 |
+// columns' highest bids [B][n] u64 | per matrix: winning rows, rows' bid columns, unassigned rows [B][3][n] i32
+extern "C" size_t reart_lap_large_workspace_bytes(int B, int n) {
+    if (B < 0 || n < 1 || n > REART_LAP_LARGE_MAX_N) return 0;
+    return reart_align_up(sizeof(double) * (size_t)B * n, 256) + reart_align_up(sizeof(int) * 4 * (size_t)B, 256) +
+           reart_align_up((size_t)B * n * (8 + 8 + 3 * 4), 256);
+}
+
+extern "C" int reart_lap_auction_large(const float *cost, const float *src, const float *tgt, int B, int n, int32_t *col4row,
+                                       int32_t *certified, double *price_out, void *workspace, size_t workspace_bytes, void *stream) {
+    if (B < 0 || n < 1 || n > REART_LAP_LARGE_MAX_N || (src == nullptr) != (tgt == nullptr)) return REART_ERR_INVALID_ARG;
+    if (B == 0) return REART_OK;
+    if (!cost || !col4row || !certified || !price_out) return REART_ERR_INVALID_ARG;
+    if (!workspace || workspace_bytes < reart_lap_large_workspace_bytes(B, n)) return REART_ERR_INVALID_ARG;
+    LapArgs a = {};
+    a.cost = cost; a.B = B; a.n = n; a.col4row = col4row; a.certified = certified; a.price_out = price_out;
+    a.src = src; a.tgt = tgt;            // accepted for the callers' sake; the large instance's chains read the matrix
+    a.max_rounds_cert = 4 * n < LAP_LARGE_CERT_ROUNDS ? 4 * n : LAP_LARGE_CERT_ROUNDS;
+    a.eps0 = LAP_EPS0; a.theta_inv = 1.0 / LAP_THETA; a.eps_final = 1e-11;
+    a.stats = (int *)((char *)workspace + reart_align_up(sizeof(double) * (size_t)B * n, 256));
+    a.pbval_ws = (double *)((char *)a.stats + reart_align_up(sizeof(int) * 4 * (size_t)B, 256));
+    const size_t lds = (size_t)n * 18;
+    if (lds > REART_LDS_DEFAULT_CAP &&
+        hipFuncSetAttribute((const void *)lap_auction_kernel<REART_LAP_LARGE_MAX_N>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            152 * 1024) != hipSuccess)
+        return REART_ERR_LAUNCH;
+    hipLaunchKernelGGL(lap_auction_kernel<REART_LAP_LARGE_MAX_N>, dim3(B), dim3(LAP_BS), lds, (hipStream_t)stream, a);
     REART_CHECK_LAUNCH();
     return REART_OK;
 }

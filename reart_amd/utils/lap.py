@@ -1,7 +1,8 @@
 """Batched linear assignment for the assignment loss (reference run_robot.py:164-187,
 utils/model_utils.py:85-103): ``[linear_sum_assignment(c) for c in cost]`` / ``parallel_lap(cost, nproc)``
-on the GPU (``reart_lap_auction``: epsilon-scaling auction + exact dual certificate).  A matrix whose
-certificate does not close is solved with scipy on the host, so the result is always an optimal assignment."""
+on the GPU (``reart_lap_auction``: epsilon-scaling auction + exact dual certificate; ``reart_lap_auction_large`` for
+4096 < n <= 8192).  A matrix whose certificate does not close is solved with scipy on the host, so the result is always
+an optimal assignment."""
 import contextlib
 import os
 
@@ -41,6 +42,9 @@ def linear_sum_assignment_batch(cost, return_stats=False, state=None, warm_assig
                                 race=False):
     """cost [B,n,n] float32 CUDA tensor (square) -> list of (row_ind, col_ind) int64 numpy arrays, like
     ``[scipy.optimize.linear_sum_assignment(c) for c in cost]`` (rows in ascending order).
+    n <= 4096: the entries described below.  4096 < n <= 8192: always the cold solve ``reart_lap_auction_large`` (one workgroup
+    per matrix; ``race``, ``method`` and a warm ``state`` have no effect, ``points`` are passed through, ``state`` receives the
+    potentials and the assignment).  Above that: scipy on the host.
     ``state``: a dict kept by the caller between calls on slowly changing matrices (the loop re-solves every
     ``assign_gap`` iterations); it carries the column potentials of the previous solve as a warm start.
     ``warm_assignment=True`` (with ``state``) also carries the previous assignment and keeps the pairs that are still
@@ -76,7 +80,9 @@ def linear_sum_assignment_batch(cost, return_stats=False, state=None, warm_assig
     col = torch.full((B, n), -1, dtype=torch.int32, device=cost.device)
     cert = torch.zeros((B,), dtype=torch.int32, device=cost.device)
     nbytes = L.reart_lap_workspace_bytes(B, n)
-    if nbytes == 0:   # n > 4096: beyond the kernel's LDS state -- the reference's host solver
+    if nbytes == 0 and n <= _lib.LAP_LARGE_MAX_N:
+        return _solve_large(L, cost, src, tgt, col, cert, return_stats, state, warm_assignment or race == "warm")
+    if nbytes == 0:   # n > 8192: beyond the kernels' LDS state -- the reference's host solver
         from scipy.optimize import linear_sum_assignment
 
         out = [linear_sum_assignment(c) for c in cost.cpu().numpy()]
@@ -141,6 +147,37 @@ def linear_sum_assignment_batch(cost, return_stats=False, state=None, warm_assig
         off = ((8 * B * n + 255) // 256) * 256
         st = ws[off:off + 16 * B].view(torch.int32).reshape(B, 4).cpu().numpy()
         return out, fallbacks, st
+    return (out, fallbacks) if return_stats else out
+
+
+def _solve_large(L, cost, src, tgt, col, cert, return_stats, state, keep_cols):
+    """4096 < n <= 8192 (``reart_lap_auction_large``): always a cold solve, one workgroup per matrix, the same certificate and
+    the same host fallback as below the limit.  A ``state`` receives the potentials and (``keep_cols``) the assignment."""
+    B, n, _ = cost.shape
+    prices = torch.zeros((B, n), dtype=torch.float64, device=cost.device)
+    if state is not None:
+        state["prices"] = prices
+    ws = _lib.workspace(L.reart_lap_large_workspace_bytes(B, n), cost.device)
+    off = ((8 * B * n + 255) // 256) * 256                    # [B][4] statistics, as in the layout below the limit
+    rc = L.reart_lap_auction_large(_lib.ptr(cost), _lib.ptr(src), _lib.ptr(tgt), B, n, _lib.ptr(col), _lib.ptr(cert), _lib.ptr(prices),
+                                   _lib.ptr(ws), ws.numel(), _lib.stream())
+    _lib.check(rc, "reart_lap_auction_large")
+    col_h, cert_h = col.cpu().numpy().astype(np.int64), cert.cpu().numpy()
+    rows = np.arange(n, dtype=np.int64)
+    out, fallbacks = [], 0
+    for b in range(B):
+        if cert_h[b]:
+            out.append((rows, col_h[b]))
+        else:  # certificate did not close: exact host solve for this matrix
+            from scipy.optimize import linear_sum_assignment
+
+            fallbacks += 1
+            out.append(linear_sum_assignment(cost[b].cpu().numpy()))
+            _forget_uncertified(state, col, b, out[-1][1])
+    if state is not None and keep_cols:
+        state["cols"] = col.clone()
+    if return_stats == "full":
+        return out, fallbacks, ws[off:off + 16 * B].view(torch.int32).reshape(B, 4).cpu().numpy()
     return (out, fallbacks) if return_stats else out
 
 
