@@ -687,6 +687,26 @@ int reart_lap_resolve(const float *cost, int B, int n, int32_t *col4row, int32_t
                       const double *price_in, double *price_out, void *workspace, size_t workspace_bytes,
                       void *stream);
 
+/* reart_lap_resolve for matrices of up to 8192 columns (every 1 <= n <= REART_LAP_LARGE_MAX_N is accepted; the Python wrapper
+ * sends it n > 4096 only): the same steps -- kept pairs, greedy take-up, augmenting row reduction, one Dijkstra search per
+ * row still free, fp64 certificate -- in an instance of the same kernel that keeps its four index arrays in LDS (16 B per
+ * column) and the row potentials in the workspace.  Always four launches, one workgroup per matrix in the sequential part, not
+ * raced: the result is a function of the matrix and the incoming state, bit for bit.  Same arguments as reart_lap_resolve:
+ * col4row holds the previous assignment on entry (out-of-range entries are free rows, a repeated column keeps its lowest
+ * row), price_in (required) the previous potentials; price_out is required and may alias price_in.
+ * Two caps bound a call whose state is useless (the matrices jumped): the certificate takes at most 256 rounds, as in
+ * reart_lap_auction_large, and a matrix takes at most `max_steps` row-reduction + path-search steps (each a dependent row
+ * read; <= 0: the library's default, a multiple of n).  A matrix that reaches either cap comes back with certified[b] = 0,
+ * the step cap also sets bit 30 of its first diagnostics word; the call still returns REART_OK and the caller solves that
+ * matrix cold (reart_lap_auction_large).
+ * workspace: reart_lap_resolve_large_workspace_bytes (0 unless B >= 0 and 1 <= n <= REART_LAP_LARGE_MAX_N); diagnostics
+ * [B][4] at the same offset as in reart_lap_workspace_bytes' layout, in reart_lap_resolve's meaning: released rows (+ bit
+ * 30), rows left for the searches, search steps, certificate rounds + row-reduction steps << 8. */
+size_t reart_lap_resolve_large_workspace_bytes(int B, int n);
+int reart_lap_resolve_large(const float *cost, int B, int n, int max_steps, int32_t *col4row, int32_t *certified,
+                            const double *price_in, double *price_out, void *workspace, size_t workspace_bytes,
+                            void *stream);
+
 /* Measurement aid for the latency roofline of reart_lap_resolve_points (no reference counterpart): B workgroups run
  * `steps` path-search steps of the re-solve stripped to what cannot be removed -- the workgroup-wide (distance, column)
  * arg-min over n <= 2048 labels held in registers and its one barrier, with the solver's own primitives -- and

@@ -22,7 +22,7 @@ MAX_K_LIST = 1024        # REART_MAX_K_LIST: K-NN list in LDS, the largest K of 
 MAX_D = 256              # REART_MAX_D: point dimension of the K-NN searches and their backward
 MAX_POSE_LEN = 1024      # REART_MAX_POSE_LEN: frames T - 1 of the relaxation model and the fused step
 IK_MAX_POINTS = 1024     # REART_IK_MAX_POINTS: sparse points of reart_ik_fit, held in LDS
-LAP_LARGE_MAX_N = 8192   # REART_LAP_LARGE_MAX_N: columns of reart_lap_auction_large (prices, owners, assignment in LDS)
+LAP_LARGE_MAX_N = 8192   # REART_LAP_LARGE_MAX_N: columns of reart_lap_auction_large / reart_lap_resolve_large (solver state in LDS)
 FPS_MAX_N_LDS = 12288    # REART_FPS_MAX_N_LDS: reart_fps, cloud staged in LDS
 FPS_MAX_N = 1 << 21      # REART_FPS_MAX_N: reart_fps_temp, 21-bit index in the tie key
 
@@ -100,6 +100,8 @@ PROTOTYPES = {
     "reart_lap_large_workspace_bytes": (c_size_t, [c_int] * 2),
     "reart_lap_auction_large": (c_int, [P, P, P, c_int, c_int, P, P, P, P, c_size_t, P]),
     "reart_lap_resolve": (c_int, [P, c_int, c_int, P, P, P, P, P, c_size_t, P]),
+    "reart_lap_resolve_large_workspace_bytes": (c_size_t, [c_int] * 2),
+    "reart_lap_resolve_large": (c_int, [P, c_int, c_int, c_int, P, P, P, P, P, c_size_t, P]),
     "reart_lap_resolve_points": (c_int, [P, P, c_int, c_int, P, P, P, P, P, c_size_t, P]),
     "reart_lap_resolve_points_race": (c_int, [P, P, c_int, c_int, c_int, P, P, P, P, P, c_size_t, P]),
     "reart_lap_resolve_points_mw": (c_int, [P, P, c_int, c_int, c_int, P, P, P, P, P, c_size_t, P]),

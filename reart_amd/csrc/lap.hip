@@ -999,18 +999,38 @@ __device__ __forceinline__ void lap_row_min_pts_seeded(float ax, float ay, float
 // MODE 0: the whole re-solve in one launch.  MODE 1: the sequential part only -- row potentials come from lap_jv_pass_kernel
 // (pre_*), the certificate is left to the next two launches (certified[b] = 2: pending).  MODE 2: certificate of a pending
 // matrix whose first round (lap_jv_pass_kernel, pass_mode 1) found a violation: the Jacobi rounds from the solve's prices.
-template <int BS, bool PTS, int MODE>
+//
+// CAP: the columns one workgroup holds (JV_CPT = CAP / BS per thread).  Up to LAP_NMAX (and in the points form) the whole state
+// is in LDS, 32 B per column: price, u (f64), owner, assigned, pred, flist (i32).  The LARGE instance (CAP = 8192, matrix form,
+// MODE 1 and 2 only: reart_lap_resolve_large) keeps 16 B per column in LDS -- 128 KB at 8192:
+//   LDS        owner, pred, assigned, flist (i32 each).  MODE 2 needs neither owner nor pred, and its potentials (f64) lie
+//              where those two were.
+//   registers  as below the limit: the prices of the thread's columns (pr / pj), their owners during the row reduction, the
+//              labels d[] and the scanned / unowned masks of a search.
+//   workspace  the row potentials u (a.u_ws, 8 B per row; the certificate rounds' per-row scratch pb is the same array), and
+//              in MODE 1 the column prices between the phases (a.price_out itself: every thread reads and writes only its own
+//              columns there -- once before the row reduction, once after it, and the labelled columns after a search).
+// A search step reads u[i] of the one row it relaxes together with that row's costs: still one dependent trip to global
+// memory and one barrier per step.  What a thread writes to the workspace is read by other waves only behind a
+// __syncthreads(), the same barriers that ordered the accesses when the arrays were in LDS (one workgroup, one compute
+// unit: the barrier's workgroup-scope release / acquire covers global memory too).
+// a.max_steps (LARGE): row-reduction + search steps allowed for the matrix; beyond, the workgroup leaves through the
+// `solved = false` exit -- certified[b] = 0, bit 30 of stats[b][0].
+template <int BS, bool PTS, int MODE, int CAP = (PTS ? JV_PTS_NMAX : LAP_NMAX)>
 __global__ __launch_bounds__(BS) void lap_jv_kernel(JvArgs a) {
-    constexpr int JV_CPT = (PTS ? JV_PTS_NMAX : LAP_NMAX) / BS;
+    constexpr int JV_CPT = CAP / BS;
+    constexpr bool LARGE = CAP > LAP_NMAX;
+    static_assert(!LARGE || (!PTS && MODE != 0), "the large instance: matrix form, three launches");
+    static_assert(JV_CPT <= 32 && CAP % BS == 0 && (BS & (BS - 1)) == 0, "a search keeps one bit per column of a thread");
     extern __shared__ __attribute__((aligned(16))) unsigned char lsm[];
     const int n = a.n, b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     constexpr int NW = BS / 64;
-    double *price = (double *)lsm;            // [n]
-    double *u = price + n;                    // [n] row potentials
-    int *owner = (int *)(u + n);              // [n] column -> row
-    int *assigned = owner + n;                // [n] row -> column
-    int *pred = assigned + n;                 // [n] column -> row it was reached from
-    int *flist = pred + n;                    // [n] free rows / arg-min columns
+    double *price = LARGE && MODE == 1 ? a.price_out + (size_t)b * n : (double *)lsm;   // [n]
+    double *u = LARGE ? a.u_ws + (size_t)b * n : price + n;                              // [n] row potentials
+    int *owner = LARGE ? (int *)lsm : (int *)(u + n);                                    // [n] column -> row
+    int *assigned = LARGE ? owner + 2 * n : owner + n;                                   // [n] row -> column
+    int *pred = LARGE ? owner + n : assigned + n;                                        // [n] column -> row it was reached from
+    int *flist = LARGE ? assigned + n : pred + n;                                        // [n] free rows / arg-min columns
     float *psx = (float *)(flist + n);        // PTS: src x|y|z [3][n], tgt x|y|z [3][n]
     float *psy = psx + n, *psz = psy + n, *ptx = psz + n, *pty = ptx + n, *ptz = pty + n;
     __shared__ double s_rv[2][NW];
@@ -1062,7 +1082,7 @@ __global__ __launch_bounds__(BS) void lap_jv_kernel(JvArgs a) {
     if (lane == 0) s_red[wv] = mx;
     for (int j = tid; j < n; j += BS) {
         price[j] = race ? a.price_start[(size_t)b * n + j] : (a.price_in ? a.price_in[(size_t)b * n + j] : 0.0);
-        owner[j] = -1;
+        if (!(LARGE && MODE == 2)) owner[j] = -1;             // (there the potentials lie where the owners were)
         const int c = (race ? a.col_start : a.col4row)[(size_t)b * n + j];
         assigned[j] = (c >= 0 && c < n) ? c : -1;
     }
@@ -1074,6 +1094,7 @@ __global__ __launch_bounds__(BS) void lap_jv_kernel(JvArgs a) {
     const double keep_tol = mx * a.keep_tol;
     int st_freed = 0, st_left = 0, st_steps = 0, st_cert = 0, st_arr = 0;
     bool solved = true;
+    [[maybe_unused]] bool gave_up = false;                     // LARGE: a.max_steps reached
     if (MODE != 2) {
     // previous pairs: a repeated column keeps its lowest row
     for (int i = tid; i < n; i += BS)
@@ -1088,6 +1109,7 @@ __global__ __launch_bounds__(BS) void lap_jv_kernel(JvArgs a) {
             const double v1 = a.pre_v1[(size_t)b * n + i];
             const int j = assigned[i];
             u[i] = v1; flist[i] = a.pre_j1[(size_t)b * n + i];
+            if (LARGE && (unsigned)flist[i] >= (unsigned)n) flist[i] = 0;               // (no arg-min: a row without a finite cost)
             if (j >= 0) {
                 const double cur = a.pre_cur[(size_t)b * n + i];          // of the column col4row named: still the row's
                 if (cur - v1 > keep_tol) { assigned[i] = -1; owner[j] = -1; }
@@ -1185,11 +1207,13 @@ __global__ __launch_bounds__(BS) void lap_jv_kernel(JvArgs a) {
             own[k] = j < n ? owner[j] : -1;
         }
         int ncur = nfree, budget = JV_ARR_BUDGET * nfree + 64;          // uniform over the workgroup: every thread follows the chain
+        [[maybe_unused]] bool capped = false;
+        if (LARGE && a.max_steps < budget) { budget = a.max_steps; capped = true; }
         int *next = pred;                                   // not needed before the path search
         int par = 0;
-        for (int pass = 0; pass < 2 && ncur > 0; ++pass) {
+        for (int pass = 0; pass < 2 && ncur > 0 && !(LARGE && gave_up); ++pass) {
             int nnext = 0;
-            for (int k0 = 0; k0 < ncur; ++k0) {
+            for (int k0 = 0; k0 < ncur && !(LARGE && gave_up); ++k0) {
                 int i = flist[jv_order(k0, ncur, racer)];
                 for (;;) {
                     float rc[JV_CPT];
@@ -1210,10 +1234,12 @@ __global__ __launch_bounds__(BS) void lap_jv_kernel(JvArgs a) {
                     lap_lanes_top2<(NW <= 2 ? 1 : (NW <= 4 ? 2 : (NW <= 8 ? 3 : 4)))>(v1, j1, v2, i0);
                     par ^= 1;
                     const bool tie = !(v1 < v2);
-                    const bool stop = budget-- <= 0 || (tie && i0 >= 0);
+                    const bool spent = budget-- <= 0;
+                    const bool stop = spent || (tie && i0 >= 0) || (LARGE && j1 == 0x7fffffff);
                     if (stop) {
                         if (tid == 0) { next[nnext] = i; u[i] = v1; }
                         ++nnext;
+                        if (LARGE && spent && capped) gave_up = true;
                         break;
                     }
                     if ((j1 & (BS - 1)) == tid) {                            // the arg-min's thread
@@ -1235,6 +1261,7 @@ __global__ __launch_bounds__(BS) void lap_jv_kernel(JvArgs a) {
             __syncthreads();
             ncur = nnext;
         }
+        if (LARGE && gave_up) { ncur = 0; solved = false; }     // no searches: the matrix is reported uncertified
 #pragma unroll
         for (int k = 0; k < JV_CPT; ++k) {
             const int j = tid + k * BS;
@@ -1255,6 +1282,7 @@ __global__ __launch_bounds__(BS) void lap_jv_kernel(JvArgs a) {
     double pj[JV_CPT];
 #pragma unroll
     for (int k = 0; k < JV_CPT; ++k) pj[k] = tid + k * BS < n ? price[tid + k * BS] : 0.0;
+    [[maybe_unused]] const int steps_cap = LARGE ? a.max_steps - st_arr : 0;
     for (int f = 0; f < nfree; ++f) {
         const int i0 = flist[jv_order(f, nfree, racer)];
         double d[JV_CPT];
@@ -1303,6 +1331,7 @@ __global__ __launch_bounds__(BS) void lap_jv_kernel(JvArgs a) {
             bv = lane < NW ? s_rv[par][lane] : INFINITY; bj = lane < NW ? s_rj[par][lane] : 0x7fffffff;
             lap_lanes_argmin<(NW <= 2 ? 1 : (NW <= 4 ? 2 : (NW <= 8 ? 3 : 4)))>(bv, bj);
             ++st_steps;
+            if (LARGE && st_steps > steps_cap) { gave_up = true; break; }       // (sink < 0: the exit of an unsolved matrix)
             mu = bv;
             const int jstar = bj == 0x7fffffff ? bj : (bj & ~JV_OWNED);
             JPH(2);
@@ -1388,7 +1417,7 @@ __global__ __launch_bounds__(BS) void lap_jv_kernel(JvArgs a) {
         if (!changed) { certified = 1; break; }
     }
     for (int i = tid; i < n; i += BS) a.col4row[(size_t)b * n + i] = assigned[i];
-    if (a.price_out)
+    if (a.price_out && !(LARGE && MODE == 1))             // (there the prices are kept in price_out all along)
         for (int j = tid; j < n; j += BS) a.price_out[(size_t)b * n + j] = dd[j];
     if (tid == 0) a.certified[b] = MODE == 1 ? (solved ? 2 : 0) : certified;
     if (MODE == 1 && tid == 0) { a.scale[b] = mx; a.cert_bad[b] = 0; }
@@ -1397,7 +1426,7 @@ __global__ __launch_bounds__(BS) void lap_jv_kernel(JvArgs a) {
     if (tid == 0 && a.stats) {
         int *o = a.stats + 4 * b;
         if (MODE == 2) o[3] += st_cert;          // on top of the first round the pass kernel ran
-        else { o[0] = st_freed + (racer << 16); o[1] = st_left; o[2] = st_steps; o[3] = (MODE == 1 ? 1 : st_cert) + (st_arr << 8); }
+        else { o[0] = st_freed + (racer << 16) + (LARGE && gave_up ? 1 << 30 : 0); o[1] = st_left; o[2] = st_steps; o[3] = (MODE == 1 ? 1 : st_cert) + (st_arr << 8); }
     }
 }
 
@@ -1519,6 +1548,28 @@ __global__ __launch_bounds__(JV_PASSP_BS) void lap_jv_pass_pts_kernel(JvArgs a) 
 
 // Re-solve from the assignment in col4row and the potentials in price_in (both from an earlier solve of a similar batch,
 // reart_lap_auction* or these functions); same outputs and the same certificate as reart_lap_auction.
+// ---- the large instance of the matrix form (lap_jv_kernel<JV_LARGE_BS, false, 1 | 2, 8192>): see the kernel's comment
+// Threads per workgroup, from the compiler's resource report (profiles/lap_resolve_large_resources.txt): 512 threads hold 16
+// columns each, the per-thread state of the 4096 instance (256 x 16): 185 VGPRs, no scratch, two waves per SIMD.  256 x 32
+// doubles the labels and prices a thread keeps (d[], pj[]: 128 VGPRs for them alone): 256 VGPRs and 86 more values in AGPRs.
+#define JV_LARGE_BS 512
+#define JV_LARGE_LDS_PER_COL 16        // owner, pred, assigned, flist: i32 each
+static_assert((size_t)REART_LAP_LARGE_MAX_N * JV_LARGE_LDS_PER_COL <= 152 * 1024 - 4096, "the large re-solve's index arrays stay in LDS");
+// Steps (row reduction + searches) a matrix may take when the caller passes max_steps <= 0, as a multiple of n: the number
+// of steps that takes as long as ONE cold solve, so that a warm attempt followed by its cold second attempt costs about two
+// cold solves at worst.  Measured (tools/bench_lap_resolve_large.py, profiles/lap_resolve_large_bench.json, "max_steps";
+// B = 19): a sequential step -- one dependent row read, one barrier -- takes 2.81 / 2.98 / 3.21 us at n = 4097 / 6144 / 8192
+// (the jump case under a limit of 32 n steps, most of them search steps), a cold solve 628 / 643 / 1113 ms (medians), which
+// is 54.5 / 35.2 / 42.4 x n steps; the smallest, rounded down.  The timings of that file were taken with this limit.
+#define LAP_LARGE_STEPS_PER_N 35
+extern "C" size_t reart_lap_resolve_large_workspace_bytes(int B, int n) {
+    if (B < 0 || n < 1 || n > REART_LAP_LARGE_MAX_N) return 0;
+    // the layout of reart_lap_workspace_bytes (potentials | diagnostics [B][4] | unused [B][n] f64 | v1, cur [B][n] f64 | j1 [B][n]
+    // i32 | scale [B] f64 | cert_bad [B] i32) and behind it the row potentials [B][n] f64
+    return reart_align_up(sizeof(double) * (size_t)B * n, 256) * 5 + reart_align_up(sizeof(int) * 4 * (size_t)B, 256) +
+           reart_align_up(sizeof(int) * (size_t)B * n, 256) + reart_align_up(sizeof(double) * (size_t)B, 256) +
+           reart_align_up(sizeof(int) * (size_t)B, 256);
+}
 // the state arrays of the many-compute-unit row reduction, behind the race layout
 static size_t jv_mc_extra_bytes(int B, int n) {
     return reart_align_up(sizeof(double) * (size_t)B * n, 256) + 6 * reart_align_up(sizeof(int) * (size_t)B * n, 256) +
@@ -1531,22 +1582,33 @@ extern "C" size_t reart_lap_mc_workspace_bytes(int B, int n, int racers) {
 
 // per_wave: 0 = one row at a time (lap_jv_kernel), 1 = row reduction one chain per wave (lap_mw.hip), 2 = row reduction on
 // arr_wgs workgroups per problem (lap_mw.hip, three launches)
-template <bool PTS>
+// LARGE: the instance of reart_lap_resolve_large (matrix form, n <= REART_LAP_LARGE_MAX_N): always the three-launch form, at
+// every n, so that its logic can be tested on matrices of a few rows
+template <bool PTS, bool LARGE = false>
 static int jv_launch(JvArgs a, void *workspace, size_t workspace_bytes, void *stream, int racers = 1, int per_wave = 0, int arr_wgs = 0,
                      int *tie_out = nullptr) {
-    if (a.B < 0 || a.n < 1 || a.n > (PTS ? JV_PTS_NMAX : LAP_NMAX)) return REART_ERR_INVALID_ARG;
+    static_assert(!(PTS && LARGE), "the large instance reads a matrix");
+    constexpr int CAP = LARGE ? REART_LAP_LARGE_MAX_N : (PTS ? JV_PTS_NMAX : LAP_NMAX);
+    if (a.B < 0 || a.n < 1 || a.n > CAP) return REART_ERR_INVALID_ARG;
     if (racers < 1 || racers > JV_RACE_MAX) return REART_ERR_INVALID_ARG;
     if (a.B == 0) return REART_OK;
     if (!a.col4row || !a.certified || !a.price_in) return REART_ERR_INVALID_ARG;
     if (per_wave && (!PTS || a.n < JV_SPLIT_NMIN || a.n > reart_internal_jvmw_nmax())) return REART_ERR_UNSUPPORTED;
     if (a.n < JV_SPLIT_NMIN) racers = 1;       // one launch does everything there: nothing worth racing
-    if (!workspace || workspace_bytes < (racers > 1 ? reart_lap_race_workspace_bytes(a.B, a.n, racers) : reart_lap_workspace_bytes(a.B, a.n)))
+    if (!workspace || workspace_bytes < (LARGE ? reart_lap_resolve_large_workspace_bytes(a.B, a.n)
+                                               : racers > 1 ? reart_lap_race_workspace_bytes(a.B, a.n, racers) : reart_lap_workspace_bytes(a.B, a.n)))
         return REART_ERR_INVALID_ARG;
     if (!a.price_out) a.price_out = (double *)workspace;
-    a.max_rounds_cert = 4 * a.n; a.keep_tol = 1e-12;
+    a.max_rounds_cert = LARGE && 4 * a.n > LAP_LARGE_CERT_ROUNDS ? LAP_LARGE_CERT_ROUNDS : 4 * a.n; a.keep_tol = 1e-12;
     a.stats = (int *)((char *)workspace + reart_align_up(sizeof(double) * (size_t)a.B * a.n, 256));
-    const size_t lds = (size_t)a.n * (2 * 8 + 4 * 4 + (PTS ? 6 * 4 : 0));
-    constexpr int JVBS = PTS ? JV_PTS_BS : 256;
+    const size_t lds = LARGE ? (size_t)a.n * JV_LARGE_LDS_PER_COL : (size_t)a.n * (2 * 8 + 4 * 4 + (PTS ? 6 * 4 : 0));
+    constexpr int JVBS = LARGE ? JV_LARGE_BS : (PTS ? JV_PTS_BS : 256);
+    if constexpr (LARGE) {
+        if (lds > REART_LDS_DEFAULT_CAP &&
+            (hipFuncSetAttribute((const void *)lap_jv_kernel<JVBS, PTS, 1, CAP>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024) != hipSuccess ||
+             hipFuncSetAttribute((const void *)lap_jv_kernel<JVBS, PTS, 2, CAP>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024) != hipSuccess))
+            return REART_ERR_LAUNCH;
+    } else {
     if (lds > REART_LDS_DEFAULT_CAP &&
         (hipFuncSetAttribute((const void *)lap_jv_kernel<JVBS, PTS, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024) != hipSuccess ||
          hipFuncSetAttribute((const void *)lap_jv_kernel<JVBS, PTS, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024) != hipSuccess ||
@@ -1557,6 +1619,7 @@ static int jv_launch(JvArgs a, void *workspace, size_t workspace_bytes, void *st
         REART_CHECK_LAUNCH();
         return REART_OK;
     }
+    }
     {
         const size_t bn = reart_align_up(sizeof(double) * (size_t)a.B * a.n, 256);
         char *w = (char *)a.stats + reart_align_up(sizeof(int) * 4 * (size_t)a.B, 256) + bn;      // past the auction's row bids
@@ -1564,7 +1627,8 @@ static int jv_launch(JvArgs a, void *workspace, size_t workspace_bytes, void *st
         a.pre_cur = (double *)w; w += bn;
         a.pre_j1 = (int *)w; w += reart_align_up(sizeof(int) * (size_t)a.B * a.n, 256);
         a.scale = (double *)w; w += reart_align_up(sizeof(double) * (size_t)a.B, 256);
-        a.cert_bad = (int *)w;
+        a.cert_bad = (int *)w; w += reart_align_up(sizeof(int) * (size_t)a.B, 256);
+        if (LARGE) a.u_ws = (double *)w;                                                          // [B][n], behind the layout below the limit
     }
     int per = PTS ? (256 + a.B - 1) / a.B : (2 * 256 + a.B - 1) / a.B;   // workgroups per matrix: one of 16 waves (points) / two of 4 per compute unit over the batch
     const int pass_waves = (PTS ? JV_PASSP_BS : JV_PASS_BS) / 64;
@@ -1613,7 +1677,7 @@ static int jv_launch(JvArgs a, void *workspace, size_t workspace_bytes, void *st
         const int rc = reart_internal_jvmw_launch(a, racers, (hipStream_t)stream);
         if (rc != REART_OK) return rc;
     } else {
-        hipLaunchKernelGGL((lap_jv_kernel<JVBS, PTS, 1>), dim3(a.B, racers), dim3(JVBS), lds, (hipStream_t)stream, a);
+        hipLaunchKernelGGL((lap_jv_kernel<JVBS, PTS, 1, CAP>), dim3(a.B, racers), dim3(JVBS), lds, (hipStream_t)stream, a);
         REART_CHECK_LAUNCH();
     }
     a.done = nullptr;
@@ -1621,7 +1685,7 @@ static int jv_launch(JvArgs a, void *workspace, size_t workspace_bytes, void *st
     launch_pass();
     REART_CHECK_LAUNCH();
     a.price_in = a.price_out;                                  // the certificate continues from the solve's potentials
-    hipLaunchKernelGGL((lap_jv_kernel<JVBS, PTS, 2>), dim3(a.B), dim3(JVBS), lds, (hipStream_t)stream, a);
+    hipLaunchKernelGGL((lap_jv_kernel<JVBS, PTS, 2, CAP>), dim3(a.B), dim3(JVBS), lds, (hipStream_t)stream, a);
     REART_CHECK_LAUNCH();
     if (PTS && a.tie_edges && tie_out)                         // the cycle check over the pairs the pass listed (cert_bad: the rounds above moved the potentials)
         return reart_internal_tie_cycles(a.B, a.n, a.col4row, tie_out, a.tie_edges, a.tie_n, a.tie_cap, a.cert_bad, (hipStream_t)stream);
@@ -1635,6 +1699,20 @@ extern "C" int reart_lap_resolve(const float *cost, int B, int n, int32_t *col4r
     JvArgs a = {};
     a.cost = cost; a.B = B; a.n = n; a.col4row = col4row; a.certified = certified; a.price_in = price_in; a.price_out = price_out;
     return jv_launch<false>(a, workspace, workspace_bytes, stream);
+}
+
+// reart_lap_resolve for 1 <= n <= REART_LAP_LARGE_MAX_N: the same steps with one workgroup of JV_LARGE_BS threads per matrix,
+// at most LAP_LARGE_CERT_ROUNDS certificate rounds and at most max_steps sequential steps per matrix (<= 0: the default).
+extern "C" int reart_lap_resolve_large(const float *cost, int B, int n, int max_steps, int32_t *col4row, int32_t *certified,
+                                       const double *price_in, double *price_out, void *workspace, size_t workspace_bytes,
+                                       void *stream) {
+    if (B < 0 || n < 1 || n > REART_LAP_LARGE_MAX_N) return REART_ERR_INVALID_ARG;
+    if (B == 0) return REART_OK;
+    if (!cost || !price_out) return REART_ERR_INVALID_ARG;
+    JvArgs a = {};
+    a.cost = cost; a.B = B; a.n = n; a.col4row = col4row; a.certified = certified; a.price_in = price_in; a.price_out = price_out;
+    a.max_steps = max_steps > 0 ? max_steps : LAP_LARGE_STEPS_PER_N * n + 64;      // (+ 64: the row reduction's own allowance at small n)
+    return jv_launch<false, true>(a, workspace, workspace_bytes, stream);
 }
 
 // The same re-solve for Euclidean costs between two point sets WITHOUT a cost matrix: c_ij = the value reart_cdist(src,

@@ -163,6 +163,9 @@ struct JvArgs {
     // potentials -- its scan meets exactly those -- for the cycle check that follows the solve; null: not asked for
     int *tie_edges, *tie_n;    // [B][n][tie_cap] every row's tight columns (its first tie_cap) | [B][n] how many it has
     int tie_cap;
+    // large instance of the matrix form (lap_jv_kernel<., false, ., 8192>, reart_lap_resolve_large)
+    double *u_ws;              // [B][n] row potentials of the sequential part / per-row scratch of the certificate rounds
+    int max_steps;             // row-reduction + path-search steps of one matrix before it is given up (certified 0, bit 30 of stats[b][0])
 };
 
 // ties.hip: the cycle check over pair lists a solve's certificate pass wrote (reart_lap_resolve_points_mc_ties); `stale` [B]

@@ -1,7 +1,7 @@
 """Batched linear assignment for the assignment loss (reference run_robot.py:164-187,
 utils/model_utils.py:85-103): ``[linear_sum_assignment(c) for c in cost]`` / ``parallel_lap(cost, nproc)``
-on the GPU (``reart_lap_auction``: epsilon-scaling auction + exact dual certificate; ``reart_lap_auction_large`` for
-4096 < n <= 8192).  A matrix whose certificate does not close is solved with scipy on the host, so the result is always
+on the GPU (``reart_lap_auction``: epsilon-scaling auction + exact dual certificate; ``reart_lap_auction_large`` and the warm
+``reart_lap_resolve_large`` for 4096 < n <= 8192).  A matrix whose certificate does not close is solved with scipy on the host, so the result is always
 an optimal assignment."""
 import contextlib
 import os
@@ -42,9 +42,11 @@ def linear_sum_assignment_batch(cost, return_stats=False, state=None, warm_assig
                                 race=False):
     """cost [B,n,n] float32 CUDA tensor (square) -> list of (row_ind, col_ind) int64 numpy arrays, like
     ``[scipy.optimize.linear_sum_assignment(c) for c in cost]`` (rows in ascending order).
-    n <= 4096: the entries described below.  4096 < n <= 8192: always the cold solve ``reart_lap_auction_large`` (one workgroup
-    per matrix; ``race``, ``method`` and a warm ``state`` have no effect, ``points`` are passed through, ``state`` receives the
-    potentials and the assignment).  Above that: scipy on the host.
+    n <= 4096: the entries described below.  4096 < n <= 8192: one workgroup per matrix, never raced -- with
+    ``warm_assignment`` (or ``race="warm"``) and the potentials and assignment of an earlier call in ``state`` the warm re-solve
+    ``reart_lap_resolve_large`` (``method="paths"``; matrices it gives up are solved cold in the same call), otherwise the cold
+    solve ``reart_lap_auction_large``; ``points`` are passed through, ``state`` receives the potentials, the assignment and which
+    path ran (``resolve_form``, ``resolve_cold``: see ``_solve_large``).  Above that: scipy on the host.
     ``state``: a dict kept by the caller between calls on slowly changing matrices (the loop re-solves every
     ``assign_gap`` iterations); it carries the column potentials of the previous solve as a warm start.
     ``warm_assignment=True`` (with ``state``) also carries the previous assignment and keeps the pairs that are still
@@ -81,7 +83,7 @@ def linear_sum_assignment_batch(cost, return_stats=False, state=None, warm_assig
     cert = torch.zeros((B,), dtype=torch.int32, device=cost.device)
     nbytes = L.reart_lap_workspace_bytes(B, n)
     if nbytes == 0 and n <= _lib.LAP_LARGE_MAX_N:
-        return _solve_large(L, cost, src, tgt, col, cert, return_stats, state, warm_assignment or race == "warm")
+        return _solve_large(L, cost, src, tgt, col, cert, return_stats, state, warm_assignment or race == "warm", method)
     if nbytes == 0:   # n > 8192: beyond the kernels' LDS state -- the reference's host solver
         from scipy.optimize import linear_sum_assignment
 
@@ -150,19 +152,69 @@ def linear_sum_assignment_batch(cost, return_stats=False, state=None, warm_assig
     return (out, fallbacks) if return_stats else out
 
 
-def _solve_large(L, cost, src, tgt, col, cert, return_stats, state, keep_cols):
-    """4096 < n <= 8192 (``reart_lap_auction_large``): always a cold solve, one workgroup per matrix, the same certificate and
-    the same host fallback as below the limit.  A ``state`` receives the potentials and (``keep_cols``) the assignment."""
+# Sequential steps (row reduction + path searches) one matrix of a warm large re-solve may take before it is given up and solved
+# cold; 0: the library's default (LAP_LARGE_STEPS_PER_N x n + 64 in csrc/lap.hip, see there for where the multiple comes from)
+RESOLVE_LARGE_MAX_STEPS = 0
+
+
+def _solve_large(L, cost, src, tgt, col, cert, return_stats, state, keep_cols, method="paths"):
+    """4096 < n <= 8192, one workgroup per matrix, the same certificate and the same host fallback as below the limit.
+    With the potentials and the assignment of an earlier call in ``state`` (``keep_cols``, ``method="paths"``): the warm
+    re-solve ``reart_lap_resolve_large`` from them; the matrices it leaves uncertified -- a certificate that did not close
+    within its rounds, or the step limit (``RESOLVE_LARGE_MAX_STEPS``) after a jump of the costs -- are solved cold on the GPU
+    in the same call, as a sub-batch, and go to scipy only if that fails too.  Otherwise the cold solve
+    ``reart_lap_auction_large``.  A ``state`` receives the potentials, (``keep_cols``) the assignment, ``resolve_form``
+    ("jv": the warm re-solve ran, statistics in ``reart_lap_resolve``'s layout; "cold": the auction's) and ``resolve_cold``
+    (matrices of this call solved cold after a warm attempt)."""
     B, n, _ = cost.shape
-    prices = torch.zeros((B, n), dtype=torch.float64, device=cost.device)
+    dev = cost.device
+    off = ((8 * B * n + 255) // 256) * 256                    # [B][4] statistics, as in the layout below the limit
+    warm = bool(keep_cols and method == "paths" and state is not None and state.get("prices") is not None
+                and state.get("cols") is not None and tuple(state["prices"].shape) == (B, n) and tuple(state["cols"].shape) == (B, n)
+                and state["prices"].device == dev and state["cols"].device == dev and state["prices"].dtype == torch.float64
+                and state["prices"].is_contiguous())
+    stats = None
+    if warm:
+        prices = state["prices"]
+        col.copy_(state["cols"])
+        ws = _lib.workspace(L.reart_lap_resolve_large_workspace_bytes(B, n), dev)
+        rc = L.reart_lap_resolve_large(_lib.ptr(cost), B, n, int(RESOLVE_LARGE_MAX_STEPS), _lib.ptr(col), _lib.ptr(cert), _lib.ptr(prices),
+                                       _lib.ptr(prices), _lib.ptr(ws), ws.numel(), _lib.stream())
+        _lib.check(rc, "reart_lap_resolve_large")
+        cert_h = cert.cpu().numpy().copy()
+        if return_stats == "full":                            # (the workspace is shared with the cold solve below)
+            stats = ws[off:off + 16 * B].view(torch.int32).reshape(B, 4).cpu().numpy().copy()
+        todo = np.nonzero(cert_h == 0)[0]
+        n_cold = len(todo)
+    else:
+        prices = torch.zeros((B, n), dtype=torch.float64, device=dev)
+        cert_h = np.zeros((B,), np.int32)
+        todo, n_cold = np.arange(B), 0
     if state is not None:
         state["prices"] = prices
-    ws = _lib.workspace(L.reart_lap_large_workspace_bytes(B, n), cost.device)
-    off = ((8 * B * n + 255) // 256) * 256                    # [B][4] statistics, as in the layout below the limit
-    rc = L.reart_lap_auction_large(_lib.ptr(cost), _lib.ptr(src), _lib.ptr(tgt), B, n, _lib.ptr(col), _lib.ptr(cert), _lib.ptr(prices),
-                                   _lib.ptr(ws), ws.numel(), _lib.stream())
-    _lib.check(rc, "reart_lap_auction_large")
-    col_h, cert_h = col.cpu().numpy().astype(np.int64), cert.cpu().numpy()
+        state["resolve_form"] = "jv" if warm else "cold"
+        state["resolve_cold"] = n_cold
+    if len(todo):
+        whole = len(todo) == B
+        idx = None if whole else torch.from_numpy(todo).to(dev)
+        sub = lambda t: t if (whole or t is None) else t[idx].contiguous()
+        c2, k2, p2 = ((col, cert, prices) if whole else
+                      (torch.full((len(todo), n), -1, dtype=torch.int32, device=dev), torch.zeros((len(todo),), dtype=torch.int32, device=dev),
+                       torch.zeros((len(todo), n), dtype=torch.float64, device=dev)))
+        B2 = len(todo)
+        ws = _lib.workspace(L.reart_lap_large_workspace_bytes(B2, n), dev)
+        cost2, src2, tgt2 = sub(cost), sub(src), sub(tgt)
+        rc = L.reart_lap_auction_large(_lib.ptr(cost2), _lib.ptr(src2), _lib.ptr(tgt2), B2, n, _lib.ptr(c2), _lib.ptr(k2), _lib.ptr(p2),
+                                       _lib.ptr(ws), ws.numel(), _lib.stream())
+        _lib.check(rc, "reart_lap_auction_large")
+        if not whole:
+            col[idx] = c2
+            prices[idx] = p2
+        cert_h[todo] = k2.cpu().numpy()
+        if return_stats == "full" and stats is None:
+            off2 = ((8 * B2 * n + 255) // 256) * 256
+            stats = ws[off2:off2 + 16 * B2].view(torch.int32).reshape(B2, 4).cpu().numpy().copy()
+    col_h = col.cpu().numpy().astype(np.int64)
     rows = np.arange(n, dtype=np.int64)
     out, fallbacks = [], 0
     for b in range(B):
@@ -177,7 +229,7 @@ def _solve_large(L, cost, src, tgt, col, cert, return_stats, state, keep_cols):
     if state is not None and keep_cols:
         state["cols"] = col.clone()
     if return_stats == "full":
-        return out, fallbacks, ws[off:off + 16 * B].view(torch.int32).reshape(B, 4).cpu().numpy()
+        return out, fallbacks, stats
     return (out, fallbacks) if return_stats else out
 
 
