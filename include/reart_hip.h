@@ -604,6 +604,35 @@ int reart_knn_points_idx_warm(const float *p1, const float *p2, int N, int P1, i
                               int32_t *seed, float *dists, int64_t *idx, void *workspace,
                               size_t workspace_bytes, void *stream);
 
+/* The bidirectional K = 1 Chamfer sum of networks/loss.py:24-29 with its gradient as ONE call, warm-started from its own
+ * previous call (csrc/chamfer_loss.hip):
+ *   loss = sum_n ( sum_i |x_i - y_nn(i)|^2 + sum_j |y_j - x_nn'(j)|^2 ),   x [N,P1,3], y [N,P2,3] float32, P1 != P2 allowed.
+ * Both searches run in ONE launch of the exact box-pruned search of reart_knn_points_idx_warm (same distances and indices,
+ * bit for bit, ties -> lowest index in the numbering THIS entry sees, whatever the seeds hold; a caller that stores its clouds
+ * in another order, as utils.chamfer.ChamferLoss does by default, resolves ties between distinct targets in that order);
+ * one consumer launch writes everything else.
+ *   seed_xy [N,P1], seed_yx [N,P2] i32 in/out: neighbour indices of the previous call (-1, out-of-range or repeated entries
+ *       are tolerated: seeds only bound the search); they receive this call's indices;
+ *   y_unchanged != 0: y is bit for bit the y of the previous call with THIS workspace and these shapes: its SoA image and
+ *       boxes in the workspace are reused.  The first call with a workspace passes 0;
+ *   d_xy, i_xy [N,P1], d_yx, i_yx [N,P2] (each nullable): squared distances and int64 indices of both directions;
+ *   loss [1] (device): the per-point distances added in a fixed order in double, rounded once;
+ *   grad_x [N,P1,3] = 2 (x_i - y_nn(i)) + 2 sum_{j: nn'(j) = i} (x_i - y_j); grad_y [N,P2,3] (nullable) likewise for y.
+ *       The sums over j are 64-bit fixed-point sums of the float32 differences: deterministic, each addend truncated by
+ *       less than 2^-fx_bits[n];
+ *   fx_bits [N] i32 (device, out): fractional bits used for batch element n, 0..39, chosen from the clouds' boxes so that
+ *       max(P1,P2) addends of magnitude up to twice the largest |coordinate| stay below 2^62 (coordinates so large that
+ *       even 0 bits do not fit -- max(P1,P2) * max|coordinate| >= 2^60 -- are outside the contract).
+ * Non-finite coordinates give meaningless values, never an out-of-range access.  N <= 65535.  N, P1 or P2 = 0: REART_OK,
+ * nothing is launched or written.  Five launches (three when y is unchanged) and one 4-byte memset on `stream` (the counter
+ * of the loss reduction, cleared in front of every call: no call depends on how an earlier one ended, so a failed or
+ * aborted launch leaves nothing behind that a later call would trip over); no host synchronisation. */
+size_t reart_chamfer_loss_workspace_bytes(int N, int P1, int P2);
+int reart_chamfer_loss(const float *x, const float *y, int N, int P1, int P2, int32_t *seed_xy, int32_t *seed_yx,
+                       int y_unchanged, float *d_xy, int64_t *i_xy, float *d_yx, int64_t *i_yx, float *loss,
+                       float *grad_x, float *grad_y, int32_t *fx_bits, void *workspace, size_t workspace_bytes,
+                       void *stream);
+
 /* ------------------------------------------------------------------------ */
 /* Batched linear assignment (assignment loss)                               */
 /* ------------------------------------------------------------------------ */

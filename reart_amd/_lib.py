@@ -90,6 +90,8 @@ PROTOTYPES = {
     "reart_grid_knn": (c_int, [P, P, c_int, c_int, P, c_int, c_int, P, P, P, c_size_t, P]),
     "reart_knn_points_warm_workspace_bytes": (c_size_t, [c_int] * 4),
     "reart_knn_points_idx_warm": (c_int, [P, P, c_int, c_int, c_int, c_int, P, P, P, P, c_size_t, P]),
+    "reart_chamfer_loss_workspace_bytes": (c_size_t, [c_int] * 3),
+    "reart_chamfer_loss": (c_int, [P, P, c_int, c_int, c_int, P, P, c_int, P, P, P, P, P, P, P, P, P, c_size_t, P]),
     "reart_lap_workspace_bytes": (c_size_t, [c_int] * 2),
     "reart_lap_auction": (c_int, [P, c_int, c_int, P, P, P, P, P, c_size_t, P]),
     "reart_lap_auction_warm": (c_int, [P, c_int, c_int, P, P, P, P, P, c_size_t, P]),

@@ -1,0 +1,265 @@
+// reart_amd/csrc/chamfer_loss.hip -- the bidirectional K = 1 Chamfer sum of networks/loss.py:24-29 with its gradient as
+// ONE warm-started C-ABI call (reart_chamfer_loss):
+//   soa_kernel + box_kernel   SoA images and 16-target boxes of x (every call) and of y (unless the caller says y is unchanged)
+//   search                    both directions in ONE reart_search_launch (SearchArgs.k1[0..1], n1 = 2): exact, box-pruned,
+//                             bounded by the seeds of the previous call (prune.hip, unchanged)
+//   chamfer_loss_kernel       the consumer below: distances, indices, next seeds, the loss and the complete gradients
+// The consumer restates the technique of the fused step's chamfer_grad_body (step.hip): a workgroup owns a range of
+// targets, walks the records of the OTHER cloud and adds the differences of the points that chose one of its targets into
+// 64-bit fixed-point sums in LDS by integer atomics -- exact to one quantum per addend and independent of the order of
+// arrival, so the gradient is deterministic without a sort, there is no floating-point atomic and no global accumulator.
+// What differs from the step: P1 != P2, a gradient for y, a fixed-point scale per batch element taken from the boxes the
+// prep has just computed, and the loss reduced inside the same launch by the last workgroup to finish.
+#include "common.h"
+#include "internal.h"
+#include <math.h>
+
+#define CL_BS 256        // threads per consumer workgroup = targets it owns
+#define CL_IL 4          // records of the other cloud in flight per thread
+
+struct ChamferLossPlan {
+    int S, Ppad1, Ppad2, nqg, nr1, nr2, nparts;
+    size_t o_xsoa, o_ysoa, o_xbox, o_ybox, o_pd0, o_pi0, o_pd1, o_pi1, o_part, o_ticket, total;
+};
+static int chamfer_loss_plan(int N, int P1, int P2, ChamferLossPlan *p) {
+    if (N < 0 || N > 65535 || P1 < 0 || P2 < 0) return REART_ERR_INVALID_ARG;   // N is a grid dimension
+    // record and gradient offsets are 64-bit, the per-batch products below stay in int
+    if ((long long)N * ((long long)(P1 > P2 ? P1 : P2) + 2 * CL_BS) >= (1ll << 30)) return REART_ERR_INVALID_ARG;
+    const int Pmin = P1 < P2 ? P1 : P2;
+    p->S = 4;                                                    // waves per search workgroup: as reart_knn_points_idx_warm,
+    while (p->S > 1 && reart_div_up(Pmin, p->S) < 64) p->S -= 1; // from the smaller of the two target clouds (one S per launch)
+    p->Ppad1 = (int)reart_align_up((size_t)(P1 > 0 ? P1 : 1), NN_BOX);
+    p->Ppad2 = (int)reart_align_up((size_t)(P2 > 0 ? P2 : 1), NN_BOX);
+    const int q1 = reart_div_up(P1, NN_BS), q2 = reart_div_up(P2, NN_BS);
+    p->nqg = q1 > q2 ? q1 : q2;
+    p->nr1 = reart_div_up(P1, CL_BS); p->nr2 = reart_div_up(P2, CL_BS);
+    p->nparts = N * (p->nr1 + p->nr2);
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += reart_align_up(bytes, 256); return o; };
+    p->o_xsoa = take(sizeof(float) * 3 * (size_t)N * p->Ppad1);
+    p->o_ysoa = take(sizeof(float) * 3 * (size_t)N * p->Ppad2);
+    p->o_xbox = take(sizeof(float) * 8 * (size_t)N * (p->Ppad1 / NN_BOX));
+    p->o_ybox = take(sizeof(float) * 8 * (size_t)N * (p->Ppad2 / NN_BOX));
+    p->o_pd0 = take(sizeof(float) * (size_t)N * P1);
+    p->o_pi0 = take(sizeof(int) * (size_t)N * P1);
+    p->o_pd1 = take(sizeof(float) * (size_t)N * P2);
+    p->o_pi1 = take(sizeof(int) * (size_t)N * P2);
+    p->o_part = take(sizeof(double) * (size_t)(p->nparts > 0 ? p->nparts : 1));
+    p->o_ticket = take(sizeof(unsigned int));
+    p->total = off;
+    return REART_OK;
+}
+
+// float -> 64-bit fixed point with `sbits` fractional bits (0 <= sbits <= 39) by integer shifts of the mantissa: truncates
+// toward zero below 2^-sbits (error < one quantum per addend), saturates instead of shifting a bit out
+__device__ __forceinline__ long long cl_fixed_from_float(float v, int sbits) {
+    const unsigned bits = __float_as_uint(v);
+    const int ex = (int)((bits >> 23) & 0xffu);
+    const long long mant = (long long)((bits & 0x7fffffu) | (ex ? 0x800000u : 0u));
+    const int sh = (ex ? ex : 1) - 150 + sbits;
+    const long long mag = sh >= 0 ? (sh < 40 ? (mant << sh) : 0x7fffffffffffffffll) : (sh > -64 ? (mant >> (-sh)) : 0ll);
+    return (bits >> 31) ? -mag : mag;
+}
+
+struct ChamferLossArgs {
+    const float *c[2];          // the clouds [N,P[d],3]: 0 = x, 1 = y
+    const float *box[2];        // their boxes [N][Ppad[d]/NN_BOX][8]
+    const float *pd[2];         // search records of cloud d's points against the other cloud [N,P[d]]
+    const int *pi[2];
+    int P[2], nbox[2], nr[2];   // points, boxes and consumer ranges per batch element
+    float *od[2];               // nullable outputs [N,P[d]]
+    int64_t *oi[2];
+    int *seed[2];               // [N,P[d]] next seeds
+    float *grad[2];             // [N,P[d],3]; grad[1] nullable
+    int *bits;                  // [N] fractional bits of the fixed-point sums of batch element n
+    double *part;               // [N * (nr[0] + nr[1])] loss partials
+    unsigned int *ticket;       // zeroed in front of every launch
+    float *loss;
+    int N;
+};
+
+// Workgroup (r, n) of direction d owns the points r*CL_BS .. of cloud d ("own") of batch element n; o = 1 - d is the other cloud.
+//   1. scale: the largest |coordinate| of both clouds of the batch element, from their boxes
+//   2. own record: distance, index and next seed of its points, the loss terms, the first gradient term
+//   3. walk over ALL records of the other cloud: a point whose neighbour is one of its own adds (own - other) to that
+//      point's fixed-point sum in LDS
+//   4. gradient; loss partial; the last workgroup of the launch adds all partials in index order in double, rounds once
+// Every index read from a record is range-checked before it addresses memory.
+__global__ __launch_bounds__(CL_BS) void chamfer_loss_kernel(ChamferLossArgs a) {
+    __shared__ unsigned long long s_acc[CL_BS * 3];
+    __shared__ double s_red[CL_BS / REART_WAVE];
+    __shared__ float s_mx[CL_BS / REART_WAVE];
+    __shared__ int s_last;
+    const int tid = threadIdx.x, n = blockIdx.y;
+    const int d = (int)blockIdx.x < a.nr[0] ? 0 : 1, o = 1 - d;
+    const int r = (int)blockIdx.x - (d ? a.nr[0] : 0);
+    const int Pw = a.P[d], Po = a.P[o];
+    const float *own = a.c[d] + (size_t)n * Pw * 3, *oth = a.c[o] + (size_t)n * Po * 3;
+    const bool want = a.grad[d] != nullptr;      // uniform
+    for (int e = tid; e < CL_BS * 3; e += CL_BS) s_acc[e] = 0ull;
+    // ---- 1. largest finite |coordinate| of the batch element (fmaxf drops NaN; +INF padding sides are skipped)
+    float mx = 0.f;
+    for (int q = 0; q < 2; ++q) {
+        const float *bx = a.box[q] + (size_t)n * a.nbox[q] * 8;
+        for (int e = tid; e < a.nbox[q] * 8; e += CL_BS) {
+            const float v = fabsf(bx[e]);
+            if ((e & 7) < 6 && v < INFINITY) mx = fmaxf(mx, v);
+        }
+    }
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) mx = fmaxf(mx, __shfl_xor(mx, s, 64));
+    if ((tid & 63) == 0) s_mx[tid >> 6] = mx;
+    // ---- 2. own record
+    const int i = r * CL_BS + tid;
+    const bool live = i < Pw;
+    const int ic = live ? i : Pw - 1;
+    const size_t ow = (size_t)n * Pw + ic;
+    float d0 = a.pd[d][ow];
+    int j0 = a.pi[d][ow];
+    const bool ok0 = (unsigned)j0 < (unsigned)Po;
+    d0 = ok0 ? d0 : 0.0f;
+    const int j0c = ok0 ? j0 : 0;
+    float xo[3], yn[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { xo[k] = own[3 * (size_t)ic + k]; yn[k] = oth[3 * (size_t)j0c + k]; }
+    __syncthreads();
+    mx = s_mx[0];
+#pragma unroll
+    for (int w = 1; w < CL_BS / REART_WAVE; ++w) mx = fmaxf(mx, s_mx[w]);
+    // sums of at most Pmax differences, each of magnitude at most 2 mx < 2^(e+1), mx < 2^e, Pmax <= 2^c:
+    // |sum| * 2^bits < 2^(c + e + 1 + bits) <= 2^62
+    int sbits;
+    {
+        const int Pmax = Pw > Po ? Pw : Po;
+        const int c = 32 - __clz(Pmax > 1 ? Pmax - 1 : 1);                           // Pmax <= 2^c
+        const int e = (int)((__float_as_uint(mx) >> 23) & 0xffu) - 126;              // mx < 2^e (denormals: e = -126)
+        const int b = 61 - c - e;
+        sbits = b > 39 ? 39 : (b < 0 ? 0 : b);
+    }
+    if (blockIdx.x == 0 && tid == 0) a.bits[n] = sbits;
+    if (live) {
+        if (a.od[d]) a.od[d][ow] = d0;
+        if (a.oi[d]) a.oi[d][ow] = (int64_t)j0c;
+        a.seed[d][ow] = ok0 ? j0 : -1;
+    }
+    // ---- 3. the other cloud's records
+    if (want) {
+        const int *pio = a.pi[o] + (size_t)n * Po;
+        const int r0 = r * CL_BS;
+        for (int jb = tid; jb < Po; jb += CL_IL * CL_BS) {
+            int jl[CL_IL];
+#pragma unroll
+            for (int u = 0; u < CL_IL; ++u) {
+                const int j = jb + u * CL_BS;
+                const int t = pio[j < Po ? j : Po - 1];
+                // in range of the own cloud AND of this workgroup's targets, else no access at all
+                jl[u] = (j < Po && (unsigned)t < (unsigned)Pw && (unsigned)(t - r0) < (unsigned)CL_BS) ? t - r0 : -1;
+            }
+#pragma unroll
+            for (int u = 0; u < CL_IL; ++u) {
+                if (jl[u] < 0) continue;
+                const int j = jb + u * CL_BS;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const float df = own[3 * (size_t)(r0 + jl[u]) + k] - oth[3 * (size_t)j + k];
+                    atomicAdd(&s_acc[3 * jl[u] + k], (unsigned long long)cl_fixed_from_float(df, sbits));
+                }
+            }
+        }
+    }
+    __syncthreads();
+    // ---- 4. gradient and loss
+    double term = 0.0;
+    if (live) {
+        term = (double)d0;
+        if (want) {
+            const double inv2 = 2.0 * exp2((double)-sbits);
+            float *G = a.grad[d] + 3 * ow;
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                G[k] = (ok0 ? 2.0f * (xo[k] - yn[k]) : 0.0f) + (float)((double)(long long)s_acc[3 * tid + k] * inv2);
+        }
+    }
+    term = reart_wave_sum_d(term);
+    if ((tid & 63) == 0) s_red[tid >> 6] = term;
+    __syncthreads();
+    const int nbx = a.nr[0] + a.nr[1], total = nbx * a.N;
+    if (tid == 0) {
+        double t = 0.0;
+        for (int w = 0; w < CL_BS / REART_WAVE; ++w) t += s_red[w];
+        // device-scope atomics: the partial and the ticket meet in L2 whichever XCD the workgroups ran on
+        __hip_atomic_store(&a.part[(size_t)n * nbx + blockIdx.x], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned int k = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        s_last = (k == (unsigned int)(total - 1));
+    }
+    __syncthreads();
+    if (!s_last) return;
+    if (tid < 64) {
+        // fixed order: lane l adds the partials l, l + 64, ... in double, then the butterfly; one rounding to float
+        double t = 0.0;
+        for (int e = tid; e < total; e += 64) t += __hip_atomic_load(&a.part[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        t = reart_wave_sum_d(t);
+        if (tid == 0) a.loss[0] = (float)t;
+    }
+}
+
+extern "C" size_t reart_chamfer_loss_workspace_bytes(int N, int P1, int P2) {
+    ChamferLossPlan p;
+    if (N < 1 || P1 < 1 || P2 < 1) return 0;
+    return chamfer_loss_plan(N, P1, P2, &p) == REART_OK ? p.total : 0;
+}
+
+extern "C" int reart_chamfer_loss(const float *x, const float *y, int N, int P1, int P2, int32_t *seed_xy, int32_t *seed_yx,
+                                  int y_unchanged, float *d_xy, int64_t *i_xy, float *d_yx, int64_t *i_yx, float *loss,
+                                  float *grad_x, float *grad_y, int32_t *fx_bits, void *workspace, size_t workspace_bytes,
+                                  void *stream) {
+    ChamferLossPlan p;
+    int rc = chamfer_loss_plan(N, P1, P2, &p);
+    if (rc != REART_OK) return rc;
+    if (N == 0 || P1 == 0 || P2 == 0) return REART_OK;
+    if (!x || !y || !seed_xy || !seed_yx || !loss || !grad_x || !fx_bits) return REART_ERR_INVALID_ARG;
+    if (!workspace || workspace_bytes < p.total) return REART_ERR_INVALID_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    char *ws = (char *)workspace;
+    float *xsoa = (float *)(ws + p.o_xsoa), *ysoa = (float *)(ws + p.o_ysoa);
+    float *xbox = (float *)(ws + p.o_xbox), *ybox = (float *)(ws + p.o_ybox);
+    // ---- prep: x always; y's image and boxes only when y is new to this workspace.  The ticket of the consumer's last-
+    // workgroup test is cleared in front of every call (4 bytes): a call never depends on how an earlier one ended
+    if (hipMemsetAsync(ws + p.o_ticket, 0, sizeof(unsigned int), st) != hipSuccess) return REART_ERR_LAUNCH;
+    SoaArgs sa = {};
+    sa.job[0].src = x; sa.job[0].dst = xsoa; sa.job[0].P = P1; sa.job[0].Ppad = p.Ppad1;
+    sa.job[1] = sa.job[0];
+    if (!y_unchanged) { sa.job[1].src = y; sa.job[1].dst = ysoa; sa.job[1].P = P2; sa.job[1].Ppad = p.Ppad2; }
+    rc = reart_soa_launch(sa, p.Ppad1 > p.Ppad2 ? p.Ppad1 : p.Ppad2, N, y_unchanged ? 1 : 2, st);
+    if (rc != REART_OK) return rc;
+    rc = reart_boxes_launch(xsoa, N, p.Ppad1, xbox, st);
+    if (rc != REART_OK) return rc;
+    if (!y_unchanged) {
+        rc = reart_boxes_launch(ysoa, N, p.Ppad2, ybox, st);
+        if (rc != REART_OK) return rc;
+    }
+    // ---- both directions in one search launch.  The launch has one (batch, query group) count for both jobs: both take
+    // the larger number of groups; a group beyond a job's own queries repeats that job's last query and writes nothing
+    SearchArgs sr = {};
+    for (int j = 0; j < 2; ++j) {
+        KnnJob &jb = sr.k1[j];
+        jb.q = j ? y : x; jb.tsoa = j ? xsoa : ysoa; jb.boxes = j ? xbox : ybox;
+        jb.seed = j ? seed_yx : seed_xy;
+        jb.P1 = j ? P2 : P1; jb.P2 = j ? P1 : P2; jb.Ppad = j ? p.Ppad1 : p.Ppad2; jb.L = 0; jb.nqg = p.nqg;
+        jb.pd = (float *)(ws + (j ? p.o_pd1 : p.o_pd0)); jb.pi = (int *)(ws + (j ? p.o_pi1 : p.o_pi0));
+    }
+    sr.n1 = 2; sr.G = N * p.nqg; sr.S1 = sr.S3 = p.S; sr.sparse = 40; sr.share = 2;
+    rc = reart_search_launch(sr, st);
+    if (rc != REART_OK) return rc;
+    // ---- consumer
+    ChamferLossArgs a = {};
+    a.c[0] = x; a.c[1] = y; a.box[0] = xbox; a.box[1] = ybox;
+    a.pd[0] = sr.k1[0].pd; a.pd[1] = sr.k1[1].pd; a.pi[0] = sr.k1[0].pi; a.pi[1] = sr.k1[1].pi;
+    a.P[0] = P1; a.P[1] = P2; a.nbox[0] = p.Ppad1 / NN_BOX; a.nbox[1] = p.Ppad2 / NN_BOX; a.nr[0] = p.nr1; a.nr[1] = p.nr2;
+    a.od[0] = d_xy; a.od[1] = d_yx; a.oi[0] = i_xy; a.oi[1] = i_yx; a.seed[0] = seed_xy; a.seed[1] = seed_yx;
+    a.grad[0] = grad_x; a.grad[1] = grad_y; a.bits = fx_bits;
+    a.part = (double *)(ws + p.o_part); a.ticket = (unsigned int *)(ws + p.o_ticket); a.loss = loss; a.N = N;
+    hipLaunchKernelGGL(chamfer_loss_kernel, dim3(p.nr1 + p.nr2, N), dim3(CL_BS), 0, st, a);
+    REART_CHECK_LAUNCH();
+    return REART_OK;
+}

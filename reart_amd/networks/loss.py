@@ -7,7 +7,12 @@ from .. import _lib
 
 def recon_loss(pc_trans_list, pc_list, chamfer_dist):
     """Sum of the bidirectional per-point Chamfer distance (networks/loss.py:24-29).
-    pc_trans_list, pc_list: [T-1, N, 3]."""
+    pc_trans_list, pc_list: [T-1, N, 3].  A ``utils.chamfer.ChamferLoss`` as ``chamfer_dist`` returns that sum itself
+    (one warm-started native call with a fused backward)."""
+    from ..utils.chamfer import ChamferLoss
+
+    if isinstance(chamfer_dist, ChamferLoss):
+        return chamfer_dist(pc_trans_list, pc_list)
     cd = chamfer_dist(pc_trans_list, pc_list, bidirectional=True)  # [T-1, N]
     return torch.sum(cd)
 

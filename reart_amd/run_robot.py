@@ -42,8 +42,8 @@ from reart_amd.networks.loss import flow_loss, recon_loss
 from reart_amd.networks.model import BaseModel, KinematicModel
 from reart_amd.networks.pointnet2_utils import farthest_point_sample, index_points
 from reart_amd.relax import RelaxEngine
-from reart_amd.utils.chamfer import ChamferDistance
-from reart_amd.utils.flow_utils import blend_anchor_motion
+from reart_amd.utils.chamfer import ChamferDistance, ChamferLoss
+from reart_amd.utils.flow_utils import blend_anchor_motion, blend_anchor_motion_batch, pad_reference_sets
 from reart_amd.utils.model_utils import tau_cosine
 
 
@@ -459,8 +459,14 @@ class OperatorLoop:
         else:
             self.optimizer = torch.optim.Adam([p for p in model.parameters() if p.requires_grad], lr=args.trans_lr,
                                               weight_decay=args.weight_decay)
-        self.chamfer_dist = ChamferDistance()
+        # --fused_losses: the Chamfer term as one warm-started call with a fused backward (utils.chamfer.ChamferLoss), the
+        # T - 1 blends of the flow term as one call (flow_utils.blend_anchor_motion_batch, bit for bit the per-frame calls)
+        self.fused_losses = bool(getattr(args, "fused_losses", False))
+        self.chamfer_dist = ChamferLoss() if self.fused_losses else ChamferDistance()
         self.knn_flow = KNN(k=3, transpose_mode=True)
+        self.ref_batch = None
+        if self.fused_losses and args.use_flow_loss and pc_ref_list is not None:
+            self.ref_batch = pad_reference_sets(pc_ref_list, flow_ref_list)
         self.matched = None
         # the kinematic model moves the cost matrices smoothly: the previous solve's pairs and potentials start the next
         # (shortest augmenting paths, reart_lap_resolve); the base model's resampled labels make them jump: cold solves
@@ -521,11 +527,14 @@ class OperatorLoop:
             c = args.cano_idx
             with torch.no_grad():
                 comp = torch.cat((pc_trans_list[:c], cano_pc[None], pc_trans_list[c:]), dim=0)
-                blended = [blend_anchor_motion(q, r, f, self.knn_flow, return_mask=True)
-                           for q, r, f in zip(comp[:-1], self.pc_ref_list, self.flow_ref_list)]
+                if self.ref_batch is not None:
+                    gt_flow, gt_mask = blend_anchor_motion_batch(comp[:-1], *self.ref_batch, self.knn_flow, return_mask=True)
+                else:
+                    blended = [blend_anchor_motion(q, r, f, self.knn_flow, return_mask=True)
+                               for q, r, f in zip(comp[:-1], self.pc_ref_list, self.flow_ref_list)]
+                    gt_flow, gt_mask = torch.stack([b[0] for b in blended]), torch.stack([b[1] for b in blended])
             comp = torch.cat((pc_trans_list[:c], cano_pc[None], pc_trans_list[c:]), dim=0)
-            fl = args.lambda_flow * flow_loss(torch.stack([b[0] for b in blended]), comp[1:] - comp[:-1],
-                                              flow_mask_list=torch.stack([b[1] for b in blended]),
+            fl = args.lambda_flow * flow_loss(gt_flow, comp[1:] - comp[:-1], flow_mask_list=gt_mask,
                                               robust=args.use_robust_loss)
             losses["flow Loss"] = fl
             loss = loss + fl
@@ -922,6 +931,9 @@ def build_parser():
     p.add_argument("--fused_ik", action="store_true",
                    help="retarget error of a kinematic model: fit all novel poses in one launch (kinematic_utils.ik_batch) instead of "
                         "one Adam loop per pose; same optimum, not bit-equal to the default")
+    p.add_argument("--fused_losses", action="store_true",
+                   help="operator loop (the base model outside the fused engine): the Chamfer term as one warm-started call with a "
+                        "fused backward, the T-1 flow blends as one call; same losses up to the summation order of the Chamfer sum")
     return p
 
 

@@ -25,6 +25,44 @@ def blend_anchor_motion(query_loc, reference_loc, reference_flow, knn, return_ma
     return (flow, mask) if return_mask else flow
 
 
+def pad_reference_sets(reference_locs, reference_flows):
+    """The ragged per-frame reference sets of ``blend_anchor_motion_batch`` as padded tensors, built once:
+    (ref [B,nr_max,3], ref_flow [B,nr_max,3], ref_len [B] int64 or None when all sets have nr_max points)."""
+    B, nr = len(reference_locs), max(int(r.shape[0]) for r in reference_locs)
+    dev = reference_locs[0].device
+    ref = torch.zeros((B, nr, 3), dtype=torch.float32, device=dev)
+    flo = torch.zeros((B, nr, 3), dtype=torch.float32, device=dev)
+    for b, (r, f) in enumerate(zip(reference_locs, reference_flows)):
+        ref[b, :r.shape[0]] = r.float()
+        flo[b, :f.shape[0]] = f.float()
+    lens = [int(r.shape[0]) for r in reference_locs]
+    ref_len = None if min(lens) == nr else torch.tensor(lens, dtype=torch.int64, device=dev)
+    return ref, flo, ref_len
+
+
+@torch.no_grad()
+def blend_anchor_motion_batch(query_locs, ref, ref_flow, ref_len, knn, return_mask=False):
+    """The B calls ``blend_anchor_motion(query_locs[b], reference_loc[b], reference_flow[b], knn)`` of an iteration
+    (run_robot.py:194-201) as one native call (``reart_blend_anchor_motion_batch``), bit for bit the per-frame results.
+    query_locs [B,m,3]; ref, ref_flow [B,nr_max,3] and ref_len [B] int64 or None from ``pad_reference_sets``.
+    Returns flow [B,m,3] (and mask [B,m] bool)."""
+    _lib.require_gpu(query_locs, ref, ref_flow, ref_len)
+    q = query_locs.contiguous().float()
+    r, f = ref.contiguous().float(), ref_flow.contiguous().float()
+    B, nq, nr, k = q.shape[0], q.shape[1], r.shape[1], knn.k
+    if r.shape[0] != B or f.shape != r.shape:
+        raise ValueError("blend_anchor_motion_batch: query_locs [B,m,3], ref and ref_flow [B,nr_max,3]")
+    flow = torch.empty((B, nq, 3), dtype=torch.float32, device=q.device)
+    mask = torch.empty((B, nq), dtype=torch.bool, device=q.device)
+    L = _lib.lib()
+    ws = _lib.workspace(L.reart_blend_anchor_motion_batch_workspace_bytes(B, nq, nr, k), q.device)
+    euclid = 0 if getattr(knn, "_squared", False) else 1
+    rc = L.reart_blend_anchor_motion_batch(_lib.ptr(q), _lib.ptr(r), _lib.ptr(f), _lib.ptr(ref_len), B, nq, nr, k, euclid,
+                                           _lib.ptr(flow), _lib.ptr(mask), _lib.ptr(ws), ws.numel(), _lib.stream())
+    _lib.check(rc, "reart_blend_anchor_motion_batch")
+    return (flow, mask) if return_mask else flow
+
+
 @torch.no_grad()
 def find_mutual_correspondences(nns01, nns10):
     """utils/flow_utils.py:102-113: the pairs (i, nns01[i]) whose target points back at i."""
