@@ -633,6 +633,38 @@ int reart_chamfer_loss(const float *x, const float *y, int N, int P1, int P2, in
                        float *grad_x, float *grad_y, int32_t *fx_bits, void *workspace, size_t workspace_bytes,
                        void *stream);
 
+/* One iteration's flow term (run_robot.py:194-209: blend_anchor_motion of every frame pair, flow_loss, and the gradient that
+ * autograd carries through the cat and the subtraction) as ONE call over reference sets prepared once, warm-started from its own
+ * previous call (csrc/flow_term.hip).  K = 3 only.
+ *   reart_flow_term_prepare, once per run: ref, ref_flow [B,nr_max,3] padded, ref_len [B] i64 or NULL (all nr_max), every
+ *       length >= 3.  Builds the sets' searchable image (SoA rows, boxes of 16 consecutive targets), their lengths and a copy of
+ *       their flows inside `workspace`; ref and ref_flow are not read again.
+ *   reart_flow_term: comp = pc_trans[:cano_idx] | cano | pc_trans[cano_idx:] (pc_trans [B,N,3], cano [N,3], by indexing); pair f
+ *       searches comp[f] in reference set f, pred[f] = comp[f + 1] - comp[f].
+ *     order [N] i32 or NULL: the point visited at position i (a permutation; the search is fastest when consecutive positions
+ *         are neighbours in space).  Only the visiting order changes: every output below is in the caller's numbering;
+ *     seed [B,N,3] i32 in/out, by visit position: neighbour indices of the previous call (any contents: -1, out-of-range and
+ *         repeated entries are tolerated, seeds only bound the search); receives this call's;
+ *     gt_flow [B,N,3], mask [B,N] u8, dists [B,N,3], idx [B,N,3] i64 (each nullable): the blended flow and validity mask of
+ *         reart_blend_anchor_motion_batch, and the neighbours of reart_knn_cuda (K = 3), bit for bit, whatever the seeds hold
+ *         (dists squared, or their sqrt when `euclidean`; ties -> lowest index in the numbering prepare saw);
+ *     loss [1] (device, nullable) = weight x float32(sum): the per-point terms of reart_flow_loss added in a fixed order in
+ *         double and rounded once;
+ *     G [B,N,3] = d loss / d pc_trans: with gp[f] = (d flow_loss / d pred[f]) x weight, complete frame j gets
+ *         gp[j - 1] - gp[j] (a term that does not exist is dropped; the canonical frame gets none).  accumulate != 0 adds that
+ *         finished difference onto G instead of storing it.
+ * workspace_bytes must be exactly what reart_flow_term_workspace_bytes(B, N, nr_max) returned, for prepare and for every call:
+ * it is how the call knows nr_max.  B <= REART_MAX_POSE_LEN, N and nr_max <= 2^20, B x N and B x nr_max <= 2^26; beyond that the
+ * size is 0 and the entries return REART_ERR_UNSUPPORTED.  Non-finite coordinates give meaningless values, never an out-of-range
+ * access.  A call is three launches on `stream` and no memset (the first launch also clears the counters of the last: no call
+ * depends on how an earlier one ended); no host synchronisation, no buffers other than the arguments: capturable in a graph. */
+size_t reart_flow_term_workspace_bytes(int B, int N, int nr_max);
+int reart_flow_term_prepare(const float *ref, const float *ref_flow, const int64_t *ref_len, int B, int nr_max, void *workspace,
+                            size_t workspace_bytes, void *stream);
+int reart_flow_term(const float *pc_trans, const float *cano, const int32_t *order, int B, int N, int cano_idx, int euclidean,
+                    int robust, float smooth_weight, float weight, int32_t *seed, float *gt_flow, uint8_t *mask, float *dists,
+                    int64_t *idx, float *loss, float *G, int accumulate, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------ */
 /* Batched linear assignment (assignment loss)                               */
 /* ------------------------------------------------------------------------ */

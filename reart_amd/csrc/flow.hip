@@ -4,10 +4,11 @@
 // knn_cuda.KNN(k=3) call at :158) and flow_loss (networks/loss.py:10-21) with its gradient.
 #include "common.h"
 #include "internal.h"
+#include "flow_dev.h"
 #include <math.h>
 
 // ---------------------------------------------------------------------------------------
-// blend: inverse-distance blending of the k nearest anchors' flow + validity mask
+// blend: inverse-distance blending of the k nearest anchors' flow + validity mask (reart_blend_point, flow_dev.h)
 //   d[d < 1e-10] = 1e-10; w = 1/d; w /= sum w; flow = sum_k w_k f[idx_k]
 //   mask = min d <= max_k |f[idx_k]|^2  or  min d <= 0.05            (flow_utils.py:160-167)
 // ---------------------------------------------------------------------------------------
@@ -18,25 +19,10 @@ __global__ __launch_bounds__(256) void blend_kernel(const float *__restrict__ di
                                                     uint8_t *__restrict__ mask) {
     const int n = blockIdx.x * 256 + threadIdx.x;
     if (n >= nq) return;
-    float wsum = 0.f, dmin = INFINITY, fmx = -INFINITY;
-    for (int j = 0; j < k; ++j) {
-        float d = dist[(size_t)n * k + j];
-        if (d < 1e-10f) d = 1e-10f;
-        wsum += 1.0f / d;
-        dmin = fminf(dmin, d);
-        const float *f = ref_flow + 3 * idx[(size_t)n * k + j];
-        fmx = fmaxf(fmx, (f[0] * f[0] + f[1] * f[1]) + f[2] * f[2]);
-    }
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-    for (int j = 0; j < k; ++j) {
-        float d = dist[(size_t)n * k + j];
-        if (d < 1e-10f) d = 1e-10f;
-        const float wn = (1.0f / d) / wsum;
-        const float *f = ref_flow + 3 * idx[(size_t)n * k + j];
-        a0 += f[0] * wn; a1 += f[1] * wn; a2 += f[2] * wn;
-    }
+    float a0, a1, a2;
+    const bool m = reart_blend_point(dist + (size_t)n * k, idx + (size_t)n * k, k, ref_flow, a0, a1, a2);
     flow[3 * (size_t)n] = a0; flow[3 * (size_t)n + 1] = a1; flow[3 * (size_t)n + 2] = a2;
-    mask[n] = (dmin <= fmx) || (dmin <= 0.05f);
+    mask[n] = m;
 }
 
 static size_t blend_ws_layout(int nq, int nr, int k, size_t *o_d, size_t *o_i, size_t *o_knn) {
@@ -89,25 +75,10 @@ __global__ __launch_bounds__(256) void blend_batch_kernel(const float *__restric
     if (n >= nq) return;
     const size_t q = (size_t)b * nq + n;
     const float *rf = ref_flow + (size_t)b * nr_max * 3;
-    float wsum = 0.f, dmin = INFINITY, fmx = -INFINITY;
-    for (int j = 0; j < k; ++j) {
-        float d = dist[q * k + j];
-        if (d < 1e-10f) d = 1e-10f;
-        wsum += 1.0f / d;
-        dmin = fminf(dmin, d);
-        const float *f = rf + 3 * idx[q * k + j];
-        fmx = fmaxf(fmx, (f[0] * f[0] + f[1] * f[1]) + f[2] * f[2]);
-    }
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-    for (int j = 0; j < k; ++j) {
-        float d = dist[q * k + j];
-        if (d < 1e-10f) d = 1e-10f;
-        const float wn = (1.0f / d) / wsum;
-        const float *f = rf + 3 * idx[q * k + j];
-        a0 += f[0] * wn; a1 += f[1] * wn; a2 += f[2] * wn;
-    }
+    float a0, a1, a2;
+    const bool m = reart_blend_point(dist + q * k, idx + q * k, k, rf, a0, a1, a2);
     flow[3 * q] = a0; flow[3 * q + 1] = a1; flow[3 * q + 2] = a2;
-    mask[q] = (dmin <= fmx) || (dmin <= 0.05f);
+    mask[q] = m;
 }
 
 static size_t blend_batch_ws_layout(int B, int nq, int nr, int k, size_t *o_d, size_t *o_i, size_t *o_knn) {
@@ -149,16 +120,8 @@ extern "C" int reart_blend_anchor_motion_batch(const float *query, const float *
 
 // ---------------------------------------------------------------------------------------
 // flow_loss (networks/loss.py:10-21) and d loss / d pred
-//   L = sum_{b,n} [ m f + smooth (not m) |pred|^2 ],  f = |pred-gt|^2 or Huber(delta=1)
+//   L = sum_{b,n} [ m f + smooth (not m) |pred|^2 ],  f = |pred-gt|^2 or Huber(delta=1)   (reart_flow_point, flow_dev.h)
 // ---------------------------------------------------------------------------------------
-__device__ __forceinline__ float huber1(float x) {
-    const float a = fabsf(x);
-    return a <= 1.0f ? 0.5f * x * x : (a - 0.5f);
-}
-__device__ __forceinline__ float huber1_grad(float x) {
-    return fabsf(x) <= 1.0f ? x : (x > 0.f ? 1.0f : -1.0f);
-}
-
 #define FL_BS 256
 __global__ __launch_bounds__(FL_BS) void flow_loss_kernel(const float *__restrict__ gt,
                                                           const float *__restrict__ pred,
@@ -170,18 +133,7 @@ __global__ __launch_bounds__(FL_BS) void flow_loss_kernel(const float *__restric
     double acc = 0.0;
     for (size_t e = (size_t)blockIdx.x * FL_BS + threadIdx.x; e < total; e += (size_t)gridDim.x * FL_BS) {
         const bool m = mask ? (mask[e] != 0) : true;
-        float f = 0.f, sm = 0.f;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float p = pred[3 * e + c], d = p - gt[3 * e + c];
-            f += robust ? huber1(d) : d * d;
-            sm += p * p;
-            if (grad) {
-                const float gf = robust ? huber1_grad(d) : 2.0f * d;
-                grad[3 * e + c] = m ? gf : smooth * (2.0f * p);
-            }
-        }
-        acc += m ? (double)f : (double)(smooth * sm);
+        acc += reart_flow_point(gt + 3 * e, pred + 3 * e, m, robust, smooth, grad ? grad + 3 * e : nullptr);
     }
     acc = reart_wave_sum_d(acc);
     if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = acc;

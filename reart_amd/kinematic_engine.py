@@ -31,7 +31,8 @@ class KinematicEngine:
 
     def __init__(self, model, cano_pc, pc_list, cano_idx, pc_ref_list=None, flow_ref_list=None, trans_lr=1e-2,
                  weight_decay=0.0, assign_iter=0, assign_gap=5, downsample=4, lambda_assign=3e-1, lambda_flow=1.0,
-                 use_robust_loss=False, smooth_weight=1e-2, knn_squared=False, use_assign_loss=True, src_idx=None, tgt_idx=None):
+                 use_robust_loss=False, smooth_weight=1e-2, knn_squared=False, use_assign_loss=True, src_idx=None, tgt_idx=None,
+                 warm_flow=False):
         _lib.require_gpu(cano_pc, pc_list)
         self.root = hasattr(model, "root_6d") and hasattr(model, "root_t")      # networks/model.py:153-158
         self._pris = None
@@ -117,6 +118,16 @@ class KinematicEngine:
                 self._flow_pad[f, :lens[f]] = fl
             if min(lens) != self._nr_max:
                 self._ref_len = torch.tensor(lens, dtype=torch.int64, device=self.dev)
+        # warm_flow: the flow term of the fused post as one warm-started call over references prepared once (utils.flow_utils.
+        # FlowTerm) behind a reart_kin_post without its flow branch; shapes that call does not serve keep the branch
+        self._flow_term = None
+        if warm_flow and self.refs is not None and min(int(r.shape[0]) for r, _ in self.refs) >= 3:
+            from .utils.flow_utils import FlowTerm
+
+            ft = FlowTerm([r for r, _ in self.refs], [f for _, f in self.refs], self.cano_idx, weight=self.lambda_flow,
+                          robust=self.robust, smooth_weight=self.smooth, knn_squared=bool(knn_squared))
+            if ft.serves(self.pc_trans, self.cano):
+                self._flow_term = ft
         self._matched_buf = torch.zeros((self.B, n, 3), dtype=torch.float32, device=self.dev)
         self._loss3 = torch.zeros((3,), dtype=torch.float32, device=self.dev)
         self._post_ws = torch.empty((max(int(_lib.lib().reart_kin_post_workspace_bytes(self.B, self.N, self._nr_max, 3)), 256),),
@@ -342,12 +353,19 @@ class KinematicEngine:
             return self._post_expressions()
         L = _lib.lib()
         n = int(self.src_idx.numel())
+        warm = self._flow_term is not None     # then reart_kin_post runs without references: its assignment branch overwrites G
         rc = L.reart_kin_post(_lib.ptr(self.pc_trans), _lib.ptr(self.cano), self.B, self.N, self.cano_idx, _lib.ptr(self._pc_src),
                               _lib.ptr(self.tgt_pts), _lib.ptr(self.lap_state["cols"]), _lib.ptr(self._slot), n, self.lambda_assign,
-                              _lib.ptr(self._ref_pad), _lib.ptr(self._flow_pad), _lib.ptr(self._ref_len), self._nr_max, 3, self.euclid,
+                              None if warm else _lib.ptr(self._ref_pad), None if warm else _lib.ptr(self._flow_pad),
+                              None if warm else _lib.ptr(self._ref_len), self._nr_max, 3, self.euclid,
                               self.lambda_flow, int(self.robust), self.smooth, _lib.ptr(self.G), _lib.ptr(self._matched_buf),
                               _lib.ptr(self._loss3), _lib.ptr(self._post_ws), self._post_ws.numel(), _lib.stream())
         _lib.check(rc, "reart_kin_post")
+        if warm:
+            # the flow gradient is added onto the G just written, the value into losses[1], and the total is redone: replaying
+            # the pair twice around a re-solve gives the same buffers (seeds never change a result)
+            self._flow_term.add_gradient(self.pc_trans, self.cano, self.G, self._loss3[1])
+            torch.add(self._loss3[0], self._loss3[1], out=self._loss3[2])
         self.matched = self._matched_buf
         losses = {"opt assignment loss": self._loss3[0]}
         if self.refs is not None:

@@ -43,7 +43,7 @@ from reart_amd.networks.model import BaseModel, KinematicModel
 from reart_amd.networks.pointnet2_utils import farthest_point_sample, index_points
 from reart_amd.relax import RelaxEngine
 from reart_amd.utils.chamfer import ChamferDistance, ChamferLoss
-from reart_amd.utils.flow_utils import blend_anchor_motion, blend_anchor_motion_batch, pad_reference_sets
+from reart_amd.utils.flow_utils import FlowTerm, blend_anchor_motion, blend_anchor_motion_batch, pad_reference_sets
 from reart_amd.utils.model_utils import tau_cosine
 
 
@@ -460,13 +460,19 @@ class OperatorLoop:
             self.optimizer = torch.optim.Adam([p for p in model.parameters() if p.requires_grad], lr=args.trans_lr,
                                               weight_decay=args.weight_decay)
         # --fused_losses: the Chamfer term as one warm-started call with a fused backward (utils.chamfer.ChamferLoss), the
-        # T - 1 blends of the flow term as one call (flow_utils.blend_anchor_motion_batch, bit for bit the per-frame calls)
+        # T - 1 blends of the flow term as one call (flow_utils.blend_anchor_motion_batch, bit for bit the per-frame calls).
+        # --fused_flow: the whole flow term -- cat, blends, cat, subtraction, flow_loss, lambda_flow -- as one warm-started
+        # call (flow_utils.FlowTerm: the same gradient bit for bit); ``flow_term = None`` after construction puts the
+        # expressions back (what the tests compare FlowTerm with)
         self.fused_losses = bool(getattr(args, "fused_losses", False))
         self.chamfer_dist = ChamferLoss() if self.fused_losses else ChamferDistance()
         self.knn_flow = KNN(k=3, transpose_mode=True)
-        self.ref_batch = None
+        self.ref_batch = self.flow_term = None
         if self.fused_losses and args.use_flow_loss and pc_ref_list is not None:
             self.ref_batch = pad_reference_sets(pc_ref_list, flow_ref_list)
+        if getattr(args, "fused_flow", False) and args.use_flow_loss and pc_ref_list is not None:
+            self.flow_term = FlowTerm(pc_ref_list, flow_ref_list, args.cano_idx, weight=args.lambda_flow,
+                                      robust=args.use_robust_loss)
         self.matched = None
         # the kinematic model moves the cost matrices smoothly: the previous solve's pairs and potentials start the next
         # (shortest augmenting paths, reart_lap_resolve); the base model's resampled labels make them jump: cold solves
@@ -523,7 +529,11 @@ class OperatorLoop:
             rec = recon_loss(pc_trans_list, pc_list, self.chamfer_dist)
             losses["recon Loss"] = rec
             loss = loss + rec
-        if args.use_flow_loss:
+        if args.use_flow_loss and self.flow_term is not None:
+            fl = self.flow_term(pc_trans_list, cano_pc)
+            losses["flow Loss"] = fl
+            loss = loss + fl
+        elif args.use_flow_loss:
             c = args.cano_idx
             with torch.no_grad():
                 comp = torch.cat((pc_trans_list[:c], cano_pc[None], pc_trans_list[c:]), dim=0)
@@ -558,7 +568,8 @@ def make_projection_loop(args, model, cano_pc, pc_list, pc_ref_list=None, flow_r
                                flow_ref_list if args.use_flow_loss else None, trans_lr=args.trans_lr,
                                weight_decay=args.weight_decay, assign_iter=args.assign_iter, assign_gap=args.assign_gap,
                                downsample=args.downsample, lambda_assign=args.lambda_assign, lambda_flow=args.lambda_flow,
-                               use_robust_loss=args.use_robust_loss, use_assign_loss=args.use_assign_loss)
+                               use_robust_loss=args.use_robust_loss, use_assign_loss=args.use_assign_loss,
+                               warm_flow=bool(getattr(args, "fused_flow", False)))
     return OperatorLoop(args, model, cano_pc, pc_list, pc_ref_list, flow_ref_list, tau_func)
 
 
@@ -934,6 +945,10 @@ def build_parser():
     p.add_argument("--fused_losses", action="store_true",
                    help="operator loop (the base model outside the fused engine): the Chamfer term as one warm-started call with a "
                         "fused backward, the T-1 flow blends as one call; same losses up to the summation order of the Chamfer sum")
+    p.add_argument("--fused_flow", action="store_true",
+                   help="the flow term (blends, flow loss and its gradient) as one warm-started call over references prepared once "
+                        "(flow_utils.FlowTerm): in the operator loop, and in the kinematic engine (warm_flow); the same gradients bit "
+                        "for bit, the loss as one double sum")
     return p
 
 
