@@ -310,12 +310,7 @@ class KinematicEngine:
             fb, raw, changed = self._inplace.finish()
             if changed and ran:
                 behind()
-            st = raw.copy()
-            self.lap_state["commit_conflicts"] = (st[:, 1] >> 16) & 0xffff
-            st[:, 1] &= 0xffff
-            self.lap_state["backward_rounds"] = (st[:, 0] >> 21) & 0x3ff
-            st[:, 0] &= 0x1fffff
-            self.lap_state["winner"] = (st[:, 0] >> 16) & 31
+            st = lap.unpack_chain_stats(raw, self.lap_state)
         else:       # the first solve (cold), sizes outside the chain forms: the general entry (its columns are a new tensor)
             _, fb, st = lap.linear_sum_assignment_points(pc_src.contiguous(), self.tgt_pts, self.lap_state, return_stats="full", device_cols=True)
             self._g_post = None                     # a graph that reads the columns must see the new tensor
@@ -326,14 +321,15 @@ class KinematicEngine:
         self.lap_stats = st
         # sequential steps of this solve per problem (slowest, mean) and the slowest problem's search steps alone -- the latency
         # roofline of bench.py multiplies them by the measured floor of one step
-        seq = st[:, 2].astype(np.int64)
+        search, reduction, winner = lap.stats_fields(st)
+        seq = search.astype(np.int64)
         search_only = int(seq.max())
         if self.lap_state.get("resolve_form", "jv") == "jv":           # one row at a time: the row reduction's steps are sequential too
-            seq = seq + (st[:, 3].astype(np.int64) >> 8)
+            seq = seq + reduction.astype(np.int64)
         elif self.lap_state.get("backward_rounds") is not None:        # the backward growth before the searches: the same kind of step
             seq = seq + np.asarray(self.lap_state["backward_rounds"], dtype=np.int64)
         self.lap_steps_log.append((int(seq.max()), float(seq.mean()), search_only))
-        self.lap_winners += np.bincount((st[:, 0] >> 16) & 31, minlength=32)[:32]                  # raced re-solves: who finished first
+        self.lap_winners += np.bincount(winner, minlength=32)[:32]                  # raced re-solves: who finished first
         return ran
 
     def _pre(self):

@@ -118,7 +118,7 @@ class AssignmentPhase:
                                     # steps, mean row-reduction steps, most search steps, mean backward rounds)
         self.stats_raw = []         # per device-side refresh: the solver's [B,4] statistics words as written (tools/exp_tail.py)
         self.capture_guard = None   # a context-manager factory entered around the graph capture (the sweep's _CaptureGate)
-        self._have = False
+        self._have, self._inplace = False, None
 
     def _native_tables(self):
         """Index tables of the device-side refresh, in the engine's STORAGE order (built once): the stored position of every
@@ -139,86 +139,51 @@ class AssignmentPhase:
         slot[src] = torch.arange(self.n, dtype=torch.int32, device=dev)
         self._src_stored, self._slot, self._tgt_stored = src.int().contiguous(), slot, tgt.int().contiguous()
         self._src_pts = torch.empty((self.B, self.n, 3), device=dev)
-        self._cert = torch.zeros((self.B,), dtype=torch.int32, device=dev)
-        # what the host reads after a refresh -- certificate flags | tie flags | statistics -- in one pinned buffer, written by the
-        # refresh's last launch (reart_publish_words)
-        self._words_host = torch.zeros((6 * self.B,), dtype=torch.int32).pin_memory()
-        self._words_np = self._words_host.numpy()
-        self._cert_host, self._stats_host = self._words_host[:self.B], self._words_host[2 * self.B:]
 
     def _refresh_on_device(self):
         """A refresh after the first, without a host-side tensor operation: gather (reart_gather_points) -> re-solve from the
-        previous optimum in place (reart_lap_resolve_points_mc) -> pair map (reart_assign_pairs), all queued behind the
-        forward; the host waits for the B certificate flags only (an uncertified problem goes to scipy, as everywhere)."""
+        previous optimum in place (lap.InPlaceResolve) -> pair map (reart_assign_pairs), all queued behind the forward; the
+        host waits for the B certificate flags only (an uncertified problem goes to scipy, as everywhere)."""
         from reart_amd import _lib
         from reart_amd.utils import lap
 
         eng, st, L = self.eng, self.lap_state, _lib.lib()
         B, n, N = self.B, self.n, eng._assign_map.shape[1]
-        racers, arr = lap._resolve_racers(B, n), min(lap._arr_wgs(B), 256)
-        need = L.reart_lap_mc_workspace_bytes(B, n, racers)
-        if getattr(self, "_ws", None) is None or self._ws.numel() < need:
-            self._ws = torch.empty((need,), dtype=torch.uint8, device=eng.device)       # owned: a captured graph keeps its address
-            self._launches = lap.ReplayedLaunches()
-        ws, stats = self._ws, bool(self.collect_stats)
-        self._launches.guard = self.capture_guard
-        cols, prices = st["cols"], st["prices"]
-        off = ((8 * B * n + 255) // 256) * 256                            # the solver's statistics: [B][4] ints behind the potentials
-        tb = lap._tie_breaker(st, B, n, eng.device) if lap.CANONICAL_TIES else None      # --deterministic: tied optima take the canonical one
+        if self._inplace is None:
+            self._inplace = lap.InPlaceResolve(B, n, eng.device)
+        self._inplace.launches.guard = self.capture_guard
+        cols = st["cols"]
+
+        def gather():
+            _lib.check(L.reart_gather_points(_lib.ptr(eng._pc_trans), _lib.ptr(self._src_stored), B, N, n, _lib.ptr(self._src_pts), _lib.stream()),
+                       "reart_gather_points")
 
         def pairs():
             _lib.check(L.reart_assign_pairs(_lib.ptr(cols), _lib.ptr(self._slot), _lib.ptr(self._tgt_stored), B, N, n,
                                             _lib.ptr(eng._assign_map), _lib.stream()), "reart_assign_pairs")
 
-        def queue():                                                      # every launch and copy of the refresh (lap.ReplayedLaunches)
-            stream = _lib.stream()
-            _lib.check(L.reart_gather_points(_lib.ptr(eng._pc_trans), _lib.ptr(self._src_stored), B, N, n, _lib.ptr(self._src_pts), stream),
-                       "reart_gather_points")
-            if tb is not None:                                            # (flags and statistics are cleared by the call's set-up launch)
-                tb.resolve_mc(self._src_pts, self.tgt_pts, racers, arr, cols, self._cert, prices, ws, copy=False)
-            else:
-                _lib.check(L.reart_lap_resolve_points_mc(_lib.ptr(self._src_pts), _lib.ptr(self.tgt_pts), B, n, racers, arr, _lib.ptr(cols),
-                                                         _lib.ptr(self._cert), _lib.ptr(prices), _lib.ptr(prices), _lib.ptr(ws), ws.numel(), stream),
-                           "reart_lap_resolve_points_mc")
+        self._inplace.begin(self._src_pts, self.tgt_pts, st, stats=bool(self.collect_stats), before=gather, after=pairs,
+                            key=(eng._pc_trans.data_ptr(), eng._assign_map.data_ptr()))
+        fb, raw, changed = self._inplace.finish()
+        if changed:                                                       # the host rewrote columns (a tie, a host solve): the map again
             pairs()
-            _lib.check(L.reart_publish_words(_lib.ptr(self._cert), B, _lib.ptr(tb.tie if tb is not None else self._cert), B,
-                                             _lib.c_void_p(ws.data_ptr() + off) if stats else None, 4 * B if stats else 0,
-                                             _lib.c_void_p(self._words_host.data_ptr()), stream), "reart_publish_words")
-
-        self._launches.run((eng._pc_trans.data_ptr(), eng._assign_map.data_ptr(), cols.data_ptr(), prices.data_ptr(), racers, arr, stats, id(tb)), queue)
-        st["resolve_form"] = "mc"
-        torch.cuda.current_stream().synchronize()
-        bad = np.nonzero(self._words_np[:B] == 0)[0].tolist()
-        if tb is not None:
-            tb.flags_from(self._words_np[B:2 * B])
-            if tb.settle(self._src_pts, self.tgt_pts, st, skip=bad):
-                pairs()
-        self._launches.settle(queue, ok=not bad)
-        if self.collect_stats:
-            sth = self._stats_host.numpy().reshape(B, 4)
-            self.stats_raw.append(sth.copy())
-            back = (sth[:, 0] >> 21) & 0x3ff               # rounds of the backward growth: sequential steps of the same kind
-            self.stats_log.append((int((sth[:, 2] + back).max()), float(sth[:, 2].mean()), float((sth[:, 3] >> 8).mean()),
-                                   int(sth[:, 2].max()), float(back.mean())))
-        fb = 0
-        for b in bad:                                                      # certificate did not close: exact host solve
-            from scipy.optimize import linear_sum_assignment
-
-            fb += 1
-            host = linear_sum_assignment(lap.cdist(self._src_pts[b:b + 1], self.tgt_pts[b:b + 1])[0].cpu().numpy())[1]
-            lap._forget_uncertified(st, cols, b, host)
-        if fb:
-            pairs()
+        if raw is not None:
+            self.stats_raw.append(raw)
+            self._log_stats(lap.unpack_chain_stats(raw, st))
         return fb
+
+    def _log_stats(self, st):
+        from reart_amd.utils import lap
+
+        search, reduction, _ = lap.stats_fields(st)
+        back = np.asarray(self.lap_state.get("backward_rounds", np.zeros(len(st), np.int64)), dtype=np.int64)
+        self.stats_log.append((int((search + back).max()), float(search.mean()), float(reduction.mean()), int(search.max()), float(back.mean())))
 
     def _device_path(self):
         from reart_amd.utils import lap
 
-        st = self.lap_state
         return (self.NATIVE and self.eng.cfg.use_assign and self.eng.cfg.lambda_assign == ctypes.c_float(self.lam).value
-                and st.get("cols") is not None and st.get("prices") is not None and st["cols"].dtype == torch.int32
-                and tuple(st["cols"].shape) == (self.B, self.n) and lap.RESOLVE_PER_WAVE and lap.MW_NMIN <= self.n <= lap.MW_NMAX
-                and lap._arr_wgs(self.B) > 0)
+                and lap.InPlaceResolve.usable(self.lap_state, self.B, self.n))
 
     NATIVE = os.environ.get("REART_ASSIGN_NATIVE", "1") != "0"
 
@@ -246,9 +211,7 @@ class AssignmentPhase:
             ev[0].record()
         if self.collect_stats:
             cols, fb, st = linear_sum_assignment_points(src_pts, self.tgt_pts, self.lap_state, device_cols=True, return_stats="full")
-            back = np.asarray(self.lap_state.get("backward_rounds", np.zeros(len(st), np.int64)), dtype=np.int64)
-            self.stats_log.append((int((st[:, 2] + back).max()), float(st[:, 2].mean()), float((st[:, 3] >> 8).mean()),
-                                   int(st[:, 2].max()), float(back.mean())))
+            self._log_stats(st)
         else:
             cols, fb = linear_sum_assignment_points(src_pts, self.tgt_pts, self.lap_state, device_cols=True)
         if self.events is not None:
@@ -314,7 +277,7 @@ class AssignmentPhaseBatch:
         self.refreshes = self.fallbacks = 0
         self.capture_guard = None
         self.work_guard = None      # a context-manager factory entered around every refresh (the sweep's gate, reader side)
-        self._have = False
+        self._have, self._inplace = False, None
 
     def refresh(self):
         if self.work_guard is None:
@@ -322,9 +285,8 @@ class AssignmentPhaseBatch:
         else:
             with self.work_guard():
                 first = self._refresh()
-        due, self._capture_due = getattr(self, "_capture_due", None), None
-        if due is not None:                     # the refresh's own graph (lap.ReplayedLaunches): captured OUTSIDE the reader section
-            self._launches.settle(*due)         # of the gate -- a capture is its writer
+        if self._inplace is not None:           # the refresh's own graph (lap.ReplayedLaunches): captured OUTSIDE the reader section
+            self._inplace.capture()             # of the gate -- a capture is its writer
         return first
 
     def _refresh(self):
@@ -349,11 +311,8 @@ class AssignmentPhaseBatch:
     def _device_path(self):
         from reart_amd.utils import lap
 
-        st, K = self.lap_state, len(self.parts)
         return (AssignmentPhase.NATIVE and all(ph.eng.cfg.use_assign and ph.eng.cfg.lambda_assign == ctypes.c_float(self.lam).value for ph in self.parts)
-                and st.get("cols") is not None and st.get("prices") is not None and st["cols"].dtype == torch.int32
-                and tuple(st["cols"].shape) == (K * self.B, self.n) and lap.RESOLVE_PER_WAVE
-                and lap.MW_NMIN <= self.n <= lap.MW_NMAX and lap._arr_wgs(K * self.B) > 0)
+                and lap.InPlaceResolve.usable(self.lap_state, len(self.parts) * self.B, self.n))
 
     def _refresh_on_device(self):
         """AssignmentPhase._refresh_on_device for the K instances of a shared launch: K gathers into one source batch, ONE
@@ -362,24 +321,19 @@ class AssignmentPhaseBatch:
         from reart_amd.utils import lap
 
         st, L, K, B, n = self.lap_state, _lib.lib(), len(self.parts), self.B, self.n
-        dev = self.parts[0].eng.device
-        if getattr(self, "_src_all", None) is None:
+        if self._inplace is None:
             for ph in self.parts:
                 ph._native_tables()
-            self._src_all = torch.empty((K * B, n, 3), device=dev)
-            self._cert = torch.zeros((K * B,), dtype=torch.int32, device=dev)
-            self._words_host = torch.zeros((2 * K * B,), dtype=torch.int32).pin_memory()       # certificate flags | tie flags (reart_publish_words)
-            self._words_np = self._words_host.numpy()
-            self._cert_host = self._words_host[:K * B]
-        racers, arr = lap._resolve_racers(K * B, n), min(lap._arr_wgs(K * B), 256)
-        need = L.reart_lap_mc_workspace_bytes(K * B, n, racers)
-        if getattr(self, "_ws", None) is None or self._ws.numel() < need:
-            self._ws = torch.empty((need,), dtype=torch.uint8, device=dev)              # owned: a captured graph keeps its address
-            self._launches = lap.ReplayedLaunches()
-        ws = self._ws
-        self._launches.guard = self.capture_guard
-        cols, prices = st["cols"], st["prices"]
-        tb = lap._tie_breaker(st, K * B, n, dev) if lap.CANONICAL_TIES else None
+            self._src_all = torch.empty((K * B, n, 3), device=self.parts[0].eng.device)
+            self._inplace = lap.InPlaceResolve(K * B, n, self._src_all.device)
+        self._inplace.launches.guard = self.capture_guard
+        cols = st["cols"]
+
+        def gather():
+            for k, ph in enumerate(self.parts):
+                N = ph.eng._assign_map.shape[1]
+                _lib.check(L.reart_gather_points(_lib.ptr(ph.eng._pc_trans), _lib.ptr(ph._src_stored), B, N, n,
+                                                 _lib.ptr(self._src_all[k * B:]), _lib.stream()), "reart_gather_points")
 
         def pairs():
             for k, ph in enumerate(self.parts):
@@ -387,40 +341,10 @@ class AssignmentPhaseBatch:
                 _lib.check(L.reart_assign_pairs(_lib.ptr(cols[k * B:]), _lib.ptr(ph._slot), _lib.ptr(ph._tgt_stored), B, N, n,
                                                 _lib.ptr(ph.eng._assign_map), _lib.stream()), "reart_assign_pairs")
 
-        def queue():                                                      # every launch and copy of the refresh (lap.ReplayedLaunches)
-            stream = _lib.stream()
-            for k, ph in enumerate(self.parts):
-                N = ph.eng._assign_map.shape[1]
-                _lib.check(L.reart_gather_points(_lib.ptr(ph.eng._pc_trans), _lib.ptr(ph._src_stored), B, N, n,
-                                                 _lib.ptr(self._src_all[k * B:]), stream), "reart_gather_points")
-            if tb is not None:                                            # (flags are cleared by the call's set-up launch)
-                tb.resolve_mc(self._src_all, self.tgt_all, racers, arr, cols, self._cert, prices, ws, copy=False)
-            else:
-                _lib.check(L.reart_lap_resolve_points_mc(_lib.ptr(self._src_all), _lib.ptr(self.tgt_all), K * B, n, racers, arr, _lib.ptr(cols),
-                                                         _lib.ptr(self._cert), _lib.ptr(prices), _lib.ptr(prices), _lib.ptr(ws), ws.numel(), stream),
-                           "reart_lap_resolve_points_mc")
-            pairs()
-            _lib.check(L.reart_publish_words(_lib.ptr(self._cert), K * B, _lib.ptr(tb.tie if tb is not None else self._cert), K * B, None, 0,
-                                             _lib.c_void_p(self._words_host.data_ptr()), stream), "reart_publish_words")
-
         key = tuple(ph.eng._pc_trans.data_ptr() for ph in self.parts) + tuple(ph.eng._assign_map.data_ptr() for ph in self.parts)
-        self._launches.run(key + (cols.data_ptr(), prices.data_ptr(), racers, arr, id(tb)), queue)
-        st["resolve_form"] = "mc"
-        torch.cuda.current_stream().synchronize()
-        bad = np.nonzero(self._words_np[:K * B] == 0)[0].tolist()
-        if tb is not None:
-            tb.flags_from(self._words_np[K * B:])
-            if tb.settle(self._src_all, self.tgt_all, st, skip=bad):
-                pairs()
-        self._capture_due = (queue, not bad)
-        fb = 0
-        for b in bad:
-            from scipy.optimize import linear_sum_assignment
-
-            fb += 1
-            host = linear_sum_assignment(lap.cdist(self._src_all[b:b + 1], self.tgt_all[b:b + 1])[0].cpu().numpy())[1]
-            lap._forget_uncertified(st, cols, b, host)
-        if fb:
+        self._inplace.begin(self._src_all, self.tgt_all, st, before=gather, after=pairs, key=key)
+        fb, _, changed = self._inplace.finish(capture=False)              # (refresh() captures, outside the gate's reader section)
+        if changed:
             pairs()
         return fb
 

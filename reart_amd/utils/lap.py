@@ -112,8 +112,7 @@ def linear_sum_assignment_batch(cost, return_stats=False, state=None, warm_assig
     n_cold, n_racers = _racers(B, n, race_warm)
     ws = _lib.workspace(L.reart_lap_race_workspace_bytes(B, n, n_racers) if racing else nbytes, cost.device)
     if return_stats == "full":      # the statistics of a matrix nobody certified in a race are never written: report zeros
-        off = ((8 * B * n + 255) // 256) * 256
-        ws[off:off + 16 * B].zero_()
+        ws[stats_words(B, n):][:16 * B].zero_()
     tail_args = (B, n, _lib.ptr(col), _lib.ptr(cert), _lib.ptr(prices) if (state is not None and warm) else None,
                  _lib.ptr(prices) if state is not None else None, _lib.ptr(ws), ws.numel(), _lib.stream())
     if racing:
@@ -131,24 +130,11 @@ def linear_sum_assignment_batch(cost, return_stats=False, state=None, warm_assig
     else:
         rc = solve(_lib.ptr(cost), *tail_args)
     _lib.check(rc, "reart_lap_auction")
-    col_h, cert_h = col.cpu().numpy().astype(np.int64), cert.cpu().numpy()
-    rows = np.arange(n, dtype=np.int64)
-    out, fallbacks = [], 0
-    for b in range(B):
-        if cert_h[b]:
-            out.append((rows, col_h[b]))
-        else:  # certificate did not close: exact host solve for this matrix
-            from scipy.optimize import linear_sum_assignment
-
-            fallbacks += 1
-            out.append(linear_sum_assignment(cost[b].cpu().numpy()))
-            _forget_uncertified(state, col, b, out[-1][1])
+    out, fallbacks = _host_lists(col, cert.cpu().numpy(), state, cost=cost)
     if state is not None and (warm_assignment or race == "warm"):
         state["cols"] = col.clone()
     if return_stats == "full":   # per matrix: phases, auction rounds, bids, certificate rounds
-        off = ((8 * B * n + 255) // 256) * 256
-        st = ws[off:off + 16 * B].view(torch.int32).reshape(B, 4).cpu().numpy()
-        return out, fallbacks, st
+        return out, fallbacks, stats_words(B, n, ws)
     return (out, fallbacks) if return_stats else out
 
 
@@ -168,7 +154,6 @@ def _solve_large(L, cost, src, tgt, col, cert, return_stats, state, keep_cols, m
     (matrices of this call solved cold after a warm attempt)."""
     B, n, _ = cost.shape
     dev = cost.device
-    off = ((8 * B * n + 255) // 256) * 256                    # [B][4] statistics, as in the layout below the limit
     warm = bool(keep_cols and method == "paths" and state is not None and state.get("prices") is not None
                 and state.get("cols") is not None and tuple(state["prices"].shape) == (B, n) and tuple(state["cols"].shape) == (B, n)
                 and state["prices"].device == dev and state["cols"].device == dev and state["prices"].dtype == torch.float64
@@ -183,7 +168,7 @@ def _solve_large(L, cost, src, tgt, col, cert, return_stats, state, keep_cols, m
         _lib.check(rc, "reart_lap_resolve_large")
         cert_h = cert.cpu().numpy().copy()
         if return_stats == "full":                            # (the workspace is shared with the cold solve below)
-            stats = ws[off:off + 16 * B].view(torch.int32).reshape(B, 4).cpu().numpy().copy()
+            stats = stats_words(B, n, ws)                     # [B][4] statistics, as in the layout below the limit
         todo = np.nonzero(cert_h == 0)[0]
         n_cold = len(todo)
     else:
@@ -212,20 +197,8 @@ def _solve_large(L, cost, src, tgt, col, cert, return_stats, state, keep_cols, m
             prices[idx] = p2
         cert_h[todo] = k2.cpu().numpy()
         if return_stats == "full" and stats is None:
-            off2 = ((8 * B2 * n + 255) // 256) * 256
-            stats = ws[off2:off2 + 16 * B2].view(torch.int32).reshape(B2, 4).cpu().numpy().copy()
-    col_h = col.cpu().numpy().astype(np.int64)
-    rows = np.arange(n, dtype=np.int64)
-    out, fallbacks = [], 0
-    for b in range(B):
-        if cert_h[b]:
-            out.append((rows, col_h[b]))
-        else:  # certificate did not close: exact host solve for this matrix
-            from scipy.optimize import linear_sum_assignment
-
-            fallbacks += 1
-            out.append(linear_sum_assignment(cost[b].cpu().numpy()))
-            _forget_uncertified(state, col, b, out[-1][1])
+            stats = stats_words(B2, n, ws)
+    out, fallbacks = _host_lists(col, cert_h, state, cost=cost)
     if state is not None and keep_cols:
         state["cols"] = col.clone()
     if return_stats == "full":
@@ -240,6 +213,67 @@ def _forget_uncertified(state, col, b, host_cols):
     col[b] = torch.from_numpy(np.asarray(host_cols)).to(device=col.device, dtype=col.dtype)
     if state is not None and state.get("prices") is not None:
         state["prices"][b].zero_()
+
+
+def _solve_uncertified(flags, state, col, cost=None, points=None):
+    """The one host fallback: every problem whose certificate flag is 0 is solved exactly with scipy -- on ``cost[b]``, or on
+    ``cdist`` of ``points = (src, tgt)`` -- and forgotten (``_forget_uncertified``).  -> {b: (row_ind, col_ind)}"""
+    host = {}
+    for b in np.nonzero(np.asarray(flags) == 0)[0].tolist():
+        from scipy.optimize import linear_sum_assignment      # (here: a run without a fallback never loads it)
+
+        c = cost[b] if cost is not None else cdist(points[0][b:b + 1], points[1][b:b + 1])[0]
+        host[b] = linear_sum_assignment(c.cpu().numpy())
+        _forget_uncertified(state, col, b, host[b][1])
+    return host
+
+
+def _host_lists(col, flags, state, **costs):
+    """-> ([(row_ind, col_ind)] per problem like scipy's -- the certified columns, or the host's solve --, host fallbacks)"""
+    col_h = col.cpu().numpy().astype(np.int64)
+    rows = np.arange(col.shape[1], dtype=np.int64)
+    host = _solve_uncertified(flags, state, col, **costs)
+    return [host.get(b, (rows, col_h[b])) for b in range(col.shape[0])], len(host)
+
+
+def stats_words(B, n, ws=None):
+    """The solvers' statistics, [B][4] int32 words behind the potentials of a workspace: their byte offset, or (``ws`` given) a
+    host copy of them."""
+    off = ((8 * B * n + 255) // 256) * 256
+    return off if ws is None else ws[off:off + 16 * B].view(torch.int32).reshape(B, 4).cpu().numpy().copy()
+
+
+def unpack_chain_stats(raw, state):
+    """The chain forms (mw, mc) pack more into the words: -> the cleaned [B,4] copy of ``raw``; ``state`` receives what was taken
+    out -- the row reduction's redone steps (upper half of word 1), the rounds of the backward growth (lap_mc_forest_kernel:
+    sequential workgroup-wide steps like the searches') and the racer that published (bits 16-20 of word 0; released rows
+    below)."""
+    st = raw.copy()
+    state["commit_conflicts"] = (st[:, 1] >> 16) & 0xffff
+    st[:, 1] &= 0xffff
+    state["backward_rounds"] = (st[:, 0] >> 21) & 0x3ff
+    st[:, 0] &= 0x1fffff
+    state["winner"] = (st[:, 0] >> 16) & 31
+    return st
+
+
+def stats_fields(st):
+    """Per problem, from the cleaned [B,4] words of any re-solve: (search steps, row-reduction steps, the racer that
+    published)."""
+    return st[:, 2], st[:, 3] >> 8, (st[:, 0] >> 16) & 31
+
+
+def settle_refresh(words, B, state, src, tgt, tb):
+    """The host half of a device-side refresh, over the words it published (numpy int32: B certificate flags | B tie flags |
+    ...): tied problems take the canonical optimum (``tb``: the TieBreaker whose kernels ran, or None), uncertified ones go to
+    scipy.  -> (host fallbacks, columns changed on the host, the uncertified problems -- any: the state is not one to capture)"""
+    bad = np.nonzero(words[:B] == 0)[0].tolist()
+    moved = 0
+    if tb is not None:
+        tb.flags_from(words[B:2 * B])
+        moved = tb.settle(src, tgt, state, skip=bad)
+    fb = len(_solve_uncertified(words[:B], state, state["cols"], points=(src, tgt)))
+    return fb, bool(moved or fb), bad
 
 
 # --deterministic (run_robot.py): when several assignments are optimal -- exact ties of the fp32 costs, about one re-solve in a
@@ -552,8 +586,7 @@ def linear_sum_assignment_points(src, tgt, state, return_stats=False, race=True,
     racers = _resolve_racers(B, n, race)
     if return_stats == "full":      # the statistics region of the workspace (shared with other calls): zeros unless written
         nb = L.reart_lap_race_workspace_bytes(B, n, racers) if racers > 1 else L.reart_lap_workspace_bytes(B, n)
-        off = ((8 * B * n + 255) // 256) * 256
-        _lib.workspace(nb, src.device)[off:off + 16 * B].zero_()
+        _lib.workspace(nb, src.device)[stats_words(B, n):][:16 * B].zero_()
     if per_wave is None:
         per_wave = RESOLVE_PER_WAVE
     arr_wgs = int(per_wave[1]) if isinstance(per_wave, tuple) else (_arr_wgs(B) if per_wave else 0)
@@ -584,33 +617,17 @@ def linear_sum_assignment_points(src, tgt, state, return_stats=False, race=True,
     cert_h = cert.cpu().numpy()
     if tb is not None:
         tb.settle(src, tgt, state, skip=set(np.nonzero(cert_h == 0)[0].tolist()))
-    col_h = None if device_cols else col.cpu().numpy().astype(np.int64)
-    rows = np.arange(n, dtype=np.int64)
-    out, fallbacks = [], 0
-    for b in range(B):
-        if cert_h[b]:
-            if not device_cols:
-                out.append((rows, col_h[b]))
-        else:  # certificate did not close: exact host solve for this matrix
-            from scipy.optimize import linear_sum_assignment
-
-            fallbacks += 1
-            out.append(linear_sum_assignment(cdist(src[b:b + 1], tgt[b:b + 1])[0].cpu().numpy()))
-            _forget_uncertified(state, state["cols"], b, out[-1][1])
-    if device_cols and return_stats != "full":
-        return state["cols"].long(), fallbacks
+    if device_cols:
+        fallbacks = len(_solve_uncertified(cert_h, state, col, points=(src, tgt)))
+        out = col.long()
+    else:
+        out, fallbacks = _host_lists(col, cert_h, state, points=(src, tgt))
     if return_stats == "full":
-        off = ((8 * B * n + 255) // 256) * 256
-        st = ws[off:off + 16 * B].view(torch.int32).reshape(B, 4).cpu().numpy().copy()
-        if per_wave and MW_NMIN <= n <= MW_NMAX:      # the per-wave row reduction reports its redone steps in the upper half
-            state["commit_conflicts"] = (st[:, 1] >> 16) & 0xffff
-            st[:, 1] &= 0xffff
-            # ... and the rounds of the backward growth (lap_mc_forest_kernel: sequential workgroup-wide steps like the searches')
-            state["backward_rounds"] = (st[:, 0] >> 21) & 0x3ff
-            st[:, 0] &= 0x1fffff
-            state["winner"] = (st[:, 0] >> 16) & 31          # the racer that published (bits 16-20 of word 0; released rows below)
-        return (state["cols"].long() if device_cols else out), fallbacks, st
-    return (out, fallbacks) if return_stats else out
+        st = stats_words(B, n, ws)
+        if per_wave and MW_NMIN <= n <= MW_NMAX:
+            st = unpack_chain_stats(st, state)
+        return out, fallbacks, st
+    return (out, fallbacks) if (return_stats or device_cols) else out
 
 
 def spatial_order(pts):
@@ -670,7 +687,9 @@ class InPlaceResolve:
     for new source points (``reart_lap_resolve_points_mc``), so that launches which read them -- a captured graph included --
     see the new optimum at the same addresses.  The host waits for the B certificate flags (and, on request, the B x 4
     statistics words) and nothing else; an uncertified problem goes to scipy like everywhere.  ``usable(state, B, n)`` says
-    whether the state qualifies (a first call has to go through ``linear_sum_assignment_points``)."""
+    whether the state qualifies (a first call has to go through ``linear_sum_assignment_points``).  The ONE device-side refresh:
+    the kinematic engine and the assignment phases (run_robot.AssignmentPhase[Batch]) differ in the launches they let ride with
+    the solve (``begin``) and in when the graph is captured (``finish`` / ``capture``)."""
 
     def __init__(self, B, n, device):
         self.B, self.n, self.device = B, n, device
@@ -682,7 +701,7 @@ class InPlaceResolve:
         self.cert_host, self.stats_host = self.words_host[:B], self.words_host[2 * B:]
         self._ws = None                      # owned: a captured graph keeps its address
         self.launches = ReplayedLaunches()
-        self._event = self._pending = None
+        self._event = self._pending = self._due = None
 
     @staticmethod
     def usable(state, B, n):
@@ -690,11 +709,12 @@ class InPlaceResolve:
                 and state.get("prices") is not None and state["cols"].dtype == torch.int32 and tuple(state["cols"].shape) == (B, n)
                 and tuple(state["prices"].shape) == (B, n))
 
-    def _queue(self, src, tgt, cols, prices, racers, arr, stats, tb):
+    def _queue(self, src, tgt, cols, prices, racers, arr, stats, tb, before, after):
         """Every launch and copy of one refresh on the current stream (no synchronisation)."""
         L, B, n = _lib.lib(), self.B, self.n
         ws = self._ws
-        off = ((8 * B * n + 255) // 256) * 256                            # the solver's statistics: [B][4] ints behind the potentials
+        if before is not None:
+            before()
         # (the flags and the statistics start defined inside the call: its set-up launch clears them)
         if tb is not None:
             tb.resolve_mc(src, tgt, racers, arr, cols, self.cert, prices, ws, copy=False)
@@ -702,15 +722,20 @@ class InPlaceResolve:
             _lib.check(L.reart_lap_resolve_points_mc(_lib.ptr(src), _lib.ptr(tgt), B, n, racers, arr, _lib.ptr(cols), _lib.ptr(self.cert),
                                                      _lib.ptr(prices), _lib.ptr(prices), _lib.ptr(ws), ws.numel(), _lib.stream()),
                        "reart_lap_resolve_points_mc")
+        if after is not None:
+            after()
         # (without a tie check the middle words repeat the certificate flags: the layout stays put)
         _lib.check(L.reart_publish_words(_lib.ptr(self.cert), B, _lib.ptr(tb.tie if tb is not None else self.cert), B,
-                                         _lib.c_void_p(ws.data_ptr() + off) if stats else None, 4 * B if stats else 0,
+                                         _lib.c_void_p(ws.data_ptr() + stats_words(B, n)) if stats else None, 4 * B if stats else 0,
                                          _lib.c_void_p(self.words_host.data_ptr()), _lib.stream()), "reart_publish_words")
 
-    def begin(self, src, tgt, state, stats=False):
-        """Queue the refresh on the current stream and record an event behind it; nothing waits.  The caller may queue more
-        work that READS ``state["cols"]`` behind it before ``finish`` -- and must queue that work again if ``finish`` says the
-        columns changed on the host (a tied or an uncertified problem: about one refresh in a thousand)."""
+    def begin(self, src, tgt, state, stats=False, before=None, after=None, key=()):
+        """Queue the refresh on the current stream and record an event behind it; nothing waits.  ``before`` / ``after``: the
+        caller's launches that ride with the solve -- queued in front of it (they write ``src``) / between it and the published
+        words (they read the columns) -- and are captured and replayed with it; ``key``: the addresses they depend on.  The
+        caller may queue more work that READS ``state["cols"]`` behind the refresh before ``finish`` -- and must queue that work
+        (``after`` included) again if ``finish`` says the columns changed on the host (a tied or an uncertified problem: about
+        one refresh in a thousand)."""
         L, B, n = _lib.lib(), self.B, self.n
         racers, arr = _resolve_racers(B, n), min(_arr_wgs(B), 256)
         need = L.reart_lap_mc_workspace_bytes(B, n, racers)
@@ -718,8 +743,8 @@ class InPlaceResolve:
             self._ws = torch.empty((need,), dtype=torch.uint8, device=self.device)
         cols, prices = state["cols"], state["prices"]
         tb = _tie_breaker(state, B, n, self.device) if CANONICAL_TIES else None      # --deterministic: the tied problems, with the solve
-        key = (src.data_ptr(), tgt.data_ptr(), cols.data_ptr(), prices.data_ptr(), self._ws.data_ptr(), racers, arr, bool(stats), id(tb))
-        queue = lambda: self._queue(src, tgt, cols, prices, racers, arr, stats, tb)
+        key = (src.data_ptr(), tgt.data_ptr(), cols.data_ptr(), prices.data_ptr(), self._ws.data_ptr(), racers, arr, bool(stats), id(tb), *key)
+        queue = lambda: self._queue(src, tgt, cols, prices, racers, arr, stats, tb, before, after)
         self.launches.run(key, queue)
         state["resolve_form"] = "mc"
         if self._event is None:
@@ -727,27 +752,26 @@ class InPlaceResolve:
         self._event.record()
         self._pending = (src, tgt, state, stats, tb, queue)
 
-    def finish(self):
-        """Wait for the refresh queued by ``begin`` (its event, not the stream) and settle it on the host.
+    def finish(self, capture=True):
+        """Wait for the refresh queued by ``begin`` (its event, not the stream) and settle it on the host (``settle_refresh``).
+        ``capture=False``: the graph capture that may be due is left to a later ``capture()`` (a caller inside a section in which
+        it must not capture).
         -> (host fallbacks, [B,4] int32 numpy statistics as the kernel wrote them or None, columns changed on the host)"""
         (src, tgt, state, stats, tb, queue), self._pending = self._pending, None
         B = self.B
         self._event.synchronize()
-        fb, changed = 0, 0
-        words = self._words_np
-        bad = np.nonzero(words[:B] == 0)[0].tolist()
-        if tb is not None:
-            tb.flags_from(words[B:2 * B])
-            changed = tb.settle(src, tgt, state, skip=bad)
-        raw = words[2 * B:].reshape(B, 4).copy() if stats else None
-        self.launches.settle(queue, ok=not bad)
-        for b in bad:                                                     # certificate did not close: exact host solve
-            from scipy.optimize import linear_sum_assignment
+        fb, changed, bad = settle_refresh(self._words_np, B, state, src, tgt, tb)
+        raw = self._words_np[2 * B:].reshape(B, 4).copy() if stats else None
+        self._due = (queue, not bad)
+        if capture:
+            self.capture()
+        return fb, raw, changed
 
-            fb += 1
-            host = linear_sum_assignment(cdist(src[b:b + 1], tgt[b:b + 1])[0].cpu().numpy())[1]
-            _forget_uncertified(state, state["cols"], b, host)
-        return fb, raw, bool(changed or fb)
+    def capture(self):
+        """Capture the refresh's launches if the last ``finish`` left that due (a capture queues nothing)."""
+        due, self._due = self._due, None
+        if due is not None:
+            self.launches.settle(*due)
 
     def __call__(self, src, tgt, state, stats=False):
         """-> (host fallbacks, [B,4] int32 numpy statistics as the kernel wrote them or None)"""

@@ -254,3 +254,76 @@ def test_replayed_launches_state_machine(monkeypatch):
     for _ in range(4):
         r.run(("b", 1), fn); r.settle(fn)
     assert events == ["queue"] * 4 and r.graph is None
+
+
+def test_host_half_of_a_device_side_refresh(fake, monkeypatch):
+    """lap.settle_refresh (what InPlaceResolve.finish does once the words are on the host): a problem whose certificate flag is 0
+    takes scipy's optimum of cdist and zero potentials, the others keep columns and potentials bit for bit; with every flag set
+    nothing is touched."""
+    from scipy.optimize import linear_sum_assignment
+
+    from reart_amd.utils import lap
+
+    B, n = 3, 6
+    fake(B, n)
+    monkeypatch.setattr(lap, "cdist", torch.cdist)
+    rng = np.random.default_rng(4)
+    src, tgt = (torch.from_numpy(rng.uniform(0, 1, (B, n, 3)).astype(np.float32)) for _ in range(2))
+    cols0 = torch.from_numpy(np.stack([rng.permutation(n) for _ in range(B)]).astype(np.int32))
+    prices0 = torch.from_numpy(rng.uniform(0.5, 1.5, (B, n)))
+    want = linear_sum_assignment(torch.cdist(src, tgt)[1].numpy())[1]
+
+    state = {"cols": cols0.clone(), "prices": prices0.clone()}
+    words = np.array([1, 0, 1, 0, 0, 0], dtype=np.int32)              # certificate flags | tie flags
+    fb, changed, bad = lap.settle_refresh(words, B, state, src, tgt, None)
+    assert fb == 1 and changed is True and bad == [1]
+    np.testing.assert_array_equal(state["cols"][1].numpy(), want)
+    assert (state["prices"][1] == 0).all()
+    for b in (0, 2):
+        assert torch.equal(state["cols"][b], cols0[b]) and torch.equal(state["prices"][b], prices0[b])
+    assert state["cols"].dtype == torch.int32 and state["prices"].dtype == torch.float64
+
+    state = {"cols": cols0.clone(), "prices": prices0.clone()}
+    words = np.array([1, 1, 1, 0, 0, 0], dtype=np.int32)
+    fb, changed, bad = lap.settle_refresh(words, B, state, src, tgt, None)
+    assert fb == 0 and changed is False and bad == []
+    assert torch.equal(state["cols"], cols0) and torch.equal(state["prices"], prices0)
+
+
+def test_chain_statistics_are_unpacked_in_one_place():
+    """lap.unpack_chain_stats on words built at the field limits: word 0 = released | winner << 16 | backward << 21,
+    word 1 = left | conflicts << 16 -- the cleaned array and the state fields are those of the expressions written out here
+    (the ones the kinematic engine carried)."""
+    from reart_amd.utils import lap
+
+    B = 2
+    released, winner, backward = np.array([0xffff, 3]), np.array([31, 0]), np.array([0x3ff, 1])
+    left, conflicts = np.array([0xffff, 0]), np.array([0xffff, 7])
+    raw = np.zeros((B, 4), np.int64)
+    raw[:, 0] = released | winner << 16 | backward << 21
+    raw[:, 1] = left | conflicts << 16
+    raw[:, 2], raw[:, 3] = (1234, 5), (77 << 8 | 1, 9 << 8 | 1)
+    raw = raw.astype(np.uint32).view(np.int32)                         # (conflicts 0xffff sets the sign bit of word 1)
+    kept = raw.copy()
+
+    want_state = {}
+    st = raw.copy()
+    want_state["commit_conflicts"] = (st[:, 1] >> 16) & 0xffff
+    st[:, 1] &= 0xffff
+    want_state["backward_rounds"] = (st[:, 0] >> 21) & 0x3ff
+    st[:, 0] &= 0x1fffff
+    want_state["winner"] = (st[:, 0] >> 16) & 31
+
+    state = {}
+    got = lap.unpack_chain_stats(raw, state)
+    np.testing.assert_array_equal(raw, kept)                           # the words as written stay as written
+    np.testing.assert_array_equal(got, st)
+    assert got.dtype == st.dtype and sorted(state) == sorted(want_state)
+    for k, v in want_state.items():
+        np.testing.assert_array_equal(state[k], v)
+        assert state[k].dtype == v.dtype
+    # ... and the fields are the ones that were packed
+    assert state["commit_conflicts"].tolist() == conflicts.tolist() and state["backward_rounds"].tolist() == backward.tolist()
+    assert state["winner"].tolist() == winner.tolist()
+    assert (got[:, 0] & 0xffff).tolist() == released.tolist() and got[:, 1].tolist() == left.tolist()
+    assert got[:, 2:].tolist() == raw[:, 2:].tolist()

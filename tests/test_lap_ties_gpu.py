@@ -283,3 +283,86 @@ def test_a_refresh_replays_from_a_graph_and_clears_its_own_flags(dev):
             assert solve.launches.replays == (4 if lap.ReplayedLaunches.ENABLED else 0)
         finally:
             lap.CANONICAL_TIES = old
+
+
+def test_launches_that_ride_with_a_refresh(dev):
+    """lap.InPlaceResolve with a caller's launches around the solve, as the assignment phases use it: ``before`` gathers the
+    source points out of a cloud (reart_gather_points), ``after`` writes the pair map (reart_assign_pairs).  A tied problem is
+    settled on the host and reported as changed; both callables run inside the replayed graph; a capture that was put off
+    happens at the later call."""
+    from reart_amd import _lib
+    from reart_amd.utils import lap
+
+    L, B, n = _lib.lib(), 2, 512
+    N = n
+    src_h, tgt_h = _problems(dev, B, n, seed=5)
+    _plant_two_swap(src_h, tgt_h, 0, 100, 20, 400, 17)
+    g = torch.Generator(device="cpu").manual_seed(7)
+    idx = torch.randperm(N, generator=g).to(dev)
+    pc = torch.empty((B, N, 3), device=dev)
+    pc[:, idx] = torch.from_numpy(src_h).to(dev)
+    tgt = torch.from_numpy(tgt_h).to(dev)
+    tgt_index = torch.stack([torch.randperm(N, generator=g) for _ in range(B)]).to(dev)
+    idx32, tgt32 = idx.int(), tgt_index.int()
+    slot = torch.full((N,), -1, dtype=torch.int32, device=dev)
+    slot[idx] = torch.arange(n, dtype=torch.int32, device=dev)
+    src_buf = torch.full((B, n, 3), float("nan"), device=dev)
+    amap = torch.full((B, N), 12345, dtype=torch.int32, device=dev)
+    old = lap.CANONICAL_TIES
+    lap.CANONICAL_TIES = True
+    try:
+        state = {}
+        lap.linear_sum_assignment_points(pc[:, idx].contiguous(), tgt, state, device_cols=True)      # cold
+        c = state["cols"].clone()
+        c[0, 20], c[0, 100] = 400, 17                                   # the other optimum of the planted tie
+        state["cols"] = c
+        assert lap.InPlaceResolve.usable(state, B, n)
+        cols = state["cols"]
+
+        def before():
+            _lib.check(L.reart_gather_points(_lib.ptr(pc), _lib.ptr(idx32), B, N, n, _lib.ptr(src_buf), _lib.stream()), "reart_gather_points")
+
+        def after():
+            _lib.check(L.reart_assign_pairs(_lib.ptr(cols), _lib.ptr(slot), _lib.ptr(tgt32), B, N, n, _lib.ptr(amap), _lib.stream()),
+                       "reart_assign_pairs")
+
+        def refresh(solve, **kw):
+            solve.begin(src_buf, tgt, state, before=before, after=after, key=(pc.data_ptr(), amap.data_ptr()))
+            fb, raw, changed = solve.finish(**kw)
+            assert fb == 0 and raw is None and state["cols"] is cols
+            if changed:
+                after()
+            torch.cuda.synchronize()
+            return changed
+
+        def want_map():
+            want = torch.full((B, N), -1, dtype=torch.int32, device=dev)
+            want[:, idx] = tgt_index.gather(1, cols.long()).int()
+            return want
+
+        solve = lap.InPlaceResolve(B, n, dev)
+        assert refresh(solve) is True                                   # (i) the tie was settled on the host
+        assert int(cols[0, 20]) == 17 and int(cols[0, 100]) == 400
+        assert torch.equal(src_buf, pc[:, idx])
+        assert torch.equal(amap, want_map())                            # (ii) the map of the canonical columns
+        for it in range(5):                                             # (iii) the second is captured, the other four replay
+            pc.add_(1e-4)                                               # in place: same address
+            src_buf.fill_(float("nan"))
+            refresh(solve)
+            assert torch.equal(src_buf, pc[:, idx]), it                 # ``before`` ran, inside the graph too
+            assert torch.equal(amap, want_map()), it
+        assert solve.launches.replays == (4 if lap.ReplayedLaunches.ENABLED else 0)
+        late = lap.InPlaceResolve(B, n, dev)                            # (iv) the capture put off
+        for it in range(2):
+            pc.add_(1e-4)
+            refresh(late, capture=False)
+            assert late.launches.graph is None
+        late.capture()                                                  # due since the second refresh
+        assert (late.launches.graph is not None) == lap.ReplayedLaunches.ENABLED
+        late.capture()                                                  # nothing due: no second capture
+        pc.add_(1e-4)
+        refresh(late)
+        assert late.launches.replays == (1 if lap.ReplayedLaunches.ENABLED else 0)
+        assert torch.equal(src_buf, pc[:, idx]) and torch.equal(amap, want_map())
+    finally:
+        lap.CANONICAL_TIES = old
