@@ -211,7 +211,11 @@ int reart_gumbel_noise(uint64_t seed, int64_t iter, int N, int P, float *out, vo
 
 /* Backward of the above (the reference relies on autograd): G = dL/d out [B,N,3] ->
  * gradients of W1, b1, W2, proposal_6d [B,P,6], proposal_t [B,P,3].  Deterministic
- * (fixed-order chunked reductions, no atomics). */
+ * (fixed-order chunked reductions, no atomics).
+ *   hT may be NULL where the pose table fits in LDS (reart_base_path(..., 1) == 0): the kernel then re-evaluates the hidden
+ *   layer from cano, W1 and b1 with the forward's own expression -- the same gradients bit for bit, and the forward need not
+ *   save hT (the fused step does not).  With hT the call reads it as before and ignores W1 / b1.  The long path needs hT:
+ *   REART_ERR_UNSUPPORTED without it. */
 size_t reart_base_backward_workspace_bytes(int N, int P, int B, int H);
 /* Which kernels serve the model at a shape: 0 = pose table [B*P][12] (backward: also the gradient tile [B][64*3]) in LDS,
  * 1 = the long path (forward: pose rows from a table in global memory; backward: frames in LDS tiles), chosen by fit alone

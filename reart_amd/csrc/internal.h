@@ -26,7 +26,8 @@ struct BaseFwdArgs {
 
 struct BaseBwdArgs {
     const float *cano, *W2, *p6d, *pt;
-    const float *yT, *hT;
+    const float *yT, *hT;       // hT == NULL: the block kernel re-evaluates the hidden layer from cano and W1 | b1
+    const float *W1, *b1;       // read only where hT == NULL
     const int *hard_idx;
     const float *tau_ptr;
     float tau;

@@ -12,8 +12,9 @@
 // -> B rigid transforms, ~1.3 MB of HBM traffic.  All of this is launch/latency bound
 // (a few MFLOP); the layout goal is few launches and deterministic reductions.
 //
-// Internal layouts (caller-owned "saved" buffers): yT [P][N] soft assignment, hT [H][N]
-// hidden activations, hard_idx [N] sampled part.
+// Internal layouts (caller-owned "saved" buffers): yT [P][N] soft assignment, hard_idx [N] sampled part, and optionally
+// hT [H][N] hidden activations: where it is NULL the forward stores none and the backward re-evaluates them (hidden_unit,
+// model_dev.h; bwd_fill_h below) -- the fused step runs that way, 4 H N bytes less written and read per iteration.
 #include "common.h"
 #include "internal.h"
 #include "model_dev.h"
@@ -169,15 +170,16 @@ void base_fwd_kernel(Batched<BaseFwdArgs> ab) {
     // hidden layer once per point: wave g evaluates its slice of the H units for the 64 points
     {
         const int jq = (a.H + NS - 1) / NS, j0 = sid * jq, j1 = (j0 + jq < a.H) ? j0 + jq : a.H;
-        for (int j = j0; j < j1; ++j) {
-            const float4 wb = *(const float4 *)(s_wb + 4 * j);
-            float acc = wb.x * x0;
-            acc = fmaf(wb.y, x1, acc);
-            acc = fmaf(wb.z, x2, acc);
-            acc = acc + wb.w;
-            const float h = acc > 0.f ? acc : 0.f;
-            s_hh[pl * HS + j] = h;
-            if (a.hT && live) a.hT[(size_t)j * a.N + n] = h;
+        // a.hT == NULL (the fused step: the backward re-evaluates hidden_unit from the point and W1|b1): the loop holds no
+        // global store and no 64-bit address arithmetic
+        if (a.hT) {
+            for (int j = j0; j < j1; ++j) {
+                const float h = hidden_unit(*(const float4 *)(s_wb + 4 * j), x0, x1, x2);
+                s_hh[pl * HS + j] = h;
+                if (live) a.hT[(size_t)j * a.N + n] = h;
+            }
+        } else {
+            for (int j = j0; j < j1; ++j) s_hh[pl * HS + j] = hidden_unit(*(const float4 *)(s_wb + 4 * j), x0, x1, x2);
         }
     }
     __syncthreads();
@@ -432,7 +434,8 @@ __global__ __launch_bounds__(256) void rt_table_kernel(const float *__restrict__
 // load (V = 4: 16-byte rows, see the call) or one dword load (V = 1: any N, H and any 4-byte-aligned pointer).
 //   * Only the workgroup's own cw = a.cpts columns of the h / G / y tiles are loaded and stored (the tiles keep their
 //     64-point layout).  Who reads a column >= cn of a tile, all of them covered by [0, cw) or by what phase a writes:
-//       s_h   the gW2 tiles (c1) up to cn16; dp (b') at nn < a.cpts, where nn >= cn yields 0 whatever it reads;
+//       s_h   the gW2 tiles (c1) up to cn16; dp (b') at nn < a.cpts, where nn >= cn yields 0 whatever it reads
+//             (a.hT == NULL: not staged here -- bwd_fill_h writes the same columns during phase a);
 //       s_G   dw (a) and the gR|gt tiles (c2) up to cn16;
 //       s_y   phase b, rows p < P, at its lane's column (a lane >= cn16 reads column 0 instead);
 //       s_ds  phase b likewise: dw is written by phase a up to cn16; gW2 and dp up to cn16;   s_dp  gW1 / gb1 (c3) up to cn16.
@@ -540,11 +543,15 @@ __device__ __forceinline__ void bwd_stage_tiles(const BaseBwdArgs &a, int n0, in
             for (int k = 0; k < V; ++k) s_w2T[(V * jq + k) * PMAX + p] = v.v[k];
         }
     };
+    // a.hT == NULL (uniform): nobody saved the hidden activations.  The h tile is then none of this function's business:
+    // the waves that have no dw tile in phase a fill it meanwhile (bwd_fill_h below).
+    const bool reh = a.hT == nullptr;
     Pc vg[UG], vgh[UG], vgl[UG], vh[UH], vr[UR], vw[UW], vy[UY];
 #pragma unroll
     for (int u = 0; u < UG; ++u) load_g(tid + u * BS, vg[u], vgh[u], vgl[u]);
 #pragma unroll
-    for (int u = 0; u < UH; ++u) vh[u] = load_t(a.hT, tid + u * BS, nH);
+    for (int u = 0; u < UH; ++u)
+        if (!reh) vh[u] = load_t(a.hT, tid + u * BS, nH);
 #pragma unroll
     for (int u = 0; u < UR; ++u) vr[u] = load_r(tid + u * BS);
 #pragma unroll
@@ -560,7 +567,8 @@ __device__ __forceinline__ void bwd_stage_tiles(const BaseBwdArgs &a, int n0, in
 #pragma unroll
     for (int u = 0; u < UG; ++u) store_g(tid + u * BS, vg[u], vgh[u], vgl[u]);
 #pragma unroll
-    for (int u = 0; u < UH; ++u) store_t(s_h, tid + u * BS, nH, vh[u]);
+    for (int u = 0; u < UH; ++u)
+        if (!reh) store_t(s_h, tid + u * BS, nH, vh[u]);
 #pragma unroll
     for (int u = 0; u < UR; ++u) store_r(tid + u * BS, vr[u]);
 #pragma unroll
@@ -569,10 +577,43 @@ __device__ __forceinline__ void bwd_stage_tiles(const BaseBwdArgs &a, int n0, in
     for (int u = 0; u < UY; ++u) store_t(s_y, ty + u * BS, nY, vy[u]);
     if (!FAST) {   // what a larger shape has beyond the first batches
         for (int e = tid + UG * BS; e < nG; e += BS) { load_g(e, vg[0], vgh[0], vgl[0]); store_g(e, vg[0], vgh[0], vgl[0]); }
-        for (int e = tid + UH * BS; e < nH; e += BS) store_t(s_h, e, nH, load_t(a.hT, e, nH));
+        if (!reh)
+            for (int e = tid + UH * BS; e < nH; e += BS) store_t(s_h, e, nH, load_t(a.hT, e, nH));
         for (int e = tid + UR * BS; e < nR; e += BS) store_r(e, load_r(e));
         for (int e = tw + UW * BS; e < nW; e += BS) store_w(e, load_w(e));
         for (int e = ty + UY * BS; e < nY; e += BS) store_t(s_y, e, nY, load_t(a.yT, e, nY));
+    }
+}
+
+// The h tile without a saved hT: hidden_unit (model_dev.h) of the chunk's points and W1 | b1 -- the forward's very expression
+// on the forward's very operands, so the forward's bits.  Run by the `nt` threads (index it) of the waves that have no dw tile
+// in phase a, BEHIND the first barrier (the points are in s_x) and in front of the barrier that ends phase a; h is first
+// read behind the one after that (gW2 tiles, dp).  So the fill costs the critical path nothing: its one round trip to
+// the L2-hot 2 KB of W1 | b1 and its 5 flops per value hide under the matrix product of the other waves, and the tile
+// staging loses its largest load.  A piece = four columns of one row; columns cn..cpts are zero as in the staged form.
+__device__ __forceinline__ void bwd_fill_h(const BaseBwdArgs &a, int cn, int it, int nt, const float *s_x, float *s_h) {
+    const int sh = a.cpts == 64 ? 4 : (a.cpts == 32 ? 3 : 2);   // log2 of the pieces per row
+    const int np = a.H << sh;
+    constexpr int U = 2;                                        // pieces in flight per thread (H = 128, 32 points, 12 waves: one batch)
+    for (int e0 = it; e0 < np; e0 += U * nt) {
+        float4 wb[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int e = e0 + u * nt, j = (e < np ? e : e0) >> sh;
+            wb[u] = make_float4(a.W1[3 * j], a.W1[3 * j + 1], a.W1[3 * j + 2], a.b1[j]);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int e = e0 + u * nt;
+            if (e < np) {
+                const int j = e >> sh, i = (e & ((1 << sh) - 1)) << 2;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float h = hidden_unit(wb[u], s_x[3 * (i + k)], s_x[3 * (i + k) + 1], s_x[3 * (i + k) + 2]);
+                    s_h[j * BW_LD + i + k] = (i + k < cn) ? h : 0.f;
+                }
+            }
+        }
     }
 }
 
@@ -644,6 +685,10 @@ __global__ __launch_bounds__(64 * BW_WAVES) void base_bwd_block_kernel(Batched<B
         typedef float f4v __attribute__((ext_vector_type(4)));
         const int ntn = (P + 15) / 16;                       // part tiles
         const int mtn = (cn + 15) >> 4;                      // point tiles
+        if (a.hT == nullptr) {                               // uniform.  At most 8 of the 16 waves have a dw tile; the others fill h
+            const int w0 = mtn * ntn < W ? mtn * ntn : 0;
+            if (grp >= w0) bwd_fill_h(a, cn, tid - 64 * w0, 64 * (W - w0), s_x, s_h);
+        }
         for (int tile = grp; tile < mtn * ntn; tile += W) {
             const int nt = tile / mtn, mt = tile - nt * mtn;
             const int nl = 16 * mt + (lane & 15), kq = lane >> 4;          // A row (point), k within the instruction
@@ -1081,6 +1126,7 @@ int reart_base_backward_launch(const BaseBwdArgs *args, const FinalizeAdam *adam
         a.cpts = (a.cpts == 64 || a.cpts == 32 || a.cpts == 16) ? a.cpts : 32;   // points per backward workgroup
         a.nchunk = reart_div_up(a.N, a.cpts);
         if (a.N != a0.N || a.P != a0.P || a.B != a0.B || a.H != a0.H || a.cpts != a0.cpts || !workspaces[k]) return REART_ERR_INVALID_ARG;
+        if (!a.hT && (!a.W1 || !a.b1)) return REART_ERR_INVALID_ARG;   // no saved hidden layer: it is re-evaluated from W1 | b1
         char *ws = (char *)workspaces[k];
         a.partial = (float *)(ws + o_part);
         if (!a.rt_table) {
@@ -1093,8 +1139,11 @@ int reart_base_backward_launch(const BaseBwdArgs *args, const FinalizeAdam *adam
     const int path = reart_base_path(a0.P, a0.B, a0.H, 1);
     if (path < 0) return path;
     int rc;
-    if (path == 1 || force_long) rc = reart_base_backward_long_launch(ak, K, st);   // the partial rows in frame tiles
-    else {
+    if (path == 1 || force_long) {
+        for (int k = 0; k < K; ++k)
+            if (!ak[k].hT) return REART_ERR_UNSUPPORTED;                             // the long kernels read the saved hT
+        rc = reart_base_backward_long_launch(ak, K, st);                             // the partial rows in frame tiles
+    } else {
         size_t lds = base_bwd_lds(a0.P, a0.B, a0.H);
         // the hidden gradient gets a tile of its own ([H][cpts + 1]) where it fits: then the tail's roles overlap
         const size_t lds_dp = sizeof(float) * (size_t)a0.H * (a0.cpts + 1);
@@ -1130,13 +1179,13 @@ extern "C" int reart_base_backward(const float *cano, int N, int P, int B, const
                                    const int32_t *hard_idx, float tau, const float *G, float *gW1,
                                    float *gb1, float *gW2, float *g6d, float *gt, void *workspace,
                                    size_t workspace_bytes, void *stream) {
-    (void)W1; (void)b1;
     if (N <= 0 || P < 1 || B <= 0 || H < 1) return REART_ERR_INVALID_ARG;
-    if (!cano || !W2 || !prop6d || !propt || !yT || !hT || !hard_idx || !G || !gW1 || !gb1 || !gW2 ||
+    if (!cano || !W2 || !prop6d || !propt || !yT || !hard_idx || !G || !gW1 || !gb1 || !gW2 ||
         !g6d || !gt)
         return REART_ERR_INVALID_ARG;
+    if (!hT && (!W1 || !b1)) return REART_ERR_INVALID_ARG;   // hT == NULL: the hidden layer is re-evaluated from W1 | b1
     BaseBwdArgs a = {};
-    a.cano = cano; a.W2 = W2; a.p6d = prop6d; a.pt = propt; a.yT = yT; a.hT = hT;
+    a.cano = cano; a.W1 = W1; a.b1 = b1; a.W2 = W2; a.p6d = prop6d; a.pt = propt; a.yT = yT; a.hT = hT;
     a.hard_idx = hard_idx; a.tau = tau; a.G = G; a.N = N; a.P = P; a.B = B; a.H = H;
     a.gW1 = gW1; a.gb1 = gb1; a.gW2 = gW2; a.g6d = g6d; a.gt = gt;
     return reart_base_backward_launch(&a, nullptr, nullptr, &workspace, workspace_bytes, 1, (hipStream_t)stream, 0);

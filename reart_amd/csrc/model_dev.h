@@ -89,6 +89,17 @@ __device__ __forceinline__ void apply_rt(const float *Rt /*[12]: R(9) t(3)*/, fl
     }
 }
 
+// Hidden unit of the seg head (networks/blocks.py:99-118): relu(W1[j] . x + b1[j]) with wb = (W1[j][0..2], b1[j]) -- the
+// ascending-c fmaf chain of oracle/model.c, then the bias, then the relu.  The ONE definition: the forward evaluates it, and
+// the backward re-evaluates it from the same operands where no hT was saved, so both hold the same bits.
+__device__ __forceinline__ float hidden_unit(const float4 wb, float x0, float x1, float x2) {
+    float acc = wb.x * x0;
+    acc = fmaf(wb.y, x1, acc);
+    acc = fmaf(wb.z, x2, acc);
+    acc = acc + wb.w;
+    return acc > 0.f ? acc : 0.f;
+}
+
 // Philox4x32-10 counter-based generator (Salmon et al. 2011) for the in-kernel Gumbel noise
 __device__ __forceinline__ void philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
                                            uint32_t k0, uint32_t k1, uint32_t *out) {

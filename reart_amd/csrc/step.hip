@@ -25,6 +25,7 @@ struct StepPlan {
     size_t o_bc;              // Adam bias corrections of the coming step (double[2])
     size_t o_ticket;          // last-workgroup ticket of the finalize kernel (zero between launches)
     size_t o_boxY, o_boxX, o_boxR;  // AABBs of every NN_BOX targets (block-skip test)
+    int keep_hT;              // the model runs on its long path (model_long.hip), whose backward reads the saved hidden layer
     int pruned;               // box-pruned, warm-started search (prune.hip) instead of the brute-force slice kernels
     int W1, W3;               // pruned: waves (box slices) per search workgroup, K = 1 / K = 3
     int sparse;               // pruned: sparse-scan limit
@@ -88,7 +89,10 @@ static int step_plan(const reart_relax_config *c, StepPlan *p) {
     p->o_pd3 = take(off, c->use_flow ? sizeof(float) * p->S3 * BN * 3 : 0);
     p->o_pi3 = take(off, c->use_flow ? sizeof(int) * p->S3 * BN * 3 : 0);
     p->o_yT = take(off, sizeof(float) * (size_t)c->P * c->N);
-    p->o_hT = take(off, sizeof(float) * (size_t)c->H * c->N);
+    // hidden activations [H][N]: only for the long kernels.  The in-LDS backward re-evaluates them from the points and W1 | b1
+    // (hidden_unit, model_dev.h), so the forward neither writes nor the backward reads 4 H N bytes per iteration
+    p->keep_hT = (c->tune_long > 0 || reart_base_path(c->P, c->B, c->H, 0) != 0 || reart_base_path(c->P, c->B, c->H, 1) != 0) ? 1 : 0;
+    p->o_hT = take(off, p->keep_hT ? sizeof(float) * (size_t)c->H * c->N : 0);
     p->o_hard = take(off, sizeof(int) * (size_t)c->N);
     p->o_rt = take(off, sizeof(float) * 12 * (size_t)c->B * c->P);
     p->o_G = take(off, sizeof(float) * 3 * BN);
@@ -783,7 +787,7 @@ static int step_describe(const reart_relax_config *cfg, const reart_relax_buffer
     fa.pt = bufs->pt; fa.gumbel = bufs->gumbel; fa.tau_ptr = bufs->tau; fa.iter_ptr = bufs->iter;
     fa.seed = c.seed; fa.tau = 1.0f; fa.N = N; fa.P = P; fa.B = B; fa.H = H; fa.Npad = p.Npad;
     fa.out = bufs->pc_trans; fa.out_soa = (float *)(ws + p.o_xsoa); fa.seg_part = bufs->seg_part;
-    fa.trans_list = bufs->trans_list; fa.yT = (float *)(ws + p.o_yT); fa.hT = (float *)(ws + p.o_hT);
+    fa.trans_list = bufs->trans_list; fa.yT = (float *)(ws + p.o_yT); fa.hT = p.keep_hT ? (float *)(ws + p.o_hT) : nullptr;
     fa.hard_idx = (int *)(ws + p.o_hard);
     fa.rt_table = (float *)(ws + p.o_rt);
     fa.boxes = c.use_boxes ? (float *)(ws + p.o_boxX) : nullptr;
@@ -933,7 +937,7 @@ static int step_describe(const reart_relax_config *cfg, const reart_relax_buffer
     float *grads = (float *)(ws + p.o_grads);
     float *gW1 = grads, *gb1 = gW1 + 3 * H, *gW2 = gb1 + H, *g6d = gW2 + P * H, *gt = g6d + 6 * B * P;
     BaseBwdArgs &ba = L.ba;
-    ba.cano = bufs->cano; ba.W2 = bufs->W2; ba.p6d = bufs->p6d; ba.pt = bufs->pt; ba.yT = fa.yT; ba.hT = fa.hT;
+    ba.cano = bufs->cano; ba.W1 = bufs->W1; ba.b1 = bufs->b1; ba.W2 = bufs->W2; ba.p6d = bufs->p6d; ba.pt = bufs->pt; ba.yT = fa.yT; ba.hT = fa.hT;
     ba.hard_idx = fa.hard_idx; ba.tau_ptr = bufs->tau; ba.tau = 1.0f; ba.G = G; ba.rt_table = fa.rt_table;
     ba.cano_idx = c.cano_idx;
     ba.gpf = c.use_flow ? (const float *)(ws + p.o_gpf) : nullptr;
