@@ -253,6 +253,35 @@ int reart_adam_step_multi(int count, float *const *param, const float *const *gr
                           float *const *exp_avg_sq, const int *n, const float *lr, int step, float beta1, float beta2,
                           float eps, void *stream);
 
+/* torch.optim.Adam's step for a user's own loop (reart_amd.optim.Adam): up to REART_ADAM_MAX_TENSORS tensors of any sizes,
+ * of one or several parameter groups, in ONE launch.  `tensors` is a HOST array of `count` records, read at the call and
+ * passed to the kernel by value (no table is copied to device memory, nothing is allocated, no synchronisation):
+ *   param, grad, exp_avg, exp_avg_sq: device float32 arrays of n elements, 4-byte alignment suffices (a view at any element
+ *     offset); grad is read only; max_exp_avg_sq: the amsgrad maximum, or NULL for no amsgrad;
+ *   step_size = lr / (1 - beta1^step) and bias_correction2_sqrt = sqrt(1 - beta2^step) of THIS tensor's 1-based step count,
+ *     formed in double by the caller as torch's non-capturable path forms them (torch keeps `step` per parameter and lr /
+ *     weight_decay per group, hence per record); weight_decay: torch's L2 form g = fma(weight_decay, p, g) (0: none);
+ *     maximize != 0: the gradient is negated.  Neither changes `grad` in memory.
+ * Per element, float32, every rounding as written, fused where torch's multi-tensor kernels fuse (csrc/adam.hip):
+ *   m = fma(1 - beta1, g - m, m);  v = fma(1 - beta2, g * g, v * beta2);  vmax = max(vmax, v);
+ *   p = fma(-step_size, m / (sqrt(v or vmax) / bias_correction2_sqrt + eps), p)
+ * with 1 - beta1 and 1 - beta2 formed in double and rounded once.  Tensors whose betas or eps differ go into separate
+ * calls, more than REART_ADAM_MAX_TENSORS tensors into several.  A record with n = 0 touches nothing (its pointers may be
+ * NULL); a call whose records are all empty launches nothing.  Refused before any launch and without touching a device,
+ * REART_ERR_INVALID_ARG: count < 0 or above the limit, a NULL table with count > 0, n < 0, a NULL param / grad / exp_avg /
+ * exp_avg_sq with n > 0, a bias_correction2_sqrt that is not finite and positive. */
+#define REART_ADAM_MAX_TENSORS 32
+typedef struct reart_adam_tensor {
+    float *param;
+    const float *grad;
+    float *exp_avg, *exp_avg_sq;
+    float *max_exp_avg_sq;
+    int n;
+    float step_size, bias_correction2_sqrt, weight_decay;
+    int maximize;
+} reart_adam_tensor;
+int reart_adam_groups(const reart_adam_tensor *tensors, int count, double beta1, double beta2, double eps, void *stream);
+
 /* ------------------------------------------------------------------------ */
 /* Fused relaxation iteration                                                */
 /* ------------------------------------------------------------------------ */

@@ -25,6 +25,7 @@ IK_MAX_POINTS = 1024     # REART_IK_MAX_POINTS: sparse points of reart_ik_fit, h
 LAP_LARGE_MAX_N = 8192   # REART_LAP_LARGE_MAX_N: columns of reart_lap_auction_large / reart_lap_resolve_large (solver state in LDS)
 FPS_MAX_N_LDS = 12288    # REART_FPS_MAX_N_LDS: reart_fps, cloud staged in LDS
 FPS_MAX_N = 1 << 21      # REART_FPS_MAX_N: reart_fps_temp, 21-bit index in the tie key
+ADAM_MAX_TENSORS = 32    # REART_ADAM_MAX_TENSORS: records of one reart_adam_groups call, passed by value to its kernel
 
 # name -> (restype, argtypes); mirrors include/reart_hip.h one to one
 PROTOTYPES = {
@@ -60,6 +61,7 @@ PROTOTYPES = {
     "reart_rotation_6d_to_matrix": (c_int, [P, c_int, P, P]),
     "reart_adam_step": (c_int, [P, P, P, P, c_int, c_int, c_float, c_float, c_float, c_float, P]),
     "reart_adam_step_multi": (c_int, [c_int, P, P, P, P, P, P, c_int, c_float, c_float, c_float, P]),
+    "reart_adam_groups": (c_int, [P, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, P]),   # records: optim.AdamTensor
     "reart_fps": (c_int, [P, c_int, c_int, c_int, P, c_int, P, P, P]),
     "reart_fps_temp": (c_int, [P, c_int, c_int, c_int, P, c_int, P, P, P, P]),
     "reart_ball_query": (c_int, [P, P, c_int, c_int, c_int, ctypes.c_double, c_int, c_int, P, P, P]),

@@ -375,14 +375,17 @@ class OperatorLoop:
         self.args, self.model, self.cano_pc, self.pc_list = args, model, cano_pc, pc_list
         self.pc_ref_list, self.flow_ref_list, self.tau_func = pc_ref_list, flow_ref_list, tau_func
         device = cano_pc.device
+        # --fused_adam: the same optimiser with its step as one launch (reart_amd.optim.Adam; same groups, options and state)
+        Adam = torch.optim.Adam
+        if getattr(args, "fused_adam", False):
+            from reart_amd.optim import Adam
         if args.model == "base":
             seg_params = [p for p in model.seg_head.parameters() if p.requires_grad]
-            self.optimizer = torch.optim.Adam([{"params": [model.proposal_6d, model.proposal_t], "lr": args.trans_lr},
-                                               {"params": seg_params, "lr": args.seg_lr}], lr=1e-3,
-                                              weight_decay=args.weight_decay)
+            self.optimizer = Adam([{"params": [model.proposal_6d, model.proposal_t], "lr": args.trans_lr},
+                                   {"params": seg_params, "lr": args.seg_lr}], lr=1e-3, weight_decay=args.weight_decay)
         else:
-            self.optimizer = torch.optim.Adam([p for p in model.parameters() if p.requires_grad], lr=args.trans_lr,
-                                              weight_decay=args.weight_decay)
+            self.optimizer = Adam([p for p in model.parameters() if p.requires_grad], lr=args.trans_lr,
+                                  weight_decay=args.weight_decay)
         # --fused_losses: the Chamfer term as one warm-started call with a fused backward (utils.chamfer.ChamferLoss), the
         # T - 1 blends of the flow term as one call (flow_utils.blend_anchor_motion_batch, bit for bit the per-frame calls).
         # --fused_flow: the whole flow term -- cat, blends, cat, subtraction, flow_loss, lambda_flow -- as one warm-started
@@ -873,6 +876,9 @@ def build_parser():
                    help="the flow term (blends, flow loss and its gradient) as one warm-started call over references prepared once "
                         "(flow_utils.FlowTerm): in the operator loop, and in the kinematic engine (warm_flow); the same gradients bit "
                         "for bit, the loss as one double sum")
+    p.add_argument("--fused_adam", action="store_true",
+                   help="operator loop: reart_amd.optim.Adam in place of torch.optim.Adam -- the same groups, options and state, "
+                        "every parameter stepped in one launch; the same formula in float32, rounded as torch's multi-tensor kernels round it")
     return p
 
 

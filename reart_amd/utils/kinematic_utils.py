@@ -245,7 +245,8 @@ def ik(dataset, model, device, verbose=True, vis=True, save_dir=None, fused=Fals
     the whole canonical cloud lands from its ground-truth novel position (mean Euclidean distance, x100).
     ``dataset``: an object with ``[0]`` -> sample, ``pose_list``, ``cano_idx``, ``novel_pose_list`` (the mirror
     ``reart_amd.dataset.Sequence`` or the reference's).  ``vis`` / ``save_dir`` are accepted; nothing is drawn.
-    ``fused=True`` (KinematicModel only): all novel poses in one launch, ``ik_batch``; the same optimum, not the same bits."""
+    ``fused=True`` (KinematicModel only): all novel poses in one launch, ``ik_batch``; the same optimum, not the same bits.
+    ``fused_adam=True`` (with ``fused=False``; any model): passed on to ``ik_single``."""
     from ..networks.model import BaseModel
     from .dataset_utils import sparse_sample_novel_state
 
@@ -329,8 +330,9 @@ def ik_batch(model, cano_pc, novel_samples, device, n_iter=200):
     return errs.cpu().numpy().astype(np.float64), theta
 
 
-def ik_single(model, cano_pc, novel_sample, device, n_iter=200, verbose=False, **ikargs):
-    """One novel pose of ``ik`` -> (retarget error x100, fitted kwargs)."""
+def ik_single(model, cano_pc, novel_sample, device, n_iter=200, verbose=False, fused_adam=False, **ikargs):
+    """One novel pose of ``ik`` -> (retarget error x100, fitted kwargs).  ``fused_adam``: the loop's optimiser is
+    ``reart_amd.optim.Adam`` (same options and state, one launch per step) instead of ``torch.optim.Adam``."""
     from ..networks.model import BaseModel
 
     src = torch.from_numpy(np.asarray(novel_sample["sparse_cano_pc"])).float().to(device)
@@ -344,7 +346,10 @@ def ik_single(model, cano_pc, novel_sample, device, n_iter=200, verbose=False, *
     else:
         kwargs["theta_list"] = (1e-6 * torch.ones((1, model.axis_list.shape[0]), device=device)).requires_grad_(True)
         opt_list = [kwargs["theta_list"]]
-    optimizer = torch.optim.Adam(opt_list, lr=1e-1, amsgrad=True)
+    Adam = torch.optim.Adam
+    if fused_adam:
+        from ..optim import Adam
+    optimizer = Adam(opt_list, lr=1e-1, amsgrad=True)
     for _ in range(n_iter):
         pc_trans, _, _ = model(src, **kwargs)
         loss = ((pc_trans.squeeze(0) - tgt) ** 2).sum()
