@@ -666,6 +666,39 @@ int reart_chamfer_loss(const float *x, const float *y, int N, int P1, int P2, in
                        float *grad_x, float *grad_y, int32_t *fx_bits, void *workspace, size_t workspace_bytes,
                        void *stream);
 
+/* The same warm-started search with the per-point distances as the result and a backward for per-point upstream gradients
+ * (utils.chamfer.ChamferPoints): what a caller needs who weights, masks, truncates or averages the distances of
+ * utils/chamfer.py:78-123 before reducing them.  x [N,P1,3], y [N,P2,3] float32, P1 != P2 allowed; the limits, the workspace
+ * (reart_chamfer_loss_workspace_bytes, same layout: an image of y built by either entry serves the other), the seeds, the tie
+ * rule and the range checks are those of reart_chamfer_loss.
+ *   reart_chamfer_points: directions is a bit mask, 1 = x -> y, 2 = y -> x, 3 = both (anything else: REART_ERR_INVALID_ARG).
+ *       A direction that is not asked for is not searched, its outputs and seeds are left untouched and may be NULL; only the
+ *       target cloud of a searched direction is prepared (y for 1, unless y_unchanged; x for 2), so a call with directions = 2
+ *       neither needs nor builds y's image.  Distances and indices are bit for bit those of reart_knn_points_idx with K = 1
+ *       and full lengths, whatever the seeds hold.  No loss, no gradient.  Two to five launches, no memset, no host
+ *       synchronisation.
+ *   reart_chamfer_points_backward: from the clouds, the indices and distances of a forward and the upstream gradients
+ *           grad_x[n,i] = 2 g_xy[n,i] (x_i - y_{i_xy[i]}) + 2 sum_{j: i_yx[j] = i} g_yx[n,j] (x_i - y_j)
+ *           grad_y[n,j] = 2 g_yx[n,j] (y_j - x_{i_yx[j]}) + 2 sum_{i: i_xy[i] = j} g_xy[n,i] (y_j - x_i)
+ *       in ONE launch without a workspace or any state of an earlier call.  g_xy, g_yx and grad_y may each be NULL: a NULL
+ *       upstream drops that direction's terms (its i_ / d_ pointers may then be NULL too), a NULL grad_y is not computed.
+ *       Rounding: the first term is fl(fl(2 g) fl(x_i - y_nn)); every addend of a sum is fl(g_j fl(x_i - y_j)), added into a
+ *       64-bit fixed-point sum (deterministic, truncated by less than 2^-bits each); the sum is doubled, rounded to float32
+ *       once and added.  With g = 1 everywhere this is reart_chamfer_loss's arithmetic.
+ *       fx_bits [N,2] i32 (device, out, written in every call): fractional bits of the sums into x ([n,0]) and into y
+ *       ([n,1]; 0 when grad_y is NULL).  Rule: with m = max_j |g_j| sqrt(d_j) over the upstream and distances of the OTHER
+ *       cloud of batch element n (which bounds every component of an addend), m (1 + 2^-20) < 2^e and max(P1,P2) <= 2^c:
+ *       bits = clamp(61 - c - e, 0, 39), so every sum stays below 2^62.  d must be the distances that belong to the indices
+ *       (as the forward returns them); upstreams so large that 0 bits do not fit are outside the contract.
+ * Non-finite inputs give meaningless values, never an out-of-range access: every index is range-checked.  N, P1 or P2 = 0:
+ * REART_OK, nothing is launched or written. */
+int reart_chamfer_points(const float *x, const float *y, int N, int P1, int P2, int directions, int32_t *seed_xy,
+                         int32_t *seed_yx, int y_unchanged, float *d_xy, int64_t *i_xy, float *d_yx, int64_t *i_yx,
+                         void *workspace, size_t workspace_bytes, void *stream);
+int reart_chamfer_points_backward(const float *x, const float *y, int N, int P1, int P2, const int64_t *i_xy,
+                                  const int64_t *i_yx, const float *d_xy, const float *d_yx, const float *g_xy,
+                                  const float *g_yx, float *grad_x, float *grad_y, int32_t *fx_bits, void *stream);
+
 /* One iteration's flow term (run_robot.py:194-209: blend_anchor_motion of every frame pair, flow_loss, and the gradient that
  * autograd carries through the cat and the subtraction) as ONE call over reference sets prepared once, warm-started from its own
  * previous call (csrc/flow_term.hip).  K = 3 only.

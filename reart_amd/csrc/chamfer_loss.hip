@@ -263,3 +263,231 @@ extern "C" int reart_chamfer_loss(const float *x, const float *y, int N, int P1,
     REART_CHECK_LAUNCH();
     return REART_OK;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Per-point distances as outputs, per-point upstream gradients as inputs (reart_chamfer_points and
+// reart_chamfer_points_backward): the same prep, search, workspace layout and fixed-point sums as above, split at the
+// point where a caller weights, masks or averages the distances before it reduces them.
+// ---------------------------------------------------------------------------------------------
+struct ChamferPointsArgs {
+    const float *pd[2];         // search records of direction d (0: x -> y, 1: y -> x) [N,P[d]]
+    const int *pi[2];
+    int P[2], nr[2];            // points of the query cloud; consumer ranges (0: the direction was not searched)
+    float *od[2];               // [N,P[d]]
+    int64_t *oi[2];
+    int *seed[2];
+};
+
+// the own-record part of chamfer_loss_kernel alone: distance, index and next seed of every query of the searched directions
+__global__ __launch_bounds__(CL_BS) void chamfer_points_kernel(ChamferPointsArgs a) {
+    const int n = blockIdx.y;
+    const int d = (int)blockIdx.x < a.nr[0] ? 0 : 1, o = 1 - d;
+    const int i = ((int)blockIdx.x - (d ? a.nr[0] : 0)) * CL_BS + threadIdx.x;
+    if (i >= a.P[d]) return;
+    const size_t ow = (size_t)n * a.P[d] + i;
+    const float d0 = a.pd[d][ow];
+    const int j0 = a.pi[d][ow];
+    const bool ok0 = (unsigned)j0 < (unsigned)a.P[o];
+    a.od[d][ow] = ok0 ? d0 : 0.0f;
+    a.oi[d][ow] = (int64_t)(ok0 ? j0 : 0);
+    a.seed[d][ow] = ok0 ? j0 : -1;
+}
+
+extern "C" int reart_chamfer_points(const float *x, const float *y, int N, int P1, int P2, int directions, int32_t *seed_xy,
+                                    int32_t *seed_yx, int y_unchanged, float *d_xy, int64_t *i_xy, float *d_yx, int64_t *i_yx,
+                                    void *workspace, size_t workspace_bytes, void *stream) {
+    ChamferLossPlan p;
+    int rc = chamfer_loss_plan(N, P1, P2, &p);
+    if (rc != REART_OK) return rc;
+    if (directions < 1 || directions > 3) return REART_ERR_INVALID_ARG;
+    if (N == 0 || P1 == 0 || P2 == 0) return REART_OK;
+    const bool xy = (directions & 1) != 0, yx = (directions & 2) != 0;
+    if (!x || !y) return REART_ERR_INVALID_ARG;
+    if (xy && (!seed_xy || !d_xy || !i_xy)) return REART_ERR_INVALID_ARG;
+    if (yx && (!seed_yx || !d_yx || !i_yx)) return REART_ERR_INVALID_ARG;
+    if (!workspace || workspace_bytes < p.total) return REART_ERR_INVALID_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    char *ws = (char *)workspace;
+    float *xsoa = (float *)(ws + p.o_xsoa), *ysoa = (float *)(ws + p.o_ysoa);
+    float *xbox = (float *)(ws + p.o_xbox), *ybox = (float *)(ws + p.o_ybox);
+    // ---- prep: only the TARGET cloud of a searched direction needs an image: y for x -> y (unless unchanged), x for y -> x
+    const bool prep_x = yx, prep_y = xy && !y_unchanged;
+    SoaArgs sa = {};
+    int njobs = 0, maxPpad = 0;
+    if (prep_x) {
+        SoaJob &jb = sa.job[njobs++];
+        jb.src = x; jb.dst = xsoa; jb.P = P1; jb.Ppad = p.Ppad1; maxPpad = p.Ppad1;
+    }
+    if (prep_y) {
+        SoaJob &jb = sa.job[njobs++];
+        jb.src = y; jb.dst = ysoa; jb.P = P2; jb.Ppad = p.Ppad2; maxPpad = p.Ppad2 > maxPpad ? p.Ppad2 : maxPpad;
+    }
+    if (njobs) {
+        if (njobs == 1) sa.job[1] = sa.job[0];
+        rc = reart_soa_launch(sa, maxPpad, N, njobs, st);
+        if (rc != REART_OK) return rc;
+    }
+    if (prep_x) {
+        rc = reart_boxes_launch(xsoa, N, p.Ppad1, xbox, st);
+        if (rc != REART_OK) return rc;
+    }
+    if (prep_y) {
+        rc = reart_boxes_launch(ysoa, N, p.Ppad2, ybox, st);
+        if (rc != REART_OK) return rc;
+    }
+    // ---- one search launch over the asked directions.  Both: exactly the launch of reart_chamfer_loss.  One: that job alone
+    // with the query groups of its own cloud
+    const int nqg = directions == 3 ? p.nqg : reart_div_up(xy ? P1 : P2, NN_BS);
+    SearchArgs sr = {};
+    ChamferPointsArgs a = {};
+    for (int j = 0; j < 2; ++j) {
+        if (!(directions & (1 << j))) continue;
+        KnnJob &jb = sr.k1[sr.n1++];
+        jb.q = j ? y : x; jb.tsoa = j ? xsoa : ysoa; jb.boxes = j ? xbox : ybox;
+        jb.seed = j ? seed_yx : seed_xy;
+        jb.P1 = j ? P2 : P1; jb.P2 = j ? P1 : P2; jb.Ppad = j ? p.Ppad1 : p.Ppad2; jb.L = 0; jb.nqg = nqg;
+        jb.pd = (float *)(ws + (j ? p.o_pd1 : p.o_pd0)); jb.pi = (int *)(ws + (j ? p.o_pi1 : p.o_pi0));
+        a.pd[j] = jb.pd; a.pi[j] = jb.pi; a.nr[j] = j ? p.nr2 : p.nr1;
+    }
+    if (sr.n1 == 1) sr.k1[1] = sr.k1[0];
+    sr.G = N * nqg; sr.S1 = sr.S3 = p.S; sr.sparse = 40; sr.share = 2;
+    rc = reart_search_launch(sr, st);
+    if (rc != REART_OK) return rc;
+    // ---- consumer
+    a.P[0] = P1; a.P[1] = P2;
+    a.od[0] = d_xy; a.od[1] = d_yx; a.oi[0] = i_xy; a.oi[1] = i_yx; a.seed[0] = seed_xy; a.seed[1] = seed_yx;
+    hipLaunchKernelGGL(chamfer_points_kernel, dim3(a.nr[0] + a.nr[1], N), dim3(CL_BS), 0, st, a);
+    REART_CHECK_LAUNCH();
+    return REART_OK;
+}
+
+struct ChamferPointsBwdArgs {
+    const float *c[2];          // the clouds [N,P[d],3]: 0 = x, 1 = y
+    const int64_t *idx[2];      // neighbour of every point of cloud d in the other cloud [N,P[d]] (NULL with g[d])
+    const float *dd[2];         // its squared distance
+    const float *g[2];          // upstream gradient of that distance; NULL: the direction's terms are dropped
+    float *grad[2];             // [N,P[d],3]; grad[1] nullable
+    int *bits;                  // [N,2] fractional bits of the fixed-point sums into cloud d of batch element n
+    int P[2], nr[2];
+};
+
+// Workgroup (r, n) of cloud d owns the points r*CL_BS .. of cloud d ("own"); o = 1 - d is the other cloud.
+//   1. scale: m = max_j |g[o][j]| sqrt(dd[o][j]) over the other cloud of the batch element bounds every component of an
+//      addend into an own point (|own_k - other_k| <= |own - other| = sqrt(d_j) up to a few roundings)
+//   2. own term: fl(2 g[d][i]) * fl(own_i - other_nn(i))
+//   3. walk over ALL indices of the other cloud: a point j whose neighbour is one of its own adds fl(g[o][j] * fl(own - other_j))
+//      to that point's fixed-point sum in LDS
+//   4. gradient = own term + 2 * sum
+// Every index is range-checked before it addresses memory.  Nothing but the arguments is read: no workspace, no state.
+__global__ __launch_bounds__(CL_BS) void chamfer_points_bwd_kernel(ChamferPointsBwdArgs a) {
+    __shared__ unsigned long long s_acc[CL_BS * 3];
+    __shared__ float s_mx[CL_BS / REART_WAVE];
+    const int tid = threadIdx.x, n = blockIdx.y;
+    const int d = (int)blockIdx.x < a.nr[0] ? 0 : 1, o = 1 - d;
+    const int r = (int)blockIdx.x - (d ? a.nr[0] : 0);
+    const int Pw = a.P[d], Po = a.P[o];
+    const float *own = a.c[d] + (size_t)n * Pw * 3, *oth = a.c[o] + (size_t)n * Po * 3;
+    const float *gw = a.g[d], *go = a.g[o];      // uniform
+    for (int e = tid; e < CL_BS * 3; e += CL_BS) s_acc[e] = 0ull;
+    // ---- 1. scale (fmaxf drops NaN, non-finite products are skipped)
+    float mx = 0.f;
+    if (go) {
+        const float *gg = go + (size_t)n * Po, *dj = a.dd[o] + (size_t)n * Po;
+        for (int j = tid; j < Po; j += CL_BS) {
+            const float v = fabsf(gg[j]) * sqrtf(dj[j]);
+            if (v < INFINITY) mx = fmaxf(mx, v);
+        }
+    }
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) mx = fmaxf(mx, __shfl_xor(mx, s, 64));
+    if ((tid & 63) == 0) s_mx[tid >> 6] = mx;
+    // ---- 2. own term
+    const int i = r * CL_BS + tid;
+    const bool live = i < Pw;
+    const int ic = live ? i : Pw - 1;
+    const size_t ow = (size_t)n * Pw + ic;
+    float first[3] = {0.f, 0.f, 0.f};
+    if (gw) {
+        const int64_t j0 = a.idx[d][ow];
+        const bool ok0 = (unsigned long long)j0 < (unsigned long long)Po;
+        const size_t j0c = ok0 ? (size_t)j0 : 0;
+        const float g2 = 2.0f * gw[ow];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) first[k] = ok0 ? g2 * (own[3 * (size_t)ic + k] - oth[3 * j0c + k]) : 0.0f;
+    }
+    __syncthreads();
+    mx = s_mx[0];
+#pragma unroll
+    for (int w = 1; w < CL_BS / REART_WAVE; ++w) mx = fmaxf(mx, s_mx[w]);
+    // sums of at most Pmax addends, each of magnitude at most m (1 + 2^-20) < 2^e, Pmax <= 2^c:
+    // |sum| * 2^bits < 2^(c + e + bits) <= 2^61
+    int sbits;
+    {
+        const int Pmax = Pw > Po ? Pw : Po;
+        const int c = 32 - __clz(Pmax > 1 ? Pmax - 1 : 1);                           // Pmax <= 2^c
+        const float m1 = mx * 1.000002f;                                             // > m (1 + 2^-20); INF -> e = 129
+        const int e = (int)((__float_as_uint(m1) >> 23) & 0xffu) - 126;              // m1 < 2^e (denormals: e = -126)
+        const int b = 61 - c - e;
+        sbits = b > 39 ? 39 : (b < 0 ? 0 : b);
+    }
+    if (r == 0 && tid == 0) {
+        a.bits[2 * n + d] = sbits;
+        if (d == 0 && !a.grad[1]) a.bits[2 * n + 1] = 0;      // no sums into y in this call
+    }
+    // ---- 3. the other cloud's indices
+    if (go) {
+        const int64_t *io = a.idx[o] + (size_t)n * Po;
+        const float *gg = go + (size_t)n * Po;
+        const int r0 = r * CL_BS;
+        for (int jb = tid; jb < Po; jb += CL_IL * CL_BS) {
+            int jl[CL_IL];
+#pragma unroll
+            for (int u = 0; u < CL_IL; ++u) {
+                const int j = jb + u * CL_BS;
+                const int64_t t = io[j < Po ? j : Po - 1];
+                // in range of the own cloud AND of this workgroup's targets, else no access at all
+                jl[u] = (j < Po && (unsigned long long)t < (unsigned long long)Pw &&
+                         (unsigned long long)(t - r0) < (unsigned long long)CL_BS) ? (int)(t - r0) : -1;
+            }
+#pragma unroll
+            for (int u = 0; u < CL_IL; ++u) {
+                if (jl[u] < 0) continue;
+                const int j = jb + u * CL_BS;
+                const float gj = gg[j];
+                if (gj == 0.0f) continue;        // a masked point adds nothing
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const float df = own[3 * (size_t)(r0 + jl[u]) + k] - oth[3 * (size_t)j + k];
+                    atomicAdd(&s_acc[3 * jl[u] + k], (unsigned long long)cl_fixed_from_float(gj * df, sbits));
+                }
+            }
+        }
+    }
+    __syncthreads();
+    // ---- 4. gradient
+    if (live) {
+        const double inv2 = 2.0 * exp2((double)-sbits);
+        float *G = a.grad[d] + 3 * ow;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) G[k] = first[k] + (float)((double)(long long)s_acc[3 * tid + k] * inv2);
+    }
+}
+
+extern "C" int reart_chamfer_points_backward(const float *x, const float *y, int N, int P1, int P2, const int64_t *i_xy,
+                                             const int64_t *i_yx, const float *d_xy, const float *d_yx, const float *g_xy,
+                                             const float *g_yx, float *grad_x, float *grad_y, int32_t *fx_bits, void *stream) {
+    ChamferLossPlan p;
+    const int rc = chamfer_loss_plan(N, P1, P2, &p);
+    if (rc != REART_OK) return rc;
+    if (N == 0 || P1 == 0 || P2 == 0) return REART_OK;
+    if (!x || !y || !grad_x || !fx_bits) return REART_ERR_INVALID_ARG;
+    if (g_xy && (!i_xy || !d_xy)) return REART_ERR_INVALID_ARG;
+    if (g_yx && (!i_yx || !d_yx)) return REART_ERR_INVALID_ARG;
+    ChamferPointsBwdArgs a = {};
+    a.c[0] = x; a.c[1] = y; a.idx[0] = i_xy; a.idx[1] = i_yx; a.dd[0] = d_xy; a.dd[1] = d_yx; a.g[0] = g_xy; a.g[1] = g_yx;
+    a.grad[0] = grad_x; a.grad[1] = grad_y; a.bits = fx_bits;
+    a.P[0] = P1; a.P[1] = P2; a.nr[0] = p.nr1; a.nr[1] = grad_y ? p.nr2 : 0;
+    hipLaunchKernelGGL(chamfer_points_bwd_kernel, dim3(a.nr[0] + a.nr[1], N), dim3(CL_BS), 0, (hipStream_t)stream, a);
+    REART_CHECK_LAUNCH();
+    return REART_OK;
+}

@@ -4,6 +4,10 @@ knn_gather) over the HIP K-NN kernels.
 Same names, argument meaning, return shapes and error behaviour as the reference module
 (``utils/chamfer.py:20-337``); the native calls at ``:174`` and ``:206-208`` go to
 ``reart_amd.chamferdist_C`` instead of ``chamferdist._C``.
+
+Beyond the reference: the warm-started operators ``ChamferLoss`` (the bidirectional sum with a fused backward),
+``ChamferPoints`` (the per-point distances with a backward for per-point upstream gradients) and ``WarmChamferDistance``
+(``ChamferDistance``'s interface over a ``ChamferPoints``).
 """
 import warnings
 from collections import namedtuple
@@ -89,8 +93,9 @@ class ChamferDistance(torch.nn.Module):
     block is commented out, utils/chamfer.py:104-117): the result has shape [B, P].
     """
 
-    def forward(self, source_cloud, target_cloud, bidirectional=False, reverse=False,
-                reduction="mean", return_index=False):
+    @staticmethod
+    def _check(source_cloud, target_cloud, bidirectional, reverse, reduction):
+        """The reference's validation (utils/chamfer.py:34-76), shared with ``WarmChamferDistance`` -> (bs, ns, bt, nt)."""
         for cloud in (source_cloud, target_cloud):
             if not isinstance(cloud, torch.Tensor):
                 raise TypeError("Expected input type torch.Tensor. Got {} instead".format(type(cloud)))
@@ -109,14 +114,11 @@ class ChamferDistance(torch.nn.Module):
             warnings.warn("Both bidirectional and reverse set to True. bidirectional behavior takes precedence.")
         if reduction not in ("sum", "mean"):
             raise ValueError('Reduction must either be "sum" or "mean".')
+        return bs, ns, bt, nt
 
-        len_s = torch.full((bs,), ns, dtype=torch.long, device=source_cloud.device)
-        len_t = torch.full((bt,), nt, dtype=torch.long, device=target_cloud.device)
-        fwd = knn_points(source_cloud, target_cloud, lengths1=len_s, lengths2=len_t, K=1)
-        d_fwd, i_fwd = fwd.dists[..., 0], fwd.idx[..., 0]
-        if reverse or bidirectional:
-            bwd = knn_points(target_cloud, source_cloud, lengths1=len_t, lengths2=len_s, K=1)
-            d_bwd, i_bwd = bwd.dists[..., 0], bwd.idx[..., 0]
+    @staticmethod
+    def _select(d_fwd, i_fwd, d_bwd, i_bwd, bidirectional, reverse, return_index):
+        """What the reference returns for the mode (utils/chamfer.py:119-132) from the per-direction results."""
         if bidirectional:
             total = d_fwd + d_bwd  # element-wise: needs ns == nt (utils/chamfer.py:119-123)
             return (total, i_fwd, i_bwd) if return_index else total
@@ -124,43 +126,23 @@ class ChamferDistance(torch.nn.Module):
             return (d_bwd, i_bwd) if return_index else d_bwd
         return (d_fwd, i_fwd) if return_index else d_fwd
 
-
-class _ChamferLossFn(Function):
-    """Pattern of networks/loss.py's _FlowLoss: the forward has computed the loss and both gradients, the backward
-    scales them by the upstream scalar."""
-
-    @staticmethod
-    def forward(ctx, x, y, mod):
-        loss, gx, gy = mod._run(x, y, y.requires_grad)
-        ctx.save_for_backward(gx, gy)
-        return loss
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g):
-        gx, gy = ctx.saved_tensors
-        return gx * g, (gy * g if gy is not None else None), None
+    def forward(self, source_cloud, target_cloud, bidirectional=False, reverse=False,
+                reduction="mean", return_index=False):
+        bs, ns, bt, nt = self._check(source_cloud, target_cloud, bidirectional, reverse, reduction)
+        len_s = torch.full((bs,), ns, dtype=torch.long, device=source_cloud.device)
+        len_t = torch.full((bt,), nt, dtype=torch.long, device=target_cloud.device)
+        fwd = knn_points(source_cloud, target_cloud, lengths1=len_s, lengths2=len_t, K=1)
+        d_fwd, i_fwd = fwd.dists[..., 0], fwd.idx[..., 0]
+        d_bwd = i_bwd = None
+        if reverse or bidirectional:
+            bwd = knn_points(target_cloud, source_cloud, lengths1=len_t, lengths2=len_s, K=1)
+            d_bwd, i_bwd = bwd.dists[..., 0], bwd.idx[..., 0]
+        return self._select(d_fwd, i_fwd, d_bwd, i_bwd, bidirectional, reverse, return_index)
 
 
-class ChamferLoss(torch.nn.Module):
-    """``forward(x, y) -> scalar``: the value of ``recon_loss(x, y, ChamferDistance())`` -- the sum over both directions
-    of the squared distance of every point to its nearest neighbour in the other cloud -- with its gradient, as one
-    warm-started native call (``reart_chamfer_loss``).  x [N,P1,3], y [N,P2,3] float32 on the GPU; P1 != P2 is allowed.
-
-    The module keeps, per (shapes, device): the neighbour indices of its previous call (they bound the next search and
-    never change its result), the native workspace with y's prepared image, and -- unless ``spatial_sort=False`` -- a
-    storage order per cloud (``relax.kd_order`` of the first x and of the first y, computed on the host once), in which
-    the box-pruned search is fastest.  Results are always in the caller's point numbering; ``.last`` holds the detached
-    ``(d_xy, i_xy, d_yx, i_yx)`` of the latest call.  With ``spatial_sort`` a tie between DISTINCT equidistant targets goes
-    to the one stored first (coincident points keep the caller's order, so copies of a point resolve to the lowest index).
-
-    State is never trusted for correctness: y's image is rebuilt whenever y is another tensor (``data_ptr``, shape,
-    device) or was modified in place (``_version``).  After the first call on a shape there is no host synchronisation.
-    Gradient reaches y only when ``y.requires_grad``.
-
-    Host tensors raise ``RuntimeError: ... no CPU fallback``.  Inputs the warm search does not serve (D != 3, float64)
-    go through two ``knn_points`` calls inside the module: the same value and gradients, without warm state (``.last``
-    is filled as well)."""
+class _WarmChamfer(torch.nn.Module):
+    """State of the warm-started Chamfer operators (``ChamferLoss``, ``ChamferPoints``), per (shapes, device): the seeds,
+    the native workspace with y's prepared image and the key of the y it was built from, the storage orders, ``.last``."""
 
     def __init__(self, spatial_sort=True):
         super().__init__()
@@ -172,24 +154,6 @@ class ChamferLoss(torch.nn.Module):
         """Forget seeds, orders, y's image and ``.last`` (the next call is a first call)."""
         self._state = {}
         self._last = self._raw = None
-
-    def forward(self, x, y, bidirectional=True):
-        for cloud in (x, y):
-            if not isinstance(cloud, torch.Tensor):
-                raise TypeError("Expected input type torch.Tensor. Got {} instead".format(type(cloud)))
-        if not bidirectional:
-            raise ValueError("ChamferLoss is the bidirectional sum")
-        _lib.require_gpu(x, y)
-        if x.dim() != 3 or y.dim() != 3 or x.shape[0] != y.shape[0] or x.shape[2] != y.shape[2]:
-            raise ValueError("ChamferLoss: x [N,P1,D] and y [N,P2,D]")
-        if x.device != y.device:
-            raise ValueError("Source and target clouds must be on the same device.")
-        if x.shape[2] != 3 or x.dtype != torch.float32 or y.dtype != torch.float32:
-            fwd = knn_points(x, y, K=1)
-            bwd = knn_points(y, x, K=1)
-            self._raw, self._last = None, (fwd.dists[..., 0].detach(), fwd.idx[..., 0], bwd.dists[..., 0].detach(), bwd.idx[..., 0])
-            return torch.sum(fwd.dists) + torch.sum(bwd.dists)
-        return _ChamferLossFn.apply(x, y, self)
 
     @staticmethod
     def _orders(c):
@@ -207,13 +171,13 @@ class ChamferLoss(torch.nn.Module):
         N, P1, P2 = x.shape[0], x.shape[1], y.shape[1]
         dev = x.device
         if N == 0 or P1 == 0 or P2 == 0:
-            raise ValueError("ChamferLoss: empty clouds")
+            raise ValueError(f"{type(self).__name__}: empty clouds")
         key = (N, P1, P2, dev)
         st = self._state.get(key)
         if st is None:
             nbytes = _lib.lib().reart_chamfer_loss_workspace_bytes(N, P1, P2)
             if nbytes == 0:
-                raise NotImplementedError("ChamferLoss: shape beyond reart_chamfer_loss")
+                raise NotImplementedError(f"{type(self).__name__}: shape beyond reart_chamfer_loss")
             st = {"ws": torch.empty(int(nbytes), dtype=torch.uint8, device=dev),
                   "seed_xy": torch.full((N, P1), -1, dtype=torch.int32, device=dev),
                   "seed_yx": torch.full((N, P2), -1, dtype=torch.int32, device=dev),
@@ -253,6 +217,79 @@ class ChamferLoss(torch.nn.Module):
                 sd = torch.gather(sd, 1, rows[0])                                          # row of the stored point
             st[name].copy_(sd.to(torch.int32))
 
+    @property
+    def last(self):
+        """Detached ``(d_xy [N,P1], i_xy [N,P1] int64, d_yx [N,P2], i_yx [N,P2] int64)`` of the latest call, in the caller's
+        numbering (None before the first call; a direction that was not computed is None).  With ``spatial_sort`` they are
+        renumbered on first access, not in the call."""
+        if self._last is None and self._raw is not None:
+            d_xy, i_xy, d_yx, i_yx, px, py = self._raw
+            if px is not None:
+                # rows through the inverse order, neighbour indices through the other cloud's order
+                (px, ix), (py, iy) = px, py
+                if d_xy is not None:
+                    d_xy, i_xy = torch.gather(d_xy, 1, ix), torch.gather(torch.gather(py, 1, i_xy), 1, ix)
+                if d_yx is not None:
+                    d_yx, i_yx = torch.gather(d_yx, 1, iy), torch.gather(torch.gather(px, 1, i_yx), 1, iy)
+            self._last = (d_xy, i_xy, d_yx, i_yx)
+        return self._last
+
+
+class _ChamferLossFn(Function):
+    """Pattern of networks/loss.py's _FlowLoss: the forward has computed the loss and both gradients, the backward
+    scales them by the upstream scalar."""
+
+    @staticmethod
+    def forward(ctx, x, y, mod):
+        loss, gx, gy = mod._run(x, y, y.requires_grad)
+        ctx.save_for_backward(gx, gy)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        gx, gy = ctx.saved_tensors
+        return gx * g, (gy * g if gy is not None else None), None
+
+
+class ChamferLoss(_WarmChamfer):
+    """``forward(x, y) -> scalar``: the value of ``recon_loss(x, y, ChamferDistance())`` -- the sum over both directions
+    of the squared distance of every point to its nearest neighbour in the other cloud -- with its gradient, as one
+    warm-started native call (``reart_chamfer_loss``).  x [N,P1,3], y [N,P2,3] float32 on the GPU; P1 != P2 is allowed.
+
+    The module keeps, per (shapes, device): the neighbour indices of its previous call (they bound the next search and
+    never change its result), the native workspace with y's prepared image, and -- unless ``spatial_sort=False`` -- a
+    storage order per cloud (``relax.kd_order`` of the first x and of the first y, computed on the host once), in which
+    the box-pruned search is fastest.  Results are always in the caller's point numbering; ``.last`` holds the detached
+    ``(d_xy, i_xy, d_yx, i_yx)`` of the latest call.  With ``spatial_sort`` a tie between DISTINCT equidistant targets goes
+    to the one stored first (coincident points keep the caller's order, so copies of a point resolve to the lowest index).
+
+    State is never trusted for correctness: y's image is rebuilt whenever y is another tensor (``data_ptr``, shape,
+    device) or was modified in place (``_version``).  After the first call on a shape there is no host synchronisation.
+    Gradient reaches y only when ``y.requires_grad``.
+
+    Host tensors raise ``RuntimeError: ... no CPU fallback``.  Inputs the warm search does not serve (D != 3, float64)
+    go through two ``knn_points`` calls inside the module: the same value and gradients, without warm state (``.last``
+    is filled as well)."""
+
+    def forward(self, x, y, bidirectional=True):
+        for cloud in (x, y):
+            if not isinstance(cloud, torch.Tensor):
+                raise TypeError("Expected input type torch.Tensor. Got {} instead".format(type(cloud)))
+        if not bidirectional:
+            raise ValueError("ChamferLoss is the bidirectional sum")
+        _lib.require_gpu(x, y)
+        if x.dim() != 3 or y.dim() != 3 or x.shape[0] != y.shape[0] or x.shape[2] != y.shape[2]:
+            raise ValueError("ChamferLoss: x [N,P1,D] and y [N,P2,D]")
+        if x.device != y.device:
+            raise ValueError("Source and target clouds must be on the same device.")
+        if x.shape[2] != 3 or x.dtype != torch.float32 or y.dtype != torch.float32:
+            fwd = knn_points(x, y, K=1)
+            bwd = knn_points(y, x, K=1)
+            self._raw, self._last = None, (fwd.dists[..., 0].detach(), fwd.idx[..., 0], bwd.dists[..., 0].detach(), bwd.idx[..., 0])
+            return torch.sum(fwd.dists) + torch.sum(bwd.dists)
+        return _ChamferLossFn.apply(x, y, self)
+
     def _run(self, x, y, want_gy):
         N, P1, P2 = x.shape[0], x.shape[1], y.shape[1]
         dev = x.device
@@ -289,16 +326,145 @@ class ChamferLoss(torch.nn.Module):
         self.fx_bits = st["bits"]
         return loss, gx, gy
 
-    @property
-    def last(self):
-        """Detached ``(d_xy [N,P1], i_xy [N,P1] int64, d_yx [N,P2], i_yx [N,P2] int64)`` of the latest call, in the caller's
-        numbering (None before the first call).  With ``spatial_sort`` they are renumbered on first access, not in the call."""
-        if self._last is None and self._raw is not None:
-            d_xy, i_xy, d_yx, i_yx, px, py = self._raw
-            if px is not None:
-                # rows through the inverse order, neighbour indices through the other cloud's order
-                (px, ix), (py, iy) = px, py
-                d_xy, i_xy = torch.gather(d_xy, 1, ix), torch.gather(torch.gather(py, 1, i_xy), 1, ix)
-                d_yx, i_yx = torch.gather(d_yx, 1, iy), torch.gather(torch.gather(px, 1, i_yx), 1, iy)
-            self._last = (d_xy, i_xy, d_yx, i_yx)
-        return self._last
+
+_DIRECTIONS = {"xy": 1, "yx": 2, "both": 3}
+
+
+class _ChamferPointsFn(Function):
+    """The forward hands out the per-point distances of the searched directions; the backward takes whatever upstream
+    arrives for them (None for an output that was not used) to ``reart_chamfer_points_backward``."""
+
+    @staticmethod
+    def forward(ctx, x, y, mod, directions):
+        ctx.set_materialize_grads(False)
+        xs, ys, d_xy, i_xy, d_yx, i_yx, px, py = mod._run(x, y, directions)
+        ctx.save_for_backward(xs, ys, d_xy, i_xy, d_yx, i_yx)
+        ctx.mod, ctx.orders = mod, (px, py)
+        if px is not None:
+            # stored -> caller numbering: rows through the inverse order
+            o_xy = None if d_xy is None else torch.gather(d_xy, 1, px[1])
+            o_yx = None if d_yx is None else torch.gather(d_yx, 1, py[1])
+        else:
+            # fresh tensors for autograd to mark as outputs; the saved ones and .last stay plain
+            o_xy = None if d_xy is None else d_xy.clone()
+            o_yx = None if d_yx is None else d_yx.clone()
+        return o_xy, o_yx
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_xy, g_yx):
+        if g_xy is None and g_yx is None:
+            return None, None, None, None
+        xs, ys, d_xy, i_xy, d_yx, i_yx = ctx.saved_tensors
+        px, py = ctx.orders
+        N, P1, P2 = xs.shape[0], xs.shape[1], ys.shape[1]
+        dev = xs.device
+        # an expanded tensor (from .sum()) is the common upstream: dense float32, in the stored numbering
+        if g_xy is not None:
+            g_xy = g_xy.to(torch.float32).contiguous() if px is None else torch.gather(g_xy.to(torch.float32), 1, px[0])
+        if g_yx is not None:
+            g_yx = g_yx.to(torch.float32).contiguous() if py is None else torch.gather(g_yx.to(torch.float32), 1, py[0])
+        gx = torch.empty((N, P1, 3), dtype=torch.float32, device=dev)
+        gy = torch.empty((N, P2, 3), dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
+        bits = torch.empty((N, 2), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            rc = _lib.lib().reart_chamfer_points_backward(
+                _lib.ptr(xs), _lib.ptr(ys), N, P1, P2, _lib.ptr(i_xy), _lib.ptr(i_yx), _lib.ptr(d_xy), _lib.ptr(d_yx),
+                _lib.ptr(g_xy), _lib.ptr(g_yx), _lib.ptr(gx), _lib.ptr(gy), _lib.ptr(bits), _lib.stream())
+        _lib.check(rc, "reart_chamfer_points_backward")
+        ctx.mod.fx_bits = bits
+        if px is not None:
+            gx = torch.gather(gx, 1, px[1][..., None].expand(-1, -1, 3))
+            if gy is not None:
+                gy = torch.gather(gy, 1, py[1][..., None].expand(-1, -1, 3))
+        return (gx if ctx.needs_input_grad[0] else None), gy, None, None
+
+
+class ChamferPoints(_WarmChamfer):
+    """``forward(x, y, directions="both") -> (d_xy [N,P1], d_yx [N,P2])``: the per-point squared distances to the nearest
+    neighbour in the other cloud, as ``ChamferDistance`` returns them, from the warm-started search of ``ChamferLoss``
+    (``reart_chamfer_points``), differentiable with respect to x -- and y, when it requires grad -- for ANY per-point
+    upstream gradient (``reart_chamfer_points_backward``): weights, masks, means over clouds of different sizes, robust
+    functions of the distances.  x [N,P1,3], y [N,P2,3] float32 on the GPU; P1 != P2 is allowed.  With ``directions``
+    "xy" or "yx" only that direction is searched and the other result is None.
+
+    State, its keys, ``seed()``, ``reset()``, ``spatial_sort`` and the tie rule are ``ChamferLoss``'s; results and
+    gradients are always in the caller's numbering.  ``.last`` holds the detached ``(d_xy, i_xy, d_yx, i_yx)`` of the
+    latest call (None for a direction that was not computed), ``.fx_bits`` the [N,2] fractional bits of the latest
+    backward's fixed-point sums into x and into y.  An output that is not used contributes nothing and costs nothing in
+    the backward; the backward reads only what its own forward returned, never the module's state.
+
+    Host tensors raise ``RuntimeError: ... no CPU fallback``; D != 3 or float64 go through ``knn_points(..., K=1)`` (same
+    values, gradients through its backward, no warm state); a shape beyond the workspace raises NotImplementedError."""
+
+    def forward(self, x, y, directions="both"):
+        for cloud in (x, y):
+            if not isinstance(cloud, torch.Tensor):
+                raise TypeError("Expected input type torch.Tensor. Got {} instead".format(type(cloud)))
+        _lib.require_gpu(x, y)
+        if directions not in _DIRECTIONS:
+            raise ValueError('ChamferPoints: directions must be "both", "xy" or "yx"')
+        if x.dim() != 3 or y.dim() != 3 or x.shape[0] != y.shape[0] or x.shape[2] != y.shape[2]:
+            raise ValueError("ChamferPoints: x [N,P1,D] and y [N,P2,D]")
+        if x.device != y.device:
+            raise ValueError("Source and target clouds must be on the same device.")
+        mask = _DIRECTIONS[directions]
+        if x.shape[2] != 3 or x.dtype != torch.float32 or y.dtype != torch.float32:
+            fwd = knn_points(x, y, K=1) if mask & 1 else None
+            bwd = knn_points(y, x, K=1) if mask & 2 else None
+            d_xy, i_xy = (fwd.dists[..., 0], fwd.idx[..., 0]) if fwd is not None else (None, None)
+            d_yx, i_yx = (bwd.dists[..., 0], bwd.idx[..., 0]) if bwd is not None else (None, None)
+            self._raw = None
+            self._last = (None if d_xy is None else d_xy.detach(), i_xy, None if d_yx is None else d_yx.detach(), i_yx)
+            return d_xy, d_yx
+        return _ChamferPointsFn.apply(x, y, self, mask)
+
+    def _run(self, x, y, directions):
+        """One native forward in the stored numbering -> (xs, ys, d_xy, i_xy, d_yx, i_yx, px, py)."""
+        N, P1, P2 = x.shape[0], x.shape[1], y.shape[1]
+        dev = x.device
+        st, ykey = self._prepare(x, y)
+        same_y = st["built"] == ykey     # y's SoA image and boxes in THIS workspace were built from exactly this y
+        if directions & 1:               # a y -> x search alone neither reads nor writes y's image
+            st["built"] = None           # until the call below has returned without an error
+        xd = x.detach()
+        if self.spatial_sort:
+            xs = torch.gather(xd, 1, st["px"][0][..., None].expand(-1, -1, 3))
+        else:
+            xs = xd.contiguous()
+        ys = st["ys"]
+        d_xy = i_xy = d_yx = i_yx = None
+        if directions & 1:
+            d_xy = torch.empty((N, P1), dtype=torch.float32, device=dev)
+            i_xy = torch.empty((N, P1), dtype=torch.int64, device=dev)
+        if directions & 2:
+            d_yx = torch.empty((N, P2), dtype=torch.float32, device=dev)
+            i_yx = torch.empty((N, P2), dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            rc = _lib.lib().reart_chamfer_points(
+                _lib.ptr(xs), _lib.ptr(ys), N, P1, P2, directions, _lib.ptr(st["seed_xy"]), _lib.ptr(st["seed_yx"]), int(same_y),
+                _lib.ptr(d_xy), _lib.ptr(i_xy), _lib.ptr(d_yx), _lib.ptr(i_yx), _lib.ptr(st["ws"]), st["ws"].numel(), _lib.stream())
+        _lib.check(rc, "reart_chamfer_points")
+        if directions & 1:
+            st["built"] = ykey
+        self._last, self._raw = None, (d_xy, i_xy, d_yx, i_yx, st["px"], st["py"])
+        return xs, ys, d_xy, i_xy, d_yx, i_yx, st["px"], st["py"]
+
+
+class WarmChamferDistance(ChamferDistance):
+    """``ChamferDistance`` over a ``ChamferPoints``: the same signature, validation, warnings, errors and return shapes, with
+    only the direction(s) the mode needs searched, warm from the module's previous call.  For float32 [B,P,3] clouds on
+    the GPU the distances equal ``ChamferDistance``'s bit for bit, the indices too except for a tie between DISTINCT
+    equidistant targets under ``spatial_sort=True`` (the caveat of ``ChamferLoss``).  ``recon_loss(x, y,
+    WarmChamferDistance())`` goes through the per-point branch."""
+
+    def __init__(self, spatial_sort=True):
+        super().__init__()
+        self.points = ChamferPoints(spatial_sort=spatial_sort)
+
+    def forward(self, source_cloud, target_cloud, bidirectional=False, reverse=False,
+                reduction="mean", return_index=False):
+        self._check(source_cloud, target_cloud, bidirectional, reverse, reduction)
+        d_fwd, d_bwd = self.points(source_cloud, target_cloud, "both" if bidirectional else ("yx" if reverse else "xy"))
+        _, i_fwd, _, i_bwd = self.points.last if return_index else (None,) * 4
+        return self._select(d_fwd, i_fwd, d_bwd, i_bwd, bidirectional, reverse, return_index)

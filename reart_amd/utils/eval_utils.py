@@ -44,13 +44,18 @@ def eval_seg(gt_segm, pd_segm, as_tensor=False, num_labels=128):
     return (agree / (n * n)).float().cpu().numpy()
 
 
-def compute_chamfer_list(points_set1, points_set2, reduction="sum"):
+def compute_chamfer_list(points_set1, points_set2, reduction="sum", chamfer=None):
     """utils/eval_utils.py:39-66 (KD-tree Chamfer per frame) on the GPU search: per frame the sum / mean of the squared
-    nearest-neighbour distances of both directions; "mean" / "sum" reduce over frames like the reference."""
+    nearest-neighbour distances of both directions; "mean" / "sum" reduce over frames like the reference.
+    ``chamfer``: a ``utils.chamfer.ChamferPoints`` the caller keeps between snapshots -- both directions then come from one
+    call of it, warm from the previous snapshot (same distances); None: two cold ``ChamferDistance`` searches."""
     a, b = torch.as_tensor(points_set1).float(), torch.as_tensor(points_set2).float()
-    cd = ChamferDistance()
-    d12 = cd(a, b)          # [T,N] squared NN distances a -> b
-    d21 = cd(b, a)
+    if chamfer is not None:
+        d12, d21 = chamfer(a, b)
+    else:
+        cd = ChamferDistance()
+        d12 = cd(a, b)          # [T,N] squared NN distances a -> b
+        d21 = cd(b, a)
     if reduction == "mean":
         return float((d12.mean(1) + d21.mean(1)).mean())
     per = d12.sum(1) + d21.sum(1)
