@@ -240,6 +240,47 @@ int reart_compute_pc_transform(const float *cano, const float *pose, const int64
 /* Replaces rotation_6d_to_matrix (screw_se3/geo_utils.py:632-651): d6 [n,6] -> R [n,3,3]. */
 int reart_rotation_6d_to_matrix(const float *d6, int n, float *R, void *stream);
 
+/* ---- First-order gradients through the transforms (transform_grad.hip).  The reference gets them from autograd: its
+ * trans_list, fk(...), compute_pc_transform and cano_pc are ordinary tensors.  float32; deterministic (fixed-order sums, no
+ * atomics: two runs agree bit for bit); no host synchronisation, capturable; bad arguments are refused before any launch. */
+
+/* Backward of reart_rotation_6d_to_matrix: d6 [n,6], gR = dL/dR [n,3,3] -> g6 [n,6].  The Gram-Schmidt backward of
+ * screw_se3/geo_utils.py:632-651 with F.normalize's eps: a vector of norm <= 1e-12 is divided by 1e-12 and its gradient too. */
+int reart_rotation_6d_to_matrix_backward(const float *d6, const float *gR, int n, float *g6, void *stream);
+
+/* Backward of reart_compute_pc_transform: cano [N,3], pose [B,P,4,4], part [N] i64, G = dL/d out [B,N,3] ->
+ *   g_cano [N,3] = sum_b R[b,part_n]^T G[b,n], b ascending (a label outside [0,P): zero);
+ *   g_pose [B,P,4,4]: rows 0..2 = [ sum_{n in p} G[b,n] x_n^T | sum_{n in p} G[b,n] ], the points added as reart_fk_backward
+ *   adds them (ascending inside a slice of the cloud, the slices in ascending order); row 3 = 0; a part without points: zeros.
+ * Either output may be NULL (not computed); the workspace is needed for g_pose only.  P <= 1024: REART_ERR_INVALID_ARG above
+ * (the workspace query then returns 0). */
+size_t reart_compute_pc_transform_backward_workspace_bytes(int N, int P, int B);
+int reart_compute_pc_transform_backward(const float *cano, const float *pose, const int64_t *part, const float *G,
+                                        int N, int P, int B, float *g_cano, float *g_pose,
+                                        void *workspace, size_t workspace_bytes, void *stream);
+
+/* BaseModel.forward's trans_list is [rotation_6d_to_matrix(proposal_6d) | proposal_t] (networks/model.py:60-68): an upstream
+ * g_trans [n,4,4] on it (n = B*P rows) -> gt (+)= g_trans[:, :3, 3], g6d (+)= the 6D backward of g_trans[:, :3, :3] at p6d [n,6].
+ * Row 3 is ignored.  accumulate != 0 adds onto g6d / gt (what reart_base_backward left there), 0 overwrites them.  A kernel of
+ * its own over the rows: every pose_len of the model is served alike. */
+int reart_pose_trans_backward(const float *p6d, const float *g_trans, int n, float *g6d, float *gt, int accumulate, void *stream);
+
+/* Gradient of the canonical cloud through reart_base_forward: the arguments of reart_base_backward (yT, hT, hard_idx as the
+ * forward saved them, all required; b1 is not read: hT carries the ReLU decision) -> g_cano [N,3] = the sum of
+ *   the rigid term            sum_b R[b,hard_n]^T G[b,n], and
+ *   the straight-through term dL/dw_p = sum_b G[b,n] . (R_bp x_n + t_bp) -> softmax backward with 1/tau -> W2^T -> the
+ *                             forward's ReLU activity (hT > 0) -> W1^T.
+ * The hard part and the ReLU activity are the forward's decisions.  The pose table [B*P][12] is built into the workspace and
+ * read from there, whichever kernels served the forward (reart_base_path).  P <= 32, B <= REART_MAX_POSE_LEN
+ * (REART_ERR_INVALID_ARG above; the workspace query then returns 0); H <= 256 (REART_ERR_UNSUPPORTED above). */
+size_t reart_base_backward_cano_workspace_bytes(int P, int B);
+int reart_base_backward_cano(const float *cano, int N, int P, int B,
+                             const float *W1, const float *b1, const float *W2, int H,
+                             const float *prop6d, const float *propt,
+                             const float *yT, const float *hT, const int32_t *hard_idx, float tau,
+                             const float *G, float *g_cano,
+                             void *workspace, size_t workspace_bytes, void *stream);
+
 /* One torch.optim.Adam step on one tensor (run_robot.py:145-151,219-221; amsgrad off,
  * weight_decay 0).  `step` is the 1-based step count. */
 int reart_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq,
@@ -490,7 +531,9 @@ int reart_pn2_three_interpolate_grad(const float *grad_out, const int32_t *idx, 
  *   parent[c] (-1 = root), edge_of_part[c] (index of edge "c_parent" in edge_index),
  *   order = reverse_topo (parts from root to leaf), all i32 [P];
  *   axis, moment [E,3]; theta [B,E]; distance [B,E] or NULL (= 1e-6, :176);
- *   trans [B,P,4,4] out.  P <= 64, the limit of reart_fk_backward (REART_ERR_INVALID_ARG above it). */
+ *   trans [B,P,4,4] out.  P <= 64, the limit of reart_fk_backward (REART_ERR_INVALID_ARG above it).
+ *   A single part (P = 1, E = 0) has no joint: its empty axis / moment / theta (and the joint gradients of the backward
+ *   entries) may be NULL. */
 int reart_fk_forward(const int32_t *parent, const int32_t *edge_of_part, const int32_t *order,
                      int P, const float *axis, const float *moment, const float *theta,
                      const float *distance, int B, int E, float *trans, void *stream);
@@ -506,6 +549,19 @@ int reart_fk_backward(const float *x, const int64_t *part, const float *G, int N
                       const float *distance, int B, int E, const float *trans,
                       float *g_axis, float *g_moment, float *g_theta, float *g_distance,
                       void *workspace, size_t workspace_bytes, void *stream);
+
+/* reart_fk_backward with two more arguments, both nullable (workspace: reart_fk_backward_workspace_bytes):
+ *   g_trans [B,P,4,4]: an upstream on the forward's `trans`.  Its rows 0..2 are added onto the pose gradients of the points
+ *     before the leaves -> root walk; row 3 (constants) is not read.
+ *   g_x [N,3] out: the gradient of the cloud under the hard labels, sum_b R[b,part_n]^T G[b,n] with R from `trans`.
+ * N = 0 with x, part, G NULL is legal (`fk` alone: only g_trans drives the joints).  With both NULL the four joint gradients
+ * are reart_fk_backward's bit for bit (the same launches).  P <= 64.  float32, deterministic, capturable. */
+int reart_fk_backward_trans(const float *x, const int64_t *part, const float *G, int N,
+                            const int32_t *parent, const int32_t *edge_of_part, const int32_t *order,
+                            int P, const float *axis, const float *moment, const float *theta,
+                            const float *distance, int B, int E, const float *trans, const float *g_trans,
+                            float *g_axis, float *g_moment, float *g_theta, float *g_distance, float *g_x,
+                            void *workspace, size_t workspace_bytes, void *stream);
 
 /* Retargeting: replaces the optimisation loop of ik (utils/kinematic_utils.py:200-266) for a kinematic model without
  * distance_list, joint types or root motion: per novel pose m, n_iter steps of

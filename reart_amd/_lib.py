@@ -25,6 +25,7 @@ IK_MAX_POINTS = 1024     # REART_IK_MAX_POINTS: sparse points of reart_ik_fit, h
 LAP_LARGE_MAX_N = 8192   # REART_LAP_LARGE_MAX_N: columns of reart_lap_auction_large / reart_lap_resolve_large (solver state in LDS)
 FPS_MAX_N_LDS = 12288    # REART_FPS_MAX_N_LDS: reart_fps, cloud staged in LDS
 FPS_MAX_N = 1 << 21      # REART_FPS_MAX_N: reart_fps_temp, 21-bit index in the tie key
+PC_GRAD_MAX_P = 1024     # parts of reart_compute_pc_transform_backward: one frame's pose rows staged in LDS
 ADAM_MAX_TENSORS = 32    # REART_ADAM_MAX_TENSORS: records of one reart_adam_groups call, passed by value to its kernel
 
 # name -> (restype, argtypes); mirrors include/reart_hip.h one to one
@@ -59,6 +60,12 @@ PROTOTYPES = {
                                     P, P, P, P, P, P, c_size_t, P]),
     "reart_compute_pc_transform": (c_int, [P, P, P, c_int, c_int, c_int, P, P]),
     "reart_rotation_6d_to_matrix": (c_int, [P, c_int, P, P]),
+    "reart_rotation_6d_to_matrix_backward": (c_int, [P, P, c_int, P, P]),
+    "reart_compute_pc_transform_backward_workspace_bytes": (c_size_t, [c_int] * 3),
+    "reart_compute_pc_transform_backward": (c_int, [P, P, P, P, c_int, c_int, c_int, P, P, P, c_size_t, P]),
+    "reart_pose_trans_backward": (c_int, [P, P, c_int, P, P, c_int, P]),
+    "reart_base_backward_cano_workspace_bytes": (c_size_t, [c_int] * 2),
+    "reart_base_backward_cano": (c_int, [P, c_int, c_int, c_int, P, P, P, c_int, P, P, P, P, P, c_float, P, P, P, c_size_t, P]),
     "reart_adam_step": (c_int, [P, P, P, P, c_int, c_int, c_float, c_float, c_float, c_float, P]),
     "reart_adam_step_multi": (c_int, [c_int, P, P, P, P, P, P, c_int, c_float, c_float, c_float, P]),
     "reart_adam_groups": (c_int, [P, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, P]),   # records: optim.AdamTensor
@@ -73,6 +80,8 @@ PROTOTYPES = {
     "reart_fk_backward_workspace_bytes": (c_size_t, [c_int] * 3),
     "reart_fk_backward": (c_int, [P, P, P, c_int, P, P, P, c_int, P, P, P, P, c_int, c_int, P, P, P, P, P, P,
                                   c_size_t, P]),
+    "reart_fk_backward_trans": (c_int, [P, P, P, c_int, P, P, P, c_int, P, P, P, P, c_int, c_int, P, P, P, P, P, P, P, P,
+                                        c_size_t, P]),
     "reart_ik_fit": (c_int, [P, P, P, c_int, P, P, c_int, P, P, c_int, P, c_int, P, c_int, c_float, c_float, c_float, c_float, P, P, P]),
     "reart_mlp_layer": (c_int, [P, c_int, P, c_int, c_int, c_int, P, c_int, P, P, c_int, P, P, c_int, c_int, c_int,
                                 c_int, c_int, P, c_int, c_int, P]),

@@ -103,6 +103,17 @@ __device__ __forceinline__ float reart_tau_schedule(long cur_iter, int n_iter, f
 #endif
 int reart_adam_ex(const AdamArgs &a, hipStream_t st);
 
+// ---- kinematic.hip, shared with transform_grad.hip ---------------------------------------
+#define PG_SLICES (256 / 12)   // point slices of pose_grad_kernel: twelve threads walk each, the slices are added in ascending order
+// the slices' partial sums [B][PG_SLICES][P*12] of sum_{n in p} [G[t,n] x_n^T | G[t,n]] (N >= 1, B >= 1; launch only)
+int reart_pose_grad_launch(const float *x, const int64_t *part, const float *G, int N, int P, int B, float *partial, hipStream_t st);
+// reart_fk_backward with an upstream g_trans [B,P,4,4] (nullable) on the forward's `trans`; N = 0: x, part, G may be NULL
+int reart_fk_backward_launch(const float *x, const int64_t *part, const float *G, int N, const int32_t *parent,
+                             const int32_t *edge_of_part, const int32_t *order, int P, const float *axis, const float *moment,
+                             const float *theta, const float *distance, int B, int E, const float *trans, const float *g_trans,
+                             float *g_axis, float *g_moment, float *g_theta, float *g_distance, void *workspace,
+                             size_t workspace_bytes, hipStream_t st);
+
 // generic K-NN driver (knn.hip): njobs in {1,2}; job j searches q[j] ([N,P1[j],3] AoS) in t[j]
 // ([N,P2[j],3] AoS); outputs dists/idx [N,P1[j],K].  Workspace: see knn_plan().
 int reart_knn_run(int njobs, const float *const *q, const float *const *t,

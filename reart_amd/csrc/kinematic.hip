@@ -63,7 +63,9 @@ extern "C" int reart_fk_forward(const int32_t *parent, const int32_t *edge_of_pa
                                 const float *distance, int B, int E, float *trans, void *stream) {
     if (P < 1 || P > FK_MAXP || B < 0 || E < 0) return REART_ERR_INVALID_ARG;      // the limit of reart_fk_backward: a model is refused
     if (B == 0) return REART_OK;                                                  // before its first forward, not at its first backward
-    if (!parent || !edge_of_part || !order || !axis || !moment || !theta || !trans) return REART_ERR_INVALID_ARG;
+    if (!parent || !edge_of_part || !order || !trans) return REART_ERR_INVALID_ARG;
+    // a single part has no joint: its empty axis / moment / theta may be NULL (the kernel writes the root's identity only)
+    if (E == 0 ? P != 1 : (!axis || !moment || !theta)) return REART_ERR_INVALID_ARG;
     hipLaunchKernelGGL(fk_fwd_kernel, dim3(reart_div_up(B, 64)), dim3(64), 0, (hipStream_t)stream, parent,
                        edge_of_part, order, P, axis, moment, theta, distance, B, E, trans);
     REART_CHECK_LAUNCH();
@@ -83,7 +85,7 @@ extern "C" int reart_fk_forward(const int32_t *parent, const int32_t *edge_of_pa
 // trip (68 us per launch at 9 x 4096: the longest kernel between two assignment re-solves).  Now a workgroup per (frame, slice):
 // the slice's points -- part labels, gradients, coordinates -- come into LDS in one coalesced batch, twelve threads walk them in
 // the SAME ascending order, and a second launch adds the slices in ascending order: the same additions in the same order.
-#define PG_SLICES (256 / 12)
+// (PG_SLICES: internal.h)
 __global__ __launch_bounds__(256) void pose_grad_kernel(const float *__restrict__ x,
                                                         const int64_t *__restrict__ part,
                                                         const float *__restrict__ G, int N, int P,
@@ -112,8 +114,11 @@ __global__ __launch_bounds__(256) void pose_grad_kernel(const float *__restrict_
 
 // (also clears frame t's rows of the joint gradients fk_bwd_kernel accumulates into -- [B,E] theta, [B,E] distance (nullable),
 // [B,E,6] axis/moment terms: three fill launches of their own otherwise, each a 5 us slot of the iteration)
+// partial == NULL: no points (the sums are zero).  g_trans [B,P,4,4] (nullable): an upstream on the forward's `trans`; its rows
+// 0..2 join the points' sums here, after the last slice, and walk the tree with them; its row 3 (constants) is not read.
 __global__ __launch_bounds__(256) void pose_grad_sum_kernel(const float *__restrict__ partial, int P, float *__restrict__ gpose, int E,
-                                                            float *__restrict__ g_theta, float *__restrict__ g_dist, float *__restrict__ g_lm) {
+                                                            float *__restrict__ g_theta, float *__restrict__ g_dist, float *__restrict__ g_lm,
+                                                            const float *__restrict__ g_trans) {
     const int t = blockIdx.x;
     for (int e = threadIdx.x; e < 6 * E; e += 256) {
         g_lm[(size_t)t * 6 * E + e] = 0.f;
@@ -121,10 +126,12 @@ __global__ __launch_bounds__(256) void pose_grad_sum_kernel(const float *__restr
     }
     for (int e = threadIdx.x; e < P * 12; e += 256) {
         float sum = 0.f;
-        for (int s = 0; s < PG_SLICES; ++s) sum += partial[((size_t)t * PG_SLICES + s) * P * 12 + e];
+        if (partial)
+            for (int s = 0; s < PG_SLICES; ++s) sum += partial[((size_t)t * PG_SLICES + s) * P * 12 + e];
         const int p = e / 12, cc = e % 12;
         // gpose layout 3x4 row-major: entry (i,j) for cc<9 is R[i][j] (i = cc/3, j = cc%3), cc>=9 is t[cc-9]
         const int i = cc < 9 ? cc / 3 : cc - 9, j = cc < 9 ? cc % 3 : 3;
+        if (g_trans) sum += g_trans[16 * ((size_t)t * P + p) + 4 * i + j];
         gpose[12 * ((size_t)t * P + p) + 4 * i + j] = sum;
     }
 }
@@ -197,29 +204,47 @@ extern "C" size_t reart_fk_backward_workspace_bytes(int P, int B, int E) {
            reart_align_up(sizeof(float) * 12 * (size_t)B * P * PG_SLICES, 256);      // gpose | g_lm | the slices' partial pose gradients
 }
 
+int reart_pose_grad_launch(const float *x, const int64_t *part, const float *G, int N, int P, int B, float *partial, hipStream_t st) {
+    const int pg_per = (N + PG_SLICES - 1) / PG_SLICES;
+    const size_t lds = sizeof(float) * ((size_t)P * 12 + 7 * (size_t)pg_per);
+    if (lds > REART_LDS_DEFAULT_CAP &&
+        hipFuncSetAttribute((const void *)pose_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return REART_ERR_LAUNCH;
+    hipLaunchKernelGGL(pose_grad_kernel, dim3(PG_SLICES, B), dim3(256), lds, st, x, part, G, N, P, partial);
+    return REART_OK;
+}
+
 extern "C" int reart_fk_backward(const float *x, const int64_t *part, const float *G, int N,
                                  const int32_t *parent, const int32_t *edge_of_part, const int32_t *order,
                                  int P, const float *axis, const float *moment, const float *theta,
                                  const float *distance, int B, int E, const float *trans,
                                  float *g_axis, float *g_moment, float *g_theta, float *g_distance,
                                  void *workspace, size_t workspace_bytes, void *stream) {
+    if (B != 0 && (!x || !part || !G)) return REART_ERR_INVALID_ARG;            // this entry takes no empty cloud without them
+    return reart_fk_backward_launch(x, part, G, N, parent, edge_of_part, order, P, axis, moment, theta, distance, B, E, trans,
+                                    nullptr, g_axis, g_moment, g_theta, g_distance, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int reart_fk_backward_launch(const float *x, const int64_t *part, const float *G, int N, const int32_t *parent,
+                             const int32_t *edge_of_part, const int32_t *order, int P, const float *axis, const float *moment,
+                             const float *theta, const float *distance, int B, int E, const float *trans, const float *g_trans,
+                             float *g_axis, float *g_moment, float *g_theta, float *g_distance, void *workspace,
+                             size_t workspace_bytes, hipStream_t st) {
     if (P < 1 || P > FK_MAXP || B < 0 || E < 0 || N < 0) return REART_ERR_INVALID_ARG;
     if (B == 0) return REART_OK;
-    if (!x || !part || !G || !parent || !edge_of_part || !order || !axis || !moment || !theta || !trans ||
-        !g_axis || !g_moment || !g_theta || !workspace)
-        return REART_ERR_INVALID_ARG;
+    if ((N > 0 && (!x || !part || !G)) || !parent || !edge_of_part || !order || !trans || !workspace) return REART_ERR_INVALID_ARG;
+    if (E == 0 && P == 1) return REART_OK;                     // a single part: no joint, every joint gradient is empty
+    if (!axis || !moment || !theta || !g_axis || !g_moment || !g_theta) return REART_ERR_INVALID_ARG;
     if (workspace_bytes < reart_fk_backward_workspace_bytes(P, B, E)) return REART_ERR_INVALID_ARG;
-    hipStream_t st = (hipStream_t)stream;
     float *gpose = (float *)workspace;
     float *g_lm = (float *)((char *)workspace + reart_align_up(sizeof(float) * 12 * (size_t)B * P, 256));
     float *pg_partial = (float *)((char *)g_lm + reart_align_up(sizeof(float) * 6 * (size_t)B * (E > 0 ? E : 1), 256));
-    const int pg_per = (N + PG_SLICES - 1) / PG_SLICES;
-    const size_t lds = sizeof(float) * ((size_t)P * 12 + 7 * (size_t)pg_per);
-    if (lds > REART_LDS_DEFAULT_CAP &&
-        hipFuncSetAttribute((const void *)pose_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return REART_ERR_LAUNCH;
-    hipLaunchKernelGGL(pose_grad_kernel, dim3(PG_SLICES, B), dim3(256), lds, st, x, part, G, N, P, pg_partial);
-    hipLaunchKernelGGL(pose_grad_sum_kernel, dim3(B), dim3(256), 0, st, pg_partial, P, gpose, E, g_theta, g_distance, g_lm);
+    if (N > 0) {
+        const int rc = reart_pose_grad_launch(x, part, G, N, P, B, pg_partial, st);
+        if (rc != REART_OK) return rc;
+    }
+    hipLaunchKernelGGL(pose_grad_sum_kernel, dim3(B), dim3(256), 0, st, N > 0 ? pg_partial : (const float *)nullptr, P, gpose, E,
+                       g_theta, g_distance, g_lm, g_trans);
     hipLaunchKernelGGL(fk_bwd_kernel, dim3(reart_div_up(B, 64)), dim3(64), 0, st, parent, edge_of_part, order, P,
                        axis, moment, theta, distance, B, E, trans, gpose, g_theta, g_distance, g_lm);
     if (E > 0)

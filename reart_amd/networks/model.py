@@ -38,26 +38,42 @@ class _BaseForward(torch.autograd.Function):
         ctx.tau = float(tau)
         ctx.shapes = (W1.shape, W2.shape)
         ctx.mark_non_differentiable(seg)
+        ctx.set_materialize_grads(False)      # an output nobody differentiates arrives as None, not as zeros
         return out, seg, trans
 
     @staticmethod
     def backward(ctx, g_out, g_seg, g_trans):
         cano, w1, bb1, w2, p6, ptt, yT, hT, hard = ctx.saved_tensors
         N, (B, P), H = cano.shape[0], p6.shape[:2], w1.shape[0]
-        G = g_out.contiguous().float()
-        gW1, gb1, gW2 = torch.empty_like(w1), torch.empty_like(bb1), torch.empty_like(w2)
-        g6d, gt = torch.empty_like(p6), torch.empty_like(ptt)
         L = _lib.lib()
-        ws = _lib.workspace(L.reart_base_backward_workspace_bytes(N, P, B, H), cano.device)
-        rc = L.reart_base_backward(_lib.ptr(cano), N, P, B, _lib.ptr(w1), _lib.ptr(bb1), _lib.ptr(w2), H,
-                                   _lib.ptr(p6), _lib.ptr(ptt), _lib.ptr(yT), _lib.ptr(hT), _lib.ptr(hard), ctx.tau,
-                                   _lib.ptr(G), _lib.ptr(gW1), _lib.ptr(gb1), _lib.ptr(gW2), _lib.ptr(g6d),
-                                   _lib.ptr(gt), _lib.ptr(ws), ws.numel(), _lib.stream())
-        _lib.check(rc, "reart_base_backward")
-        if g_trans is not None and g_trans.abs().sum() != 0:
-            raise NotImplementedError("gradient through trans_list is not used by the relaxation loop")
         s1, s2 = ctx.shapes
-        return None, gW1.reshape(s1), gb1, gW2.reshape(s2), g6d, gt, None, None
+        gW1 = gb1 = gW2 = g_cano = None
+        g6d, gt = torch.empty_like(p6), torch.empty_like(ptt)
+        if g_out is not None:
+            G = g_out.contiguous().float()
+            gW1, gb1, gW2 = torch.empty_like(w1), torch.empty_like(bb1), torch.empty_like(w2)
+            ws = _lib.workspace(L.reart_base_backward_workspace_bytes(N, P, B, H), cano.device)
+            rc = L.reart_base_backward(_lib.ptr(cano), N, P, B, _lib.ptr(w1), _lib.ptr(bb1), _lib.ptr(w2), H,
+                                       _lib.ptr(p6), _lib.ptr(ptt), _lib.ptr(yT), _lib.ptr(hT), _lib.ptr(hard), ctx.tau,
+                                       _lib.ptr(G), _lib.ptr(gW1), _lib.ptr(gb1), _lib.ptr(gW2), _lib.ptr(g6d),
+                                       _lib.ptr(gt), _lib.ptr(ws), ws.numel(), _lib.stream())
+            _lib.check(rc, "reart_base_backward")
+            gW1, gW2 = gW1.reshape(s1), gW2.reshape(s2)
+            if ctx.needs_input_grad[0]:      # the canonical cloud: rigid term + straight-through term
+                g_cano = torch.empty_like(cano)
+                ws = _lib.workspace(L.reart_base_backward_cano_workspace_bytes(P, B), cano.device)
+                rc = L.reart_base_backward_cano(_lib.ptr(cano), N, P, B, _lib.ptr(w1), _lib.ptr(bb1), _lib.ptr(w2), H,
+                                                _lib.ptr(p6), _lib.ptr(ptt), _lib.ptr(yT), _lib.ptr(hT), _lib.ptr(hard),
+                                                ctx.tau, _lib.ptr(G), _lib.ptr(g_cano), _lib.ptr(ws), ws.numel(), _lib.stream())
+                _lib.check(rc, "reart_base_backward_cano")
+        elif ctx.needs_input_grad[0]:        # pc_trans took no part in the loss, and trans_list does not depend on the cloud
+            g_cano = torch.zeros_like(cano)
+        if g_trans is not None:              # trans_list = [R(p6d) | pt]: onto the poses' gradients, or alone
+            Gt = g_trans.contiguous().float()
+            rc = L.reart_pose_trans_backward(_lib.ptr(p6), _lib.ptr(Gt), B * P, _lib.ptr(g6d), _lib.ptr(gt),
+                                             int(g_out is not None), _lib.stream())
+            _lib.check(rc, "reart_pose_trans_backward")
+        return g_cano, gW1, gb1, gW2, g6d, gt, None, None
 
 
 def sample_gumbel(shape, device, dtype=torch.float32):
@@ -123,7 +139,10 @@ class KinematicModel(nn.Module):
     optional ``distance_list``.  forward = k-NN label transfer (utils/model_utils.py:41-51) +
     fused FK kernel + hard-label rigid apply.  Root motion (``root_trans`` / ``load_root_trans``, the SAPIEN / real-scan
     variant, networks/model.py:113-120,153-158) is a per-frame rigid transform composed after the kernels (a [T-1,3,3]
-    Gram-Schmidt and one batched multiply in PyTorch, differentiable w.r.t. ``root_6d`` / ``root_t``)."""
+    Gram-Schmidt and one batched multiply in PyTorch, differentiable w.r.t. ``root_6d`` / ``root_t``).
+    ``pc_trans_list`` is differentiable w.r.t. the parameters and ``input_pc``.  ``trans_list`` is returned as a plain tensor,
+    which callers hand to numpy as it is; ``model(input_pc, trans_grad=True)`` returns it with its graph (joint parameters
+    and root motion), for a loss on the part transforms."""
 
     def __init__(self, pose_len, seg_part, cano_pc, knn, **kwargs):
         super().__init__()
@@ -178,15 +197,16 @@ class KinematicModel(nn.Module):
         distance_list = self.distance_list if hasattr(self, "distance_list") else None
         theta, dist = _effective_joint_values(theta_list, distance_list, self.joint_type_list)
         parent, edge_of, order = self._tree(input_pc.device)
+        trans_grad = bool(kwargs.get("trans_grad", False))  # extension: trans_list with its graph (default: a plain tensor)
         pc_trans_list, trans_list = _FK.apply(input_pc, seg_part, self.axis_list, self.moment_list, theta, dist,
-                                              parent, edge_of, order)
+                                              parent, edge_of, order, trans_grad)
         if hasattr(self, "root_6d") and hasattr(self, "root_t"):     # networks/model.py:153-158
             a1, a2 = self.root_6d[:, :3], self.root_6d[:, 3:]
             b1 = torch.nn.functional.normalize(a1, dim=-1)
             b2 = torch.nn.functional.normalize(a2 - (b1 * a2).sum(-1, keepdim=True) * b1, dim=-1)
             R = torch.stack((b1, b2, torch.cross(b1, b2, dim=-1)), dim=-2)                       # [T-1,3,3]
             pc_trans_list = torch.matmul(pc_trans_list, R.transpose(1, 2)) + self.root_t[:, None, :]
-            with torch.no_grad():
+            with torch.set_grad_enabled(trans_grad and torch.is_grad_enabled()):
                 root = torch.zeros((R.shape[0], 4, 4), dtype=R.dtype, device=R.device)
                 root[:, :3, :3], root[:, :3, 3], root[:, 3, 3] = R, self.root_t, 1.0
                 trans_list = torch.matmul(root[:, None], trans_list)

@@ -4,14 +4,38 @@ import torch
 from .. import _lib
 
 
-def rotation_6d_to_matrix(d6):
-    """Gram-Schmidt 6D -> rotation matrix, rows b1,b2,b3 (screw_se3/geo_utils.py:632-651).
-    Forward-only entry point (inside BaseModel the conversion is fused with its backward)."""
-    _lib.require_gpu(d6)
-    flat = d6.reshape(-1, 6).contiguous().float()
-    R = torch.empty((flat.shape[0], 3, 3), dtype=torch.float32, device=d6.device)
+def _r6d_forward(flat):
+    R = torch.empty((flat.shape[0], 3, 3), dtype=torch.float32, device=flat.device)
     rc = _lib.lib().reart_rotation_6d_to_matrix(_lib.ptr(flat), flat.shape[0], _lib.ptr(R), _lib.stream())
     _lib.check(rc, "reart_rotation_6d_to_matrix")
+    return R
+
+
+class _Rotation6D(torch.autograd.Function):
+    """flat [n,6] -> R [n,3,3]; backward = reart_rotation_6d_to_matrix_backward (first order only)."""
+
+    @staticmethod
+    def forward(ctx, flat):
+        ctx.save_for_backward(flat)
+        return _r6d_forward(flat)
+
+    @staticmethod
+    def backward(ctx, gR):
+        flat, = ctx.saved_tensors
+        gR = gR.contiguous().float()
+        g6 = torch.empty_like(flat)
+        rc = _lib.lib().reart_rotation_6d_to_matrix_backward(_lib.ptr(flat), _lib.ptr(gR), flat.shape[0], _lib.ptr(g6),
+                                                             _lib.stream())
+        _lib.check(rc, "reart_rotation_6d_to_matrix_backward")
+        return g6
+
+
+def rotation_6d_to_matrix(d6):
+    """Gram-Schmidt 6D -> rotation matrix, rows b1,b2,b3 (screw_se3/geo_utils.py:632-651), any leading shape.
+    Differentiable w.r.t. ``d6`` (inside BaseModel the conversion is fused with its backward)."""
+    _lib.require_gpu(d6)
+    flat = d6.reshape(-1, 6).contiguous().float()
+    R = _Rotation6D.apply(flat) if flat.requires_grad and torch.is_grad_enabled() else _r6d_forward(flat)
     return R.reshape(d6.shape[:-1] + (3, 3))
 
 

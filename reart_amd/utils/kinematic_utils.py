@@ -22,10 +22,15 @@ def tree_arrays(edge_index, reverse_topo):
 
 
 class _FK(torch.autograd.Function):
-    """pc_trans, trans_list = rigid_apply(fk(...)); gradients to axis / moment / theta / distance."""
+    """pc_trans, trans_list = rigid_apply(fk(...)); gradients to axis / moment / theta / distance and to the cloud ``x``, from
+    an upstream on either output (first order only).  An empty cloud ([0,3]) is ``fk`` alone.  ``trans_list`` carries a graph
+    only where the caller asks for it (``trans_grad``): otherwise it is the plain tensor it has always been, which callers hand
+    to numpy as it is."""
 
     @staticmethod
-    def forward(ctx, x, part, axis, moment, theta, distance, parent, edge_of, order):
+    def forward(ctx, x, part, axis, moment, theta, distance, parent, edge_of, order, *opt):
+        assert len(opt) <= 1                                      # (trans_grad,): optional, default False
+        trans_grad = bool(opt and opt[0])
         _lib.require_gpu(x, part, axis, moment, theta)
         x, part = x.contiguous().float(), part.contiguous().long()
         axis, moment, theta = axis.contiguous().float(), moment.contiguous().float(), theta.contiguous().float()
@@ -43,7 +48,10 @@ class _FK(torch.autograd.Function):
         _lib.check(rc, "reart_compute_pc_transform")
         ctx.save_for_backward(x, part, axis, moment, theta, trans, parent, edge_of, order)
         ctx.dist = dist
-        ctx.mark_non_differentiable(trans)
+        ctx.set_materialize_grads(False)      # an output nobody differentiates arrives as None, not as zeros
+        ctx.extra = (None,) * len(opt)                        # backward returns one entry per argument of this call
+        if not trans_grad:
+            ctx.mark_non_differentiable(trans)
         return out, trans
 
     @staticmethod
@@ -52,30 +60,46 @@ class _FK(torch.autograd.Function):
         dist = ctx.dist
         B, E = theta.shape
         P, N = parent.shape[0], x.shape[0]
-        G = g_out.contiguous().float()
+        need_x = ctx.needs_input_grad[0]
         g_axis, g_moment, g_theta = torch.empty_like(axis), torch.empty_like(moment), torch.empty_like(theta)
         g_dist = None if dist is None else torch.empty_like(dist)
         L = _lib.lib()
-        ws = _lib.workspace(L.reart_fk_backward_workspace_bytes(P, B, E), x.device)
-        rc = L.reart_fk_backward(_lib.ptr(x), _lib.ptr(part), _lib.ptr(G), N, _lib.ptr(parent), _lib.ptr(edge_of),
-                                 _lib.ptr(order), P, _lib.ptr(axis), _lib.ptr(moment), _lib.ptr(theta), _lib.ptr(dist),
-                                 B, E, _lib.ptr(trans), _lib.ptr(g_axis), _lib.ptr(g_moment), _lib.ptr(g_theta),
-                                 _lib.ptr(g_dist), _lib.ptr(ws), ws.numel(), _lib.stream())
-        _lib.check(rc, "reart_fk_backward")
-        return None, None, g_axis, g_moment, g_theta, g_dist, None, None, None
+        ws = _lib.workspace(L.reart_fk_backward_workspace_bytes(P, B, E), theta.device)
+        if g_trans is None and not need_x and N > 0:             # the loss reads pc_trans only and the cloud is a constant
+            G = g_out.contiguous().float()
+            rc = L.reart_fk_backward(_lib.ptr(x), _lib.ptr(part), _lib.ptr(G), N, _lib.ptr(parent), _lib.ptr(edge_of),
+                                     _lib.ptr(order), P, _lib.ptr(axis), _lib.ptr(moment), _lib.ptr(theta), _lib.ptr(dist),
+                                     B, E, _lib.ptr(trans), _lib.ptr(g_axis), _lib.ptr(g_moment), _lib.ptr(g_theta),
+                                     _lib.ptr(g_dist), _lib.ptr(ws), ws.numel(), _lib.stream())
+            _lib.check(rc, "reart_fk_backward")
+            return (None, None, g_axis, g_moment, g_theta, g_dist, None, None, None) + ctx.extra
+        pts = g_out is not None and N > 0                         # else the cloud took no part in the loss: N = 0 to the kernels
+        G = g_out.contiguous().float() if pts else None
+        Gt = None if g_trans is None else g_trans.contiguous().float()
+        g_x = torch.empty_like(x) if need_x and pts else None
+        rc = L.reart_fk_backward_trans(_lib.ptr(x if pts else None), _lib.ptr(part if pts else None), _lib.ptr(G), N if pts else 0,
+                                       _lib.ptr(parent), _lib.ptr(edge_of), _lib.ptr(order), P, _lib.ptr(axis), _lib.ptr(moment),
+                                       _lib.ptr(theta), _lib.ptr(dist), B, E, _lib.ptr(trans), _lib.ptr(Gt), _lib.ptr(g_axis),
+                                       _lib.ptr(g_moment), _lib.ptr(g_theta), _lib.ptr(g_dist), _lib.ptr(g_x), _lib.ptr(ws),
+                                       ws.numel(), _lib.stream())
+        _lib.check(rc, "reart_fk_backward_trans")
+        if need_x and g_x is None:
+            g_x = torch.zeros_like(x)
+        return (g_x, None, g_axis, g_moment, g_theta, g_dist, None, None, None) + ctx.extra
 
 
 def fk(paths_to_base, reverse_topo, edge_index, axis_list, moment_list, theta_list, distance_list=None,
        joint_type_list=None):
     """Forward kinematics over screw joints -> [T, P, 4, 4] (utils/kinematic_utils.py:151-198).
     ``paths_to_base`` is accepted for signature compatibility; with parts visited root to leaf the
-    reference's path walk always stops at the first edge, so the tree's parent links suffice."""
+    reference's path walk always stops at the first edge, so the tree's parent links suffice.
+    Differentiable w.r.t. ``axis_list``, ``moment_list``, ``theta_list`` and ``distance_list``."""
     dev = theta_list.device
     parent, edge_of, order = (torch.from_numpy(a).to(dev) for a in tree_arrays(edge_index, reverse_topo))
     theta, dist = _effective_joint_values(theta_list, distance_list, joint_type_list)
-    dummy_x = torch.zeros((1, 3), device=dev)
-    dummy_part = torch.zeros((1,), dtype=torch.long, device=dev)
-    _, trans = _FK.apply(dummy_x, dummy_part, axis_list, moment_list, theta, dist, parent, edge_of, order)
+    no_x = torch.empty((0, 3), device=dev)
+    no_part = torch.empty((0,), dtype=torch.long, device=dev)
+    _, trans = _FK.apply(no_x, no_part, axis_list, moment_list, theta, dist, parent, edge_of, order, True)
     return trans
 
 

@@ -26,13 +26,7 @@ def create_transformation(rotation, translation):
     return th_with_zeros(top)
 
 
-def compute_pc_transform(cano_pc, pose_list, cano_part):
-    """Apply each point's part transform (utils/model_utils.py:54-67):
-    cano_pc [N,3], pose_list [T-1,P,4,4], cano_part [N] -> [T-1,N,3]."""
-    _lib.require_gpu(cano_pc, pose_list, cano_part)
-    cano = cano_pc.contiguous().float()
-    pose = pose_list.contiguous().float()
-    part = cano_part.contiguous().long()
+def _pc_transform(cano, pose, part):
     B, P = pose.shape[:2]
     N = cano.shape[0]
     out = torch.empty((B, N, 3), dtype=torch.float32, device=cano.device)
@@ -40,6 +34,45 @@ def compute_pc_transform(cano_pc, pose_list, cano_part):
                                                _lib.ptr(out), _lib.stream())
     _lib.check(rc, "reart_compute_pc_transform")
     return out
+
+
+class _PcTransform(torch.autograd.Function):
+    """compute_pc_transform with its gradients w.r.t. the cloud and the poses (reart_compute_pc_transform_backward)."""
+
+    @staticmethod
+    def forward(ctx, cano, pose, part):
+        ctx.save_for_backward(cano, pose, part)
+        return _pc_transform(cano, pose, part)
+
+    @staticmethod
+    def backward(ctx, g_out):
+        cano, pose, part = ctx.saved_tensors
+        (B, P), N = pose.shape[:2], cano.shape[0]
+        G = g_out.contiguous().float()
+        g_cano = torch.empty_like(cano) if ctx.needs_input_grad[0] else None
+        g_pose = torch.empty_like(pose) if ctx.needs_input_grad[1] else None
+        L = _lib.lib()
+        ws = _lib.workspace(L.reart_compute_pc_transform_backward_workspace_bytes(N, P, B), cano.device)
+        rc = L.reart_compute_pc_transform_backward(_lib.ptr(cano), _lib.ptr(pose), _lib.ptr(part), _lib.ptr(G), N, P, B,
+                                                   _lib.ptr(g_cano), _lib.ptr(g_pose), _lib.ptr(ws), ws.numel(), _lib.stream())
+        _lib.check(rc, "reart_compute_pc_transform_backward")
+        return g_cano, g_pose, None
+
+
+def compute_pc_transform(cano_pc, pose_list, cano_part):
+    """Apply each point's part transform (utils/model_utils.py:54-67):
+    cano_pc [N,3], pose_list [T-1,P,4,4], cano_part [N] -> [T-1,N,3].  Differentiable w.r.t. ``cano_pc`` and ``pose_list``
+    (row 3 of a pose is a constant of the apply: its gradient is zero)."""
+    _lib.require_gpu(cano_pc, pose_list, cano_part)
+    cano = cano_pc.contiguous().float()
+    pose = pose_list.contiguous().float()
+    part = cano_part.contiguous().long()
+    if cano.requires_grad or pose.requires_grad:
+        if pose.shape[1] > _lib.PC_GRAD_MAX_P:
+            raise NotImplementedError(f"{pose.shape[1]} parts: the gradient of compute_pc_transform takes at most "
+                                      f"{_lib.PC_GRAD_MAX_P}")
+        return _PcTransform.apply(cano, pose, part)
+    return _pc_transform(cano, pose, part)
 
 
 def _row_mode(values):
