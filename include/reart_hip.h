@@ -1028,6 +1028,38 @@ int reart_screw_fit(const float *trans, int T, int P, const int32_t *pairs, int 
                     float *screw, float *rel, float *mean, float *recon, float *cost, float *mean_cost,
                     void *workspace, size_t workspace_bytes, void *stream);
 
+/* The screw-consistency term of networks/loss.py structure_loss (:32-57) with its gradient, as an operator of an
+ * iteration: parallel over (edge, frame), at most two launches, no host synchronisation, no atomics.
+ *   trans [T,P,4,4] and pairs [E,2] i32 (src, tgt) exactly as reart_screw_fit reads them; pairs == NULL: trans IS the
+ *   relative motion [T,E,4,4] (P ignored).  Per edge e = (a, b) and frame t, with M = inv(trans[t,a]) * trans[t,b] and
+ *   (l, m, theta, d) its screw parameters:
+ *     unit(t,e)    = (|theta| <= 1e-5 or |theta - pi| <= 1e-5) and d <= 1e-5            (d signed)
+ *     mean l, m    over the non-unit frames of e; over all frames when there is none or E <= 1
+ *     prismatic(e) = mean_t |d| > mean_t |theta|            (structure_loss's rule, not reart_screw_fit's cost rule)
+ *     G(t,e)       = screw -> SE(3) of (mean l, mean m, prismatic ? 1e-6f : theta, prismatic ? d : 1e-6f)
+ *     edge_cost[e] = sum_t |M inv(G) - I|^2_F,   loss = weight * sum_e edge_cost[e]   (added in double, rounded once)
+ *   G is a constant (the reference builds it under no_grad): grad = dloss/dtrans runs through M only,
+ *   dloss/dM = 2 weight (M inv(G) - I) inv(G)^T on rows 0..2, carried to trans[t,a] and trans[t,b] through the rigid
+ *   inverse [R^T | -R^T t].  grad has the shape of trans and is written completely: zeros where nothing arrives and in
+ *   row 3, which holds constants (the reference's 4x4 products leave a non-zero gradient there that reaches no parameter).
+ *   A part's gradient is the sum over its incident edges in ascending edge number: the same bits on every run.
+ * Outputs: loss (required), edge_cost [E], prismatic [E] u8, grad (all three nullable).
+ * T <= REART_MAX_POSE_LEN, P <= 64, E <= 4096: beyond them the workspace query returns 0 and the call
+ * REART_ERR_UNSUPPORTED.  NULL trans / loss, T or P <= 0, E < 0, a NULL or short workspace: REART_ERR_INVALID_ARG.
+ * E == 0: loss 0, grad zeros.  A pair index outside [0,P) is the caller's error (such an edge is skipped). */
+size_t reart_structure_term_workspace_bytes(int T, int P, int E);
+int reart_structure_term(const float *trans, int T, int P, const int32_t *pairs, int E, float weight, float *loss,
+                         float *edge_cost, uint8_t *prismatic, float *grad, void *workspace, size_t workspace_bytes,
+                         void *stream);
+
+/* Reverse mode of rel[t,e] = inv(trans[t,src]) * trans[t,tgt] (reart_screw_fit's `rel`, compute_relative_trans of
+ * utils/graph_utils.py:162-175) with the rigid inverse: grad_rel [T,E,4,4] (row 3 ignored) -> grad_trans [T,P,4,4],
+ * written completely, row 3 zero, a part's sum over its incident edges in ascending edge number.  Limits and statuses
+ * as reart_structure_term; pairs is required. */
+size_t reart_rel_trans_backward_workspace_bytes(int T, int P, int E);
+int reart_rel_trans_backward(const float *trans, int T, int P, const int32_t *pairs, int E, const float *grad_rel,
+                             float *grad_trans, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Replaces fps_sample_cano (utils/graph_utils.py:37-52): farthest point sampling inside every part, one
  * workgroup per part.  cano [N,3], seg [N] i64, labels [Ps] i64 -> idx [Ps,num_fps] i64 (indices into cano,
  * start = the part's first point like the reference's CUDA FPS; -1 when the part has fewer than num_fps

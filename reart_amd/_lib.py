@@ -26,7 +26,9 @@ LAP_LARGE_MAX_N = 8192   # REART_LAP_LARGE_MAX_N: columns of reart_lap_auction_l
 FPS_MAX_N_LDS = 12288    # REART_FPS_MAX_N_LDS: reart_fps, cloud staged in LDS
 FPS_MAX_N = 1 << 21      # REART_FPS_MAX_N: reart_fps_temp, 21-bit index in the tie key
 PC_GRAD_MAX_P = 1024     # parts of reart_compute_pc_transform_backward: one frame's pose rows staged in LDS
-ADAM_MAX_TENSORS = 32    # REART_ADAM_MAX_TENSORS: records of one reart_adam_groups call, passed by value to its kernel
+STRUCT_MAX_P = 64        # parts of reart_structure_term / reart_rel_trans_backward, as the kinematic entries
+STRUCT_MAX_E = 4096      # their edges: a part's incidence list is held in LDS
+ADAM_MAX_TENSORS = 32   # REART_ADAM_MAX_TENSORS: records of one reart_adam_groups call, passed by value to its kernel
 
 # name -> (restype, argtypes); mirrors include/reart_hip.h one to one
 PROTOTYPES = {
@@ -137,6 +139,10 @@ PROTOTYPES = {
     "reart_match_smnn": (c_int, [P, P, c_int, c_int, c_int, c_int, c_float, P, P, P, c_size_t, P]),
     "reart_screw_fit_workspace_bytes": (c_size_t, [c_int] * 2),
     "reart_screw_fit": (c_int, [P, c_int, c_int, P, c_int, c_int, P, P, P, P, P, P, P, c_size_t, P]),
+    "reart_structure_term_workspace_bytes": (c_size_t, [c_int] * 3),
+    "reart_structure_term": (c_int, [P, c_int, c_int, P, c_int, c_float, P, P, P, P, P, c_size_t, P]),
+    "reart_rel_trans_backward_workspace_bytes": (c_size_t, [c_int] * 3),
+    "reart_rel_trans_backward": (c_int, [P, c_int, c_int, P, c_int, P, P, P, c_size_t, P]),
     "reart_part_fps": (c_int, [P, P, c_int, P, c_int, c_int, c_int, P, P, P]),
     "reart_part_pair_cost": (c_int, [P, P, c_int, c_int, c_int, P, P, P, P]),
     "reart_group_temporal_err": (c_int, [P, c_int, c_int, P, P, c_int, P, P, P]),

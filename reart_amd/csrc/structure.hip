@@ -18,115 +18,6 @@
 #include "screw_dev.h"
 #include <math.h>
 
-// ------------------------------------------------------------------------------------------------------------
-// relative transform inv(A) * B of two [R|t] (4x4 row-major in memory) -> 3x4
-__device__ __forceinline__ void rel_transform(const float *A, const float *B, float *M) {
-    float tinv[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)  // -R_a^T t_a
-        tinv[i] = (-A[i] * A[3] + -A[4 + i] * A[7]) + -A[8 + i] * A[11];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) M[4 * i + j] = (A[i] * B[j] + A[4 + i] * B[4 + j]) + A[8 + i] * B[8 + j];
-        M[4 * i + 3] = ((A[i] * B[3] + A[4 + i] * B[7]) + A[8 + i] * B[11]) + tinv[i];
-    }
-}
-
-__device__ __forceinline__ void q_mul(const float *q1, const float *q2, float *o) {  // dq_utils.py:63-83
-    o[0] = ((q2[0] * q1[0] - q2[1] * q1[1]) - q2[2] * q1[2]) - q2[3] * q1[3];
-    o[1] = ((q2[0] * q1[1] + q2[1] * q1[0]) - q2[2] * q1[3]) + q2[3] * q1[2];
-    o[2] = ((q2[0] * q1[2] + q2[1] * q1[3]) + q2[2] * q1[0]) - q2[3] * q1[1];
-    o[3] = ((q2[0] * q1[3] - q2[1] * q1[2]) + q2[2] * q1[1]) + q2[3] * q1[0];
-}
-
-// rigid transform M (3x4) -> screw parameters: axis l, moment m, angle theta, displacement d
-__device__ __forceinline__ void transform_to_screw(const float *M, float *l, float *m, float &theta, float &d) {
-    const float eps = 1e-6f;
-    const float m00 = M[0], m01 = M[1], m02 = M[2], m10 = M[4], m11 = M[5], m12 = M[6], m20 = M[8], m21 = M[9], m22 = M[10];
-    const float a[4] = {((1.0f + m00) + m11) + m22, ((1.0f + m00) - m11) - m22, ((1.0f - m00) + m11) - m22,
-                        ((1.0f - m00) - m11) + m22};
-    float qa[4];
-    int best = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        qa[i] = a[i] > 0.f ? sqrtf(a[i]) : 0.f;
-        if (qa[i] > qa[best]) best = i;  // first maximum
-    }
-    float c[4];
-    if (best == 0) { c[0] = qa[0] * qa[0]; c[1] = m21 - m12; c[2] = m02 - m20; c[3] = m10 - m01; }
-    else if (best == 1) { c[0] = m21 - m12; c[1] = qa[1] * qa[1]; c[2] = m10 + m01; c[3] = m02 + m20; }
-    else if (best == 2) { c[0] = m02 - m20; c[1] = m10 + m01; c[2] = qa[2] * qa[2]; c[3] = m12 + m21; }
-    else { c[0] = m10 - m01; c[1] = m20 + m02; c[2] = m21 + m12; c[3] = qa[3] * qa[3]; }
-    const float den = 2.0f * fmaxf(qa[best], 0.1f);
-    float qr[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) qr[i] = c[i] / den;
-    const float tq[4] = {0.f, M[3], M[7], M[11]};
-    float qd[4];
-    q_mul(tq, qr, qd);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) qd[i] *= 0.5f;
-    const float nq = sqrtf(((qr[0] * qr[0] + qr[1] * qr[1]) + qr[2] * qr[2]) + qr[3] * qr[3]);
-    const float qn[4] = {qr[0] / nq, qr[1] / nq, qr[2] / nq, qr[3] / nq};
-    const float nim = sqrtf((qn[1] * qn[1] + qn[2] * qn[2]) + qn[3] * qn[3]);
-    float th = 2.0f * atan2f(nim, qn[0]);
-    const bool no_rot = (fabsf(th) < eps) || (fabsf(th - PI_F) < eps);
-    const float conj[4] = {qr[0], -qr[1], -qr[2], -qr[3]};
-    const float qd2[4] = {2.0f * qd[0], 2.0f * qd[1], 2.0f * qd[2], 2.0f * qd[3]};
-    float tt[4];
-    q_mul(qd2, conj, tt);
-    const float t[3] = {tt[1], tt[2], tt[3]};
-    float dd;
-    if (!no_rot) {
-        const float s = sinf(th / 2.0f);
-        l[0] = qr[1] / s; l[1] = qr[2] / s; l[2] = qr[3] / s;
-        dd = 0.f;
-    } else {
-        dd = sqrtf((t[0] * t[0] + t[1] * t[1]) + t[2] * t[2]);
-        const float dn = dd + 1e-10f;
-        l[0] = t[0] / dn; l[1] = t[1] / dn; l[2] = t[2] / dn;
-    }
-    const float cs = (l[0] + l[1]) + l[2];
-    if (!(cs >= 0.f)) { th = -th; l[0] = -l[0]; l[1] = -l[1]; l[2] = -l[2]; if (no_rot) dd = -dd; }
-    if (!no_rot) dd = (t[0] * l[0] + t[1] * l[1]) + t[2] * l[2];
-    // torch.isclose(d, 0): |d| <= 1e-8
-    if (no_rot && fabsf(dd) <= 1e-8f) l[0] = 1.0f;
-    if (no_rot) th = eps;
-    const float tl[3] = {t[1] * l[2] - t[2] * l[1], t[2] * l[0] - t[0] * l[2], t[0] * l[1] - t[1] * l[0]};
-    const float tn = tanf(th / 2.0f);
-    const float u[3] = {tl[0] / tn, tl[1] / tn, tl[2] / tn};
-    m[0] = 0.5f * (tl[0] + (l[1] * u[2] - l[2] * u[1]));
-    m[1] = 0.5f * (tl[1] + (l[2] * u[0] - l[0] * u[2]));
-    m[2] = 0.5f * (tl[2] + (l[0] * u[1] - l[1] * u[0]));
-    theta = th;
-    d = dd;
-}
-
-// sum of squares of (P * inv(G) - I) for two 3x4 rigid transforms (frobenius_cost; the 4th row contributes 0)
-__device__ __forceinline__ float frob_cost(const float *Pm, const float *Gm) {
-    // inv(G) = [G_R^T | -G_R^T g_t]
-    float gi[12];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) gi[4 * i + j] = Gm[4 * j + i];
-        gi[4 * i + 3] = (-Gm[i] * Gm[3] + -Gm[4 + i] * Gm[7]) + -Gm[8 + i] * Gm[11];
-    }
-    float acc = 0.f;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const float e = ((Pm[4 * i] * gi[j] + Pm[4 * i + 1] * gi[4 + j]) + Pm[4 * i + 2] * gi[8 + j]) - (i == j ? 1.f : 0.f);
-            acc += e * e;
-        }
-        const float e = ((Pm[4 * i] * gi[3] + Pm[4 * i + 1] * gi[7]) + Pm[4 * i + 2] * gi[11]) + Pm[4 * i + 3];
-        acc += e * e;
-    }
-    return acc;
-}
-
 #define SF_BS 256
 
 struct ScrewFitArgs {

@@ -132,15 +132,54 @@ def denoise_seg_label(cano_part, cano_pc, knn, min_num=10):
     return cano_part
 
 
+class _RelTransFn(torch.autograd.Function):
+    """rel = inv(T_src) T_tgt of ``screw_fit`` with a graph to ``trans_list``: the backward is ``reart_rel_trans_backward``
+    (rows 0..2 of the upstream; the gradient's row 3 is zero)."""
+
+    @staticmethod
+    def forward(ctx, trans_list, pairs, rel):
+        ctx.save_for_backward(trans_list.detach().contiguous(), pairs.to(torch.int32).contiguous())
+        return rel.view_as(rel)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        tr, pp = ctx.saved_tensors
+        T, P, E = tr.shape[0], tr.shape[1], pp.shape[0]
+        g = g.contiguous().float()
+        out = torch.empty_like(tr)
+        L = _lib.lib()
+        ws = _lib.workspace(L.reart_rel_trans_backward_workspace_bytes(T, P, E), tr.device)
+        rc = L.reart_rel_trans_backward(_lib.ptr(tr), T, P, _lib.ptr(pp), E, _lib.ptr(g), _lib.ptr(out), _lib.ptr(ws),
+                                        ws.numel(), _lib.stream())
+        _lib.check(rc, "reart_rel_trans_backward")
+        return out, None, None
+
+
 def compute_relative_trans(trans_list, return_trans=False):
-    """utils/graph_utils.py:170-186: screw parameters of inv(T_i) T_j for all ordered part pairs and frames."""
+    """utils/graph_utils.py:170-186: screw parameters of inv(T_i) T_j for all ordered part pairs and frames.
+    With ``return_trans`` and a ``trans_list`` that requires grad, the returned relative transforms carry a graph to
+    ``trans_list`` (``reart_rel_trans_backward``; float32, T <= 1024, P <= 64); their values are the same bits either way.
+    The four screw-parameter outputs carry no graph: the reference's run through ``dq_to_screw``'s masked writes, and
+    nothing in the reference differentiates them."""
     T, P = trans_list.shape[:2]
+    with_graph = return_trans and trans_list.requires_grad and torch.is_grad_enabled()
+    if with_graph:
+        _lib.require_gpu(trans_list)
+        if trans_list.dtype != torch.float32:
+            raise TypeError(f"compute_relative_trans: gradients for float32 transforms, not {trans_list.dtype}")
+        if T > _lib.MAX_POSE_LEN or P > _lib.STRUCT_MAX_P:
+            raise NotImplementedError(f"compute_relative_trans: gradients for T <= {_lib.MAX_POSE_LEN} frames and "
+                                      f"P <= {_lib.STRUCT_MAX_P} parts, not T = {T}, P = {P}")
     ar = torch.arange(P, device=trans_list.device)
     pairs = torch.stack([ar.repeat_interleave(P), ar.repeat(P)], dim=1)
     f = screw_fit(trans_list, pairs, want=("screw", "rel"))
     s = f["screw"].reshape(T, P, P, 8)
     res = (s[..., 0:3], s[..., 3:6], s[..., 6], s[..., 7])
-    return res + (f["rel"].reshape(T, P, P, 4, 4),) if return_trans else res
+    if not return_trans:
+        return res
+    rel = _RelTransFn.apply(trans_list, pairs, f["rel"]) if with_graph else f["rel"]
+    return res + (rel.reshape(T, P, P, 4, 4),)
 
 
 def compute_geo_cost(rel_trans, axis=None, moment=None, theta=None, distance=None):
