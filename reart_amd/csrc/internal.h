@@ -41,6 +41,10 @@ struct BaseBwdArgs {
     int cpts;                   // points per backward workgroup: 64, 32 or 16 (0: the default, 32)
     int dp_sep;                 // set by the launcher: the hidden gradient has an LDS tile of its own (else it overwrites the h tile)
     float *partial;             // [nchunk][n_out]
+    // fused step only: the Adam step sizes the finalize launch BEHIND this block launch reads (FinalizeAdam::step) are
+    // promoted here, from the slot the previous finalize launch's bookkeeping workgroup wrote.  NULL: no promotion
+    const float *step_next;     // [4]
+    float *step_cur;            // [4]
     // finalize
     float *gW1, *gb1, *gW2, *g6d, *gt;
 };
@@ -71,20 +75,23 @@ struct FinalizeAdam {
     float seg_lr, trans_lr, beta1, beta2, eps;
     float weight_decay;               // torch.optim.Adam's L2 form: g += weight_decay * p
     const int64_t *step_ptr;
-    const double *bias_corr;          // device [2]: 1 - beta1^step, sqrt(1 - beta2^step) of the coming step
+    // device [4], the step sizes of THIS step (with bc1 = 1 - beta1^step, bc2 = sqrt(1 - beta2^step) in double):
+    // (float)((double)seg_lr / bc1), (float)((double)trans_lr / bc1), (float)bc2, unused
+    const float *step;
 };
 
 // Fused step only: end-of-iteration bookkeeping (loss log, iteration counter, next temperature and
-// Adam bias corrections), done by the LAST finishing workgroup of the finalize kernel -- by then
-// every other workgroup has read this iteration's counters, so no extra launch is needed.
+// Adam step sizes), done by ONE EXTRA workgroup of the finalize kernel (the last blockIdx.x).  No other
+// workgroup of that launch reads `iter` or `tau`; the step sizes they do read (FinalizeAdam::step) are
+// another slot than the one written here (`step_next`), which the next backward block launch promotes.
 struct StepBook {
     int enabled;
     const double *frame_loss; int n_frame_part;
     const double *flow_part; int n_flow_part;
-    int64_t *iter; float *tau; float *losses; double *bias_corr;
-    unsigned int *ticket;      // device counter, zero between launches
+    int64_t *iter; float *tau; float *losses;
+    float *step_next;          // [4]: FinalizeAdam::step of the NEXT step
     int ring, n_iter;
-    float lambda_flow, fixed_tau, end_tau, start_tau, beta1, beta2;
+    float lambda_flow, fixed_tau, end_tau, start_tau, beta1, beta2, seg_lr, trans_lr;
 };
 int reart_base_backward_launch(const BaseBwdArgs *args, const FinalizeAdam *adam, const StepBook *book, void *const *workspaces,
                                size_t workspace_bytes, int K, hipStream_t st, int force_long);     // adam / book: arrays of K, or NULL

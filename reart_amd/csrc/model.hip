@@ -655,10 +655,16 @@ __global__ __launch_bounds__(64 * BW_WAVES) void base_bwd_block_kernel(Batched<B
                      (((uintptr_t)a.hT | (uintptr_t)a.yT | (uintptr_t)a.G | (uintptr_t)a.gpf | (uintptr_t)a.rt_table | (uintptr_t)a.W2) & 15) == 0;
     float x0 = 0.f, x1 = 0.f, x2 = 0.f;
     int kn = -1;
+    // Fused step: thread 0 of workgroup 0 promotes the Adam step sizes the bookkeeping workgroup of the previous finalize
+    // launch left in step_next to step_cur, which the finalize launch behind this one reads (no workgroup of THIS launch
+    // reads either).  The load rides in the batch; the store goes out with the point's, nobody waits for it.
+    const bool promote = a.step_next != nullptr && chunk == 0 && tid == 0;
+    float4 stp = make_float4(0.f, 0.f, 0.f, 0.f);
     auto load_point = [&]() {
         if (grp == 0) {
             x0 = a.cano[3 * (size_t)n]; x1 = a.cano[3 * (size_t)n + 1]; x2 = a.cano[3 * (size_t)n + 2];
             kn = live ? a.hard_idx[n] : -1;
+            if (promote) stp = *(const float4 *)a.step_next;
         }
     };
     if (PP == 20 && vec && a.H == 128 && a.B == 19 && a.cpts == 32 && cn == 32)
@@ -670,6 +676,7 @@ __global__ __launch_bounds__(64 * BW_WAVES) void base_bwd_block_kernel(Batched<B
     if (grp == 0) {
         s_x[3 * lane] = live ? x0 : 0.f; s_x[3 * lane + 1] = live ? x1 : 0.f; s_x[3 * lane + 2] = live ? x2 : 0.f;
         s_kn[lane] = kn;
+        if (promote) *(float4 *)a.step_cur = stp;
     }
     PHASE_TS(1, 11);
     // a. dw[n,p] = sum_t G[t,n] . (R[t,p] x_n + t[t,p]) as ONE matrix product on the matrix cores:
@@ -902,19 +909,20 @@ __device__ __forceinline__ void adam_update(float *p, float g, float *m, float *
 __device__ __forceinline__ void base_bwd_finalize_body(const BaseBwdArgs &a, const FinalizeAdam &ad) {
     // Every output is summed over the partial rows by FOUR lanes, a quarter of the rows each (one batch of loads in
     // flight per lane at 128 rows instead of four dependent batches), combined in a fixed order by two xor-shuffles.
-    // Everything else a lane needs from memory -- the bias corrections of this step, the parameter it updates with its
+    // Everything else a lane needs from memory -- the step sizes of this step, the parameter it updates with its
     // two moments, the 6-vector of the Gram-Schmidt backward -- is independent of the gradient and is loaded IN FRONT of
-    // the partial rows, so the whole body is one memory round trip deep; the divisions of the bias corrections stand
-    // behind the sums (in front of them they delayed the first partial load by a scalar round trip).
+    // the partial rows, so the whole body is one memory round trip deep.  The step sizes come ready-made (lr / bias
+    // correction, divided once in double by whoever wrote ad.step): behind the sums a lane has single-precision
+    // arithmetic only.
     const int og = blockIdx.x * 256 + threadIdx.x;
     const int nWr = a.P * a.H + 4 * a.H;                 // real weight entries
     const int nW = (4 * nWr + 63) & ~63;                 // four lanes per weight; pose groups start wave-aligned
     const int RQ = (a.nchunk + 3) >> 2;                  // rows per quarter
     const int o = og >> 2;                               // weight entry of this lane (first branch)
     const int no = n_out(a.P, a.H, a.B);
-    // bias corrections of THIS step, written by the previous bookkeeping kernel / prepare
-    double bc1 = 1.0, bc2 = 1.0;
-    if (ad.enabled) { bc1 = ad.bias_corr[0]; bc2 = ad.bias_corr[1]; }
+    // step sizes of THIS step: written by prepare or the previous bookkeeping workgroup, promoted by the block launch
+    float ss_seg = 0.f, ss_tr = 0.f, bc2s = 1.f;
+    if (ad.enabled) { ss_seg = ad.step[0]; ss_tr = ad.step[1]; bc2s = ad.step[2]; }
     if (og < nW) {
         if (o >= nWr) return;                            // whole quads leave together
         // partial-row order is W2 | W1 | b1; moment order is W1 | b1 | W2
@@ -952,7 +960,6 @@ __device__ __forceinline__ void base_bwd_finalize_body(const BaseBwdArgs &a, con
         acc = acc + __shfl_xor(acc, 1, 64);              // (q0 + q1), (q2 + q3): commutative, every lane of the quad agrees
         acc = acc + __shfl_xor(acc, 2, 64);
         if (og & 3) return;
-        const float ss_seg = (float)((double)ad.seg_lr / bc1), bc2s = (float)bc2;
         if (kind == 0) {
             a.gW2[q] = acc;
             if (ad.enabled) adam_update(ad.W2 + q, acc, ad.m + mo, ad.v + mo, ld, ad.seg_lr, ss_seg, bc2s, ad.beta1, ad.beta2, ad.eps, ad.weight_decay);
@@ -1005,7 +1012,6 @@ __device__ __forceinline__ void base_bwd_finalize_body(const BaseBwdArgs &a, con
         if (c >= 9 || tq != 0) return;
         float g6[6];
         r6d_backward(d6, gRt, g6);
-        const float ss_tr = (float)((double)ad.trans_lr / bc1), bc2s = (float)bc2;
         float g;
         if (c < 6) {
             g = g6[0];
@@ -1020,67 +1026,71 @@ __device__ __forceinline__ void base_bwd_finalize_body(const BaseBwdArgs &a, con
     }
 }
 
-// 256 threads of column sums / pose gradients / Adam (base_bwd_finalize_body) + TWO MORE WAVES for the bookkeeping.
-template <bool BATCH>
-__global__ __launch_bounds__(384) void base_bwd_finalize_kernel(Batched<BaseBwdArgs> ab, Batched<FinalizeAdam> adb, Batched<StepBook> bkb) {
-    const BaseBwdArgs &a = ab.a[BATCH ? blockIdx.y : 0];
-    const FinalizeAdam &ad = adb.a[BATCH ? blockIdx.y : 0];
-    const StepBook &bk = bkb.a[BATCH ? blockIdx.y : 0];
-    // Bookkeeping is done by the LAST workgroup to finish (ticket): by then every other workgroup has
-    // consumed this iteration's counters.  Every workgroup prepares it speculatively -- the loss partials
-    // are summed (fifth wave) and the next temperature / bias corrections computed (sixth wave: two double-
-    // precision pow, a sqrt, a cosine: 2.2 us on one lane) -- beside the four waves that run the main work
-    // (1.8 us), not in front of them (profiles/r05_small_kernel_clocks.txt); the winner only has to store.
-    __shared__ int s_last;
-    __shared__ double s_book[4];       // recon, flow (x lambda), bias corrections of the next step
-    __shared__ float s_tau;
-    __shared__ long s_it;
-    const int tid = threadIdx.x;
+// End-of-iteration bookkeeping of the fused step, run by ONE workgroup of the finalize launch (the extra, last one) beside
+// the body workgroups: nothing it writes is read by any of them (StepBook, internal.h), so nobody waits for anybody.  The
+// four waves share the work -- wave 0 sums the loss partials, lane 0 of waves 1 / 2 / 3 evaluates one double-precision
+// chain each (pow and the two step sizes | pow and sqrt | the cosine of the next temperature; on ONE lane they took 2.2 us,
+// profiles/r05_small_kernel_clocks.txt) -- and each stores what it computed.  The one barrier stands between the reads of
+// `iter` and `tau` (every wave) and their stores.
+__device__ __forceinline__ void base_bwd_finalize_book(const StepBook &bk) {
+    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
 #ifdef REART_PHASE_CLOCK
-    if (blockIdx.x == 1 && blockIdx.y == 0 && threadIdx.x == 0) { g_phase_ts[0][14] = __builtin_amdgcn_s_memtime(); g_phase_ts[0][8] = g_phase_ts[0][14]; }
+    if (blockIdx.y == 0 && threadIdx.x == 0) g_phase_ts[0][10] = __builtin_amdgcn_s_memtime();
 #endif
-    if (tid >= 320) {                  // sixth wave: the scalars of the next step (no memory but the iteration counter)
-        if (!bk.enabled) return;
-        if (tid == 320) {
-            const long it = (long)bk.iter[0];
-            s_it = it;
-            s_book[2] = 1.0 - pow((double)bk.beta1, (double)(it + 2));   // Adam step count of the next iteration
-            s_book[3] = sqrt(1.0 - pow((double)bk.beta2, (double)(it + 2)));
-            // iteration i (0-based) uses tau_cosine(i+1, ...) (run_robot.py:157)
-            s_tau = bk.fixed_tau > 0.f ? bk.fixed_tau : reart_tau_schedule(it + 2, bk.n_iter, bk.end_tau, bk.start_tau);
-        }
-    } else if (tid >= 256) {           // fifth wave: the loss partials
-        if (!bk.enabled) return;
-        const int l = tid - 256;
+    const long it = (long)bk.iter[0];
+    const float tau_cur = bk.tau[0];
+    double recon = 0.0, flow = 0.0, bc = 1.0;
+    float tau_next = 0.f;
+    if (w == 0) {
         // fixed assignment of terms to lanes + fixed-order tree: deterministic sums
-        double recon = 0.0, flow = 0.0;
         for (int b = l; b < bk.n_frame_part; b += 64) recon += bk.frame_loss[b];
         for (int i = l; i < bk.n_flow_part; i += 64) flow += bk.flow_part[i];
         recon = reart_wave_sum_d(recon);
-        flow = reart_wave_sum_d(flow);
-        if (l == 0) { s_book[0] = recon; s_book[1] = flow * (double)bk.lambda_flow; }
-    } else base_bwd_finalize_body(a, ad);
+        flow = reart_wave_sum_d(flow) * (double)bk.lambda_flow;
+    } else if (l == 0) {
+        // Adam step count of the next iteration: it + 2
+        if (w == 1) bc = 1.0 - pow((double)bk.beta1, (double)(it + 2));
+        else if (w == 2) bc = sqrt(1.0 - pow((double)bk.beta2, (double)(it + 2)));
+        // iteration i (0-based) uses tau_cosine(i+1, ...) (run_robot.py:157)
+        else tau_next = bk.fixed_tau > 0.f ? bk.fixed_tau : reart_tau_schedule(it + 2, bk.n_iter, bk.end_tau, bk.start_tau);
+    }
+    __syncthreads();
+    if (l == 0) {
+        float *row = (bk.losses && bk.ring > 0) ? bk.losses + 4 * (size_t)(it % bk.ring) : nullptr;
+        if (w == 0) {
+            if (row) { row[0] = (float)recon; row[1] = (float)flow; row[2] = (float)(recon + flow); }
+        } else if (w == 1) {
+            bk.step_next[0] = (float)((double)bk.seg_lr / bc);
+            bk.step_next[1] = (float)((double)bk.trans_lr / bc);
+            bk.iter[0] = it + 1;
+        } else if (w == 2) {
+            bk.step_next[2] = (float)bc;
+        } else {
+            if (row) row[3] = tau_cur;     // the temperature this iteration used
+            bk.tau[0] = tau_next;
+        }
+    }
+#ifdef REART_PHASE_CLOCK
+    __syncthreads();   // diagnostic build only: the stamp is the slowest wave's end
+    if (blockIdx.y == 0 && threadIdx.x == 0) g_phase_ts[0][14] = __builtin_amdgcn_s_memtime();
+#endif
+}
+
+// 256 threads of column sums / pose gradients / Adam (base_bwd_finalize_body): no LDS, no barrier, no atomic.  With a step
+// book the grid has one workgroup more, the last, which runs base_bwd_finalize_book instead.
+template <bool BATCH>
+__global__ __launch_bounds__(256) void base_bwd_finalize_kernel(Batched<BaseBwdArgs> ab, Batched<FinalizeAdam> adb, Batched<StepBook> bkb) {
+    const StepBook &bk = bkb.a[BATCH ? blockIdx.y : 0];
+    if (bk.enabled && blockIdx.x == gridDim.x - 1) { base_bwd_finalize_book(bk); return; }
+    const BaseBwdArgs &a = ab.a[BATCH ? blockIdx.y : 0];
+    const FinalizeAdam &ad = adb.a[BATCH ? blockIdx.y : 0];
+#ifdef REART_PHASE_CLOCK
+    if (blockIdx.x == 1 && blockIdx.y == 0 && threadIdx.x == 0) g_phase_ts[0][8] = __builtin_amdgcn_s_memtime();
+#endif
+    base_bwd_finalize_body(a, ad);
 #ifdef REART_PHASE_CLOCK
     if (blockIdx.x == 1 && blockIdx.y == 0 && threadIdx.x == 0) g_phase_ts[0][9] = __builtin_amdgcn_s_memtime();
 #endif
-    if (!bk.enabled) return;
-    __syncthreads();   // every thread of this workgroup has read the counters it needs (values already used); s_book is written
-    if (tid == 0) s_last = (atomicAdd(bk.ticket, 1u) == gridDim.x - 1) ? 1 : 0;
-    __syncthreads();
-#ifdef REART_PHASE_CLOCK
-    if (blockIdx.x == 1 && blockIdx.y == 0 && threadIdx.x == 0) g_phase_ts[0][10] = __builtin_amdgcn_s_memtime();   // after the ticket's round trip
-#endif
-    if (!s_last || tid != 0) return;
-    const long it = s_it;
-    if (bk.losses && bk.ring > 0) {
-        float *row = bk.losses + 4 * (size_t)(it % bk.ring);
-        row[0] = (float)s_book[0]; row[1] = (float)s_book[1]; row[2] = (float)(s_book[0] + s_book[1]); row[3] = bk.tau[0];
-    }
-    bk.iter[0] = it + 1;
-    bk.bias_corr[0] = s_book[2];
-    bk.bias_corr[1] = s_book[3];
-    bk.tau[0] = s_tau;
-    *bk.ticket = 0u;
 }
 
 static size_t base_bwd_ws_layout(int N, int P, int B, int H, size_t *o_rt, size_t *o_part) {
@@ -1167,8 +1177,13 @@ int reart_base_backward_launch(const BaseBwdArgs *args, const FinalizeAdam *adam
     // weights: one thread per entry; poses: 16 lanes per (frame, part); nW is rounded up to a multiple of 64
     // inside the kernel's indexing so that a 16-lane group never straddles a wave
     const int nfin = (int)reart_align_up((size_t)4 * (a0.P * a0.H + 4 * a0.H), 64) + 64 * a0.B * a0.P;
-    if (K == 1) hipLaunchKernelGGL(base_bwd_finalize_kernel<false>, dim3(reart_div_up(nfin, 256)), dim3(384), 0, st, reart_batched(ak, 1), adb, bkb);
-    else hipLaunchKernelGGL(base_bwd_finalize_kernel<true>, dim3(reart_div_up(nfin, 256), K), dim3(384), 0, st, reart_batched(ak, K), adb, bkb);
+    // + the bookkeeping workgroup, in every instance plane or in none
+    int nbook = 0;
+    for (int k = 0; k < K; ++k) nbook += bkb.a[k].enabled ? 1 : 0;
+    if (nbook != 0 && nbook != K) return REART_ERR_INVALID_ARG;
+    const int nwg = reart_div_up(nfin, 256) + (nbook ? 1 : 0);
+    if (K == 1) hipLaunchKernelGGL(base_bwd_finalize_kernel<false>, dim3(nwg), dim3(256), 0, st, reart_batched(ak, 1), adb, bkb);
+    else hipLaunchKernelGGL(base_bwd_finalize_kernel<true>, dim3(nwg, K), dim3(256), 0, st, reart_batched(ak, K), adb, bkb);
     REART_CHECK_LAUNCH();
     return REART_OK;
 }

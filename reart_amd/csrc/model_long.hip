@@ -15,7 +15,8 @@
 //             dw = sum_t G[t].(R[t] x + t[t]) chains (accumulators stay in registers across tiles, ascending t: the
 //             in-LDS order), and the tile's own gR|gt partials, which depend on nothing but G, x and the hard part, are
 //             written.  After the last tile: softmax backward, gW2, dp, gW1 / gb1 as in the in-LDS kernel.  The partial
-//             row layout n_out(P, H, B) is the same, so base_bwd_finalize_kernel is reused unchanged.
+//             row layout n_out(P, H, B) is the same, so base_bwd_finalize_kernel is reused unchanged
+//             (like the in-LDS block kernel, this one promotes the Adam step sizes that launch reads).
 //             The next tile's global loads are issued before the current tile is consumed (one round trip deep, like the
 //             prologue).  No atomics; every sum in a fixed order; reruns are bit-identical.
 #include "common.h"
@@ -434,6 +435,10 @@ __global__ __launch_bounds__(64 * BW_WAVES) void base_bwd_long_kernel(Batched<Ba
         const float x0 = a.cano[3 * (size_t)n], x1 = a.cano[3 * (size_t)n + 1], x2 = a.cano[3 * (size_t)n + 2];
         int kn = -1;
         if (grp == 0) kn = live ? a.hard_idx[n] : -1;
+        // promotion of the Adam step sizes for the finalize launch behind this one, as in base_bwd_block_kernel
+        const bool promote = a.step_next != nullptr && chunk == 0 && tid == 0;
+        float4 stp = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (promote) stp = *(const float4 *)a.step_next;
         store_h(tid, vh);
 #pragma unroll
         for (int u = 0; u < UW; ++u) {
@@ -454,6 +459,7 @@ __global__ __launch_bounds__(64 * BW_WAVES) void base_bwd_long_kernel(Batched<Ba
             s_x[3 * lane] = live ? x0 : 0.f; s_x[3 * lane + 1] = live ? x1 : 0.f; s_x[3 * lane + 2] = live ? x2 : 0.f;
             s_kn[lane] = kn;
         }
+        if (promote) *(float4 *)a.step_cur = stp;
     }
     const int p0 = grp * FW_PG;
     const bool has0 = p0 < P, has1 = p0 + 1 < P;

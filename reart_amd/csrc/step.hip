@@ -22,8 +22,10 @@ struct StepPlan {
     size_t o_ysoa, o_xsoa, o_rsoa, o_rlen, o_qmap;
     size_t o_pd0, o_pi0, o_pd1, o_pi1, o_pd3, o_pi3;
     size_t o_yT, o_hT, o_hard, o_rt, o_G, o_gpf, o_fx, o_floss, o_fpart, o_grads, o_bwd;
-    size_t o_bc;              // Adam bias corrections of the coming step (double[2])
-    size_t o_ticket;          // last-workgroup ticket of the finalize kernel (zero between launches)
+    size_t o_bc;              // Adam step sizes (FinalizeAdam::step, float[4]) in two slots: [0..3] of the coming step, read by
+                              // the finalize bodies; [4..7] of the step after it, written by the bookkeeping workgroup and
+                              // promoted to the first slot by the next backward block launch
+    size_t o_ticket;          // [2..3] persistent-search counters ([0..1] unused)
     size_t o_boxY, o_boxX, o_boxR;  // AABBs of every NN_BOX targets (block-skip test)
     int keep_hT;              // the model runs on its long path (model_long.hip), whose backward reads the saved hidden layer
     int pruned;               // box-pruned, warm-started search (prune.hip) instead of the brute-force slice kernels
@@ -103,8 +105,8 @@ static int step_plan(const reart_relax_config *c, StepPlan *p) {
     p->o_grads = take(off, sizeof(float) * p->nparams);
     p->bwd_bytes = reart_base_backward_workspace_bytes(c->N, c->P, c->B, c->H);
     p->o_bwd = take(off, p->bwd_bytes);
-    p->o_bc = take(off, 2 * sizeof(double));
-    p->o_ticket = take(off, 4 * sizeof(unsigned int));   // [0] finalize ticket, [2..3] persistent-search counters
+    p->o_bc = take(off, 8 * sizeof(float));
+    p->o_ticket = take(off, 4 * sizeof(unsigned int));   // [2..3] persistent-search counters
     p->o_boxY = take(off, sizeof(float) * 8 * (size_t)c->B * (p->Npad / NN_BOX));
     p->o_boxX = take(off, sizeof(float) * 8 * (size_t)c->B * (p->Npad / NN_BOX));
     p->o_boxR = take(off, sizeof(float) * 8 * (size_t)c->B * (p->Mpad / NN_BOX + 1));
@@ -135,7 +137,7 @@ __global__ void relax_init_kernel(reart_relax_config c, const int *__restrict__ 
                                   int *__restrict__ rlen, int *__restrict__ qmap,
                                   int64_t *__restrict__ iter, float *__restrict__ tau,
                                   const float *__restrict__ pc_list, int *__restrict__ fx_bits,
-                                  double *__restrict__ bias_corr, int *__restrict__ seed3, int *__restrict__ border) {
+                                  float *__restrict__ adam_step, int *__restrict__ seed3, int *__restrict__ border) {
     __shared__ float s_max[1024];
     const int t = threadIdx.x;
     // warm start of the first k=3 search: any 3 distinct valid indices
@@ -176,8 +178,15 @@ __global__ void relax_init_kernel(reart_relax_config c, const int *__restrict__ 
         // `iter` is caller state: it is NOT reset here, so a resumed run continues its schedule
         const long it = (long)iter[0];
         tau[0] = c.fixed_tau > 0.f ? c.fixed_tau : reart_tau_schedule(it + 1, c.n_iter, c.end_tau, c.start_tau);
-        bias_corr[0] = 1.0 - pow((double)c.beta1, (double)(it + 1));
-        bias_corr[1] = sqrt(1.0 - pow((double)c.beta2, (double)(it + 1)));
+        // Adam step sizes of the coming step, in BOTH slots (StepPlan::o_bc): whichever launch comes first finds them
+        const double bc1 = 1.0 - pow((double)c.beta1, (double)(it + 1));
+        const double bc2 = sqrt(1.0 - pow((double)c.beta2, (double)(it + 1)));
+        for (int s = 0; s < 8; s += 4) {
+            adam_step[s] = (float)((double)c.seg_lr / bc1);
+            adam_step[s + 1] = (float)((double)c.trans_lr / bc1);
+            adam_step[s + 2] = (float)bc2;
+            adam_step[s + 3] = 0.f;
+        }
     }
 }
 
@@ -219,7 +228,7 @@ extern "C" int reart_relax_prepare(const reart_relax_config *cfg, const reart_re
     if (rc != REART_OK) return rc;
     hipLaunchKernelGGL(relax_init_kernel, dim3(1), dim3(1024), 0, st, *cfg, bufs->ref_off,
                        (int *)(ws + p.o_rlen), (int *)(ws + p.o_qmap), bufs->iter, bufs->tau, bufs->pc_list,
-                       (int *)(ws + p.o_fx), (double *)(ws + p.o_bc),
+                       (int *)(ws + p.o_fx), (float *)(ws + p.o_bc),
                        (p.pruned && cfg->use_flow) ? (int *)(ws + p.o_seed3) : nullptr, (int *)(ws + p.o_border));
     if (hipMemsetAsync(ws + p.o_ticket, 0, 4 * sizeof(unsigned int), st) != hipSuccess) return REART_ERR_LAUNCH;
     if (hipMemsetAsync(ws + p.o_prof_acc, 0, 4 * sizeof(unsigned long long), st) != hipSuccess) return REART_ERR_LAUNCH;
@@ -948,15 +957,16 @@ static int step_describe(const reart_relax_config *cfg, const reart_relax_buffer
     ad.m = bufs->adam_m; ad.v = bufs->adam_v; ad.seg_lr = c.seg_lr; ad.trans_lr = c.trans_lr;
     ad.beta1 = c.beta1; ad.beta2 = c.beta2; ad.eps = c.eps; ad.step_ptr = bufs->iter;
     ad.weight_decay = c.weight_decay;
-    ad.bias_corr = (const double *)(ws + p.o_bc);
-    // loss log, iter++, next tau and bias corrections: last workgroup of the finalize kernel
+    ad.step = (const float *)(ws + p.o_bc);
+    ba.step_cur = (float *)(ws + p.o_bc); ba.step_next = ba.step_cur + 4;
+    // loss log, iter++, next tau and Adam step sizes: the extra workgroup of the finalize kernel
     StepBook &bk = L.bk;
     bk.enabled = 1; bk.frame_loss = (const double *)(ws + p.o_floss); bk.n_frame_part = B * g.ncg;
     bk.flow_part = (const double *)(ws + p.o_fpart); bk.n_flow_part = nfp;
-    bk.iter = bufs->iter; bk.tau = bufs->tau; bk.losses = bufs->losses; bk.bias_corr = (double *)(ws + p.o_bc);
-    bk.ticket = (unsigned int *)(ws + p.o_ticket);
+    bk.iter = bufs->iter; bk.tau = bufs->tau; bk.losses = bufs->losses; bk.step_next = (float *)(ws + p.o_bc) + 4;
     bk.ring = c.ring; bk.n_iter = c.n_iter; bk.lambda_flow = c.lambda_flow; bk.fixed_tau = c.fixed_tau;
     bk.end_tau = c.end_tau; bk.start_tau = c.start_tau; bk.beta1 = c.beta1; bk.beta2 = c.beta2;
+    bk.seg_lr = c.seg_lr; bk.trans_lr = c.trans_lr;
     L.ws_bwd = ws + p.o_bwd; L.bwd_bytes = p.bwd_bytes;
     return REART_OK;
 }

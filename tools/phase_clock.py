@@ -38,10 +38,10 @@ for rep in range(3):
             continue
         print(name, "deltas (s_memtime ticks):", [ts[i + 1] - ts[i] for i in range(n - 1)], "total", ts[n - 1] - ts[0],
               f"= {(ts[n - 1] - ts[0]) * TICK_US:.2f} us: the lifetime of ONE workgroup (block 1)")
-    fz = v[8:16]          # [0][8] body start, [9] body end, [10] after the ticket, [14] kernel entry (before the bookkeeping's speculative part)
-    print(f"finalize, workgroup 1: main work (column sums, Gram-Schmidt backward, Adam; the bookkeeping's speculative part -- loss partials, pow / "
-          f"sqrt / temperature -- runs on a fifth wave beside it) {(fz[1] - fz[6]) * TICK_US:.2f} us | barrier + ticket round trip "
-          f"{(fz[2] - fz[1]) * TICK_US:.2f} us = lifetime {(fz[2] - fz[6]) * TICK_US:.2f} us")
+    fz = v[8:16]          # [0][8] body workgroup 1 entry, [9] its end; [10] bookkeeping workgroup (the last one) entry, [14] its end
+    print(f"finalize: body workgroup 1 (column sums, Gram-Schmidt backward, Adam) lifetime {(fz[1] - fz[0]) * TICK_US:.2f} us | bookkeeping "
+          f"workgroup (loss partials, pow / sqrt / temperature on a wave each, one barrier, the stores) lifetime {(fz[6] - fz[2]) * TICK_US:.2f} us "
+          f"(the two run on different XCDs, whose counters are not comparable: lifetimes only)")
     if hasattr(lib, "reart_debug_post_clock"):
         lib.reart_debug_post_clock(pbuf)
         p = list(pbuf)
