@@ -1063,7 +1063,10 @@ int reart_rel_trans_backward(const float *trans, int T, int P, const int32_t *pa
 /* Replaces fps_sample_cano (utils/graph_utils.py:37-52): farthest point sampling inside every part, one
  * workgroup per part.  cano [N,3], seg [N] i64, labels [Ps] i64 -> idx [Ps,num_fps] i64 (indices into cano,
  * start = the part's first point like the reference's CUDA FPS; -1 when the part has fewer than num_fps
- * points), count [Ps] i32 = part sizes.  cuda_mode as in reart_fps. */
+ * points), count [Ps] i32 = part sizes.  cuda_mode as in reart_fps.
+ * The whole cloud's member list and running distances live in LDS: N <= REART_PART_FPS_MAX_N, REART_ERR_UNSUPPORTED
+ * above (N <= 6144 fits the default 48 KB; above that the entry point opts in to the large LDS window). */
+#define REART_PART_FPS_MAX_N 19200        /* reart_part_fps: 8 B of LDS per point of the cloud */
 int reart_part_fps(const float *cano, const int64_t *seg, int N, const int64_t *labels, int Ps, int num_fps,
                    int cuda_mode, int64_t *idx, int32_t *count, void *stream);
 

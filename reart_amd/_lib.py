@@ -25,6 +25,7 @@ IK_MAX_POINTS = 1024     # REART_IK_MAX_POINTS: sparse points of reart_ik_fit, h
 LAP_LARGE_MAX_N = 8192   # REART_LAP_LARGE_MAX_N: columns of reart_lap_auction_large / reart_lap_resolve_large (solver state in LDS)
 FPS_MAX_N_LDS = 12288    # REART_FPS_MAX_N_LDS: reart_fps, cloud staged in LDS
 FPS_MAX_N = 1 << 21      # REART_FPS_MAX_N: reart_fps_temp, 21-bit index in the tie key
+PART_FPS_MAX_N = 19200   # REART_PART_FPS_MAX_N: reart_part_fps, 8 B of LDS per point of the whole cloud
 PC_GRAD_MAX_P = 1024     # parts of reart_compute_pc_transform_backward: one frame's pose rows staged in LDS
 STRUCT_MAX_P = 64        # parts of reart_structure_term / reart_rel_trans_backward, as the kinematic entries
 STRUCT_MAX_E = 4096      # their edges: a part's incidence list is held in LDS

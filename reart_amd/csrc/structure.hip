@@ -269,7 +269,7 @@ extern "C" int reart_part_fps(const float *cano, const int64_t *seg, int N, cons
     if (!cano || !seg || !labels || !idx || !count || N <= 0 || Ps < 0 || num_fps <= 0) return REART_ERR_INVALID_ARG;
     if (Ps == 0) return REART_OK;
     const size_t lds = (size_t)N * 8;
-    if (lds > 150 * 1024) return REART_ERR_UNSUPPORTED;
+    if (N > REART_PART_FPS_MAX_N) return REART_ERR_UNSUPPORTED;   // 150 KB of the 160 KB of LDS
     if (lds > REART_LDS_DEFAULT_CAP &&
         hipFuncSetAttribute((const void *)part_fps_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024) != hipSuccess)
         return REART_ERR_LAUNCH;

@@ -79,6 +79,9 @@ def fps_sample_cano(cano_pc, cano_part, uni_label, num_fps=20, cuda_mode=None):
     seg = cano_part.contiguous().long()
     lab = torch.as_tensor(uni_label, device=cano.device).long().contiguous()
     Ps = lab.shape[0]
+    if cano.shape[0] > _lib.PART_FPS_MAX_N:
+        raise NotImplementedError(f"fps_sample_cano: clouds of N <= {_lib.PART_FPS_MAX_N} points (the per-part sampling holds "
+                                  f"the cloud's member list in LDS), not N = {cano.shape[0]}")
     idx = torch.empty((Ps, num_fps), dtype=torch.int64, device=cano.device)
     cnt = torch.empty((Ps,), dtype=torch.int32, device=cano.device)
     rc = _lib.lib().reart_part_fps(_lib.ptr(cano), _lib.ptr(seg), cano.shape[0], _lib.ptr(lab), Ps, num_fps,
