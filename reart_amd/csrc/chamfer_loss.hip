@@ -4,15 +4,19 @@
 //   search                    both directions in ONE reart_search_launch (SearchArgs.k1[0..1], n1 = 2): exact, box-pruned,
 //                             bounded by the seeds of the previous call (prune.hip, unchanged)
 //   chamfer_loss_kernel       the consumer below: distances, indices, next seeds, the loss and the complete gradients
-// The consumer restates the technique of the fused step's chamfer_grad_body (step.hip): a workgroup owns a range of
+// The consumer uses the technique of the fused step's chamfer_grad_body (step.hip): a workgroup owns a range of
 // targets, walks the records of the OTHER cloud and adds the differences of the points that chose one of its targets into
 // 64-bit fixed-point sums in LDS by integer atomics -- exact to one quantum per addend and independent of the order of
 // arrival, so the gradient is deterministic without a sort, there is no floating-point atomic and no global accumulator.
-// What differs from the step: P1 != P2, a gradient for y, a fixed-point scale per batch element taken from the boxes the
-// prep has just computed, and the loss reduced inside the same launch by the last workgroup to finish.
+// The fixed-point conversion, the block sum and the last workgroup's sum are the step's own (consumer_dev.h).  The walk is
+// not: the step's merges slice partials over a 1024-target range and captures its own d1; here P1 != P2, there is a
+// gradient for y, a fixed-point scale per batch element taken from the boxes the prep has just computed, and the loss is
+// reduced inside the same launch by the last workgroup to finish.
 #include "common.h"
 #include "internal.h"
+#include "consumer_dev.h"
 #include <math.h>
+#include <type_traits>
 
 #define CL_BS 256        // threads per consumer workgroup = targets it owns
 #define CL_IL 4          // records of the other cloud in flight per thread
@@ -50,15 +54,57 @@ static int chamfer_loss_plan(int N, int P1, int P2, ChamferLossPlan *p) {
     return REART_OK;
 }
 
-// float -> 64-bit fixed point with `sbits` fractional bits (0 <= sbits <= 39) by integer shifts of the mantissa: truncates
-// toward zero below 2^-sbits (error < one quantum per addend), saturates instead of shifting a bit out
-__device__ __forceinline__ long long cl_fixed_from_float(float v, int sbits) {
-    const unsigned bits = __float_as_uint(v);
-    const int ex = (int)((bits >> 23) & 0xffu);
-    const long long mant = (long long)((bits & 0x7fffffu) | (ex ? 0x800000u : 0u));
-    const int sh = (ex ? ex : 1) - 150 + sbits;
-    const long long mag = sh >= 0 ? (sh < 40 ? (mant << sh) : 0x7fffffffffffffffll) : (sh > -64 ? (mant >> (-sh)) : 0ll);
-    return (bits >> 31) ? -mag : mag;
+// ---- what the two gradient kernels below (chamfer_loss_kernel, chamfer_points_bwd_kernel) share.  A workgroup (r, n) of
+// cloud d owns the points r0 = r * CL_BS .. of cloud d ("own", Pw points) of batch element n; the other cloud has Po points.
+
+// largest of the threads' values over the workgroup (fmaxf drops NaN); contains one barrier
+__device__ __forceinline__ float cl_block_max(float mx, float *s_mx) {
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) mx = fmaxf(mx, __shfl_xor(mx, s, 64));
+    if ((threadIdx.x & 63) == 0) s_mx[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    mx = s_mx[0];
+#pragma unroll
+    for (int w = 1; w < CL_BS / REART_WAVE; ++w) mx = fmaxf(mx, s_mx[w]);
+    return mx;
+}
+
+// The walk over ALL points j of the other cloud: one whose neighbour io[j] is an own point of this workgroup adds
+// fl(own - other_j), times its upstream gradient gg[j] where gg is given (uniform; a zero adds nothing: a masked point), to
+// that point's fixed-point sum in LDS.  Idx: int records of the search or int64 indices of a caller.  An index is used only
+// if it is in range of the own cloud AND of this workgroup's targets, else there is no access at all.
+template <class Idx>
+__device__ __forceinline__ void cl_scatter_walk(const float *own, const float *oth, const Idx *io, const float *gg, int Pw, int Po,
+                                                int r0, int sbits, unsigned long long *s_acc) {
+    typedef typename std::make_unsigned<Idx>::type U;
+    for (int jb = threadIdx.x; jb < Po; jb += CL_IL * CL_BS) {
+        int jl[CL_IL];
+#pragma unroll
+        for (int u = 0; u < CL_IL; ++u) {
+            const int j = jb + u * CL_BS;
+            const Idx t = io[j < Po ? j : Po - 1];
+            jl[u] = (j < Po && (U)t < (U)Pw && (U)(t - r0) < (U)CL_BS) ? (int)(t - r0) : -1;
+        }
+#pragma unroll
+        for (int u = 0; u < CL_IL; ++u) {
+            if (jl[u] < 0) continue;
+            const int j = jb + u * CL_BS;
+            const float gj = gg ? gg[j] : 1.0f;
+            if (gg && gj == 0.0f) continue;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const float df = own[3 * (size_t)(r0 + jl[u]) + k] - oth[3 * (size_t)j + k];
+                atomicAdd(&s_acc[3 * jl[u] + k], (unsigned long long)reart_fixed_from_float(gg ? gj * df : df, sbits));
+            }
+        }
+    }
+}
+
+// gradient of the thread's own point: its own term + 2 * (fixed-point sum)
+__device__ __forceinline__ void cl_grad_store(float *G, const float (&first)[3], const unsigned long long *s_acc, int sbits) {
+    const double inv2 = 2.0 * exp2((double)-sbits);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) G[k] = first[k] + (float)((double)(long long)s_acc[3 * threadIdx.x + k] * inv2);
 }
 
 struct ChamferLossArgs {
@@ -106,9 +152,6 @@ __global__ __launch_bounds__(CL_BS) void chamfer_loss_kernel(ChamferLossArgs a) 
             if ((e & 7) < 6 && v < INFINITY) mx = fmaxf(mx, v);
         }
     }
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) mx = fmaxf(mx, __shfl_xor(mx, s, 64));
-    if ((tid & 63) == 0) s_mx[tid >> 6] = mx;
     // ---- 2. own record
     const int i = r * CL_BS + tid;
     const bool live = i < Pw;
@@ -122,20 +165,8 @@ __global__ __launch_bounds__(CL_BS) void chamfer_loss_kernel(ChamferLossArgs a) 
     float xo[3], yn[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) { xo[k] = own[3 * (size_t)ic + k]; yn[k] = oth[3 * (size_t)j0c + k]; }
-    __syncthreads();
-    mx = s_mx[0];
-#pragma unroll
-    for (int w = 1; w < CL_BS / REART_WAVE; ++w) mx = fmaxf(mx, s_mx[w]);
-    // sums of at most Pmax differences, each of magnitude at most 2 mx < 2^(e+1), mx < 2^e, Pmax <= 2^c:
-    // |sum| * 2^bits < 2^(c + e + 1 + bits) <= 2^62
-    int sbits;
-    {
-        const int Pmax = Pw > Po ? Pw : Po;
-        const int c = 32 - __clz(Pmax > 1 ? Pmax - 1 : 1);                           // Pmax <= 2^c
-        const int e = (int)((__float_as_uint(mx) >> 23) & 0xffu) - 126;              // mx < 2^e (denormals: e = -126)
-        const int b = 61 - c - e;
-        sbits = b > 39 ? 39 : (b < 0 ? 0 : b);
-    }
+    // sums of at most Pmax differences, each of magnitude at most 2 mx
+    const int sbits = reart_fx_bits(Pw > Po ? Pw : Po, cl_block_max(mx, s_mx));
     if (blockIdx.x == 0 && tid == 0) a.bits[n] = sbits;
     if (live) {
         if (a.od[d]) a.od[d][ow] = d0;
@@ -143,62 +174,31 @@ __global__ __launch_bounds__(CL_BS) void chamfer_loss_kernel(ChamferLossArgs a) 
         a.seed[d][ow] = ok0 ? j0 : -1;
     }
     // ---- 3. the other cloud's records
-    if (want) {
-        const int *pio = a.pi[o] + (size_t)n * Po;
-        const int r0 = r * CL_BS;
-        for (int jb = tid; jb < Po; jb += CL_IL * CL_BS) {
-            int jl[CL_IL];
-#pragma unroll
-            for (int u = 0; u < CL_IL; ++u) {
-                const int j = jb + u * CL_BS;
-                const int t = pio[j < Po ? j : Po - 1];
-                // in range of the own cloud AND of this workgroup's targets, else no access at all
-                jl[u] = (j < Po && (unsigned)t < (unsigned)Pw && (unsigned)(t - r0) < (unsigned)CL_BS) ? t - r0 : -1;
-            }
-#pragma unroll
-            for (int u = 0; u < CL_IL; ++u) {
-                if (jl[u] < 0) continue;
-                const int j = jb + u * CL_BS;
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    const float df = own[3 * (size_t)(r0 + jl[u]) + k] - oth[3 * (size_t)j + k];
-                    atomicAdd(&s_acc[3 * jl[u] + k], (unsigned long long)cl_fixed_from_float(df, sbits));
-                }
-            }
-        }
-    }
+    if (want) cl_scatter_walk(own, oth, a.pi[o] + (size_t)n * Po, nullptr, Pw, Po, r * CL_BS, sbits, s_acc);
     __syncthreads();
     // ---- 4. gradient and loss
     double term = 0.0;
     if (live) {
         term = (double)d0;
         if (want) {
-            const double inv2 = 2.0 * exp2((double)-sbits);
-            float *G = a.grad[d] + 3 * ow;
+            float first[3];
 #pragma unroll
-            for (int k = 0; k < 3; ++k)
-                G[k] = (ok0 ? 2.0f * (xo[k] - yn[k]) : 0.0f) + (float)((double)(long long)s_acc[3 * tid + k] * inv2);
+            for (int k = 0; k < 3; ++k) first[k] = ok0 ? 2.0f * (xo[k] - yn[k]) : 0.0f;
+            cl_grad_store(a.grad[d] + 3 * ow, first, s_acc, sbits);
         }
     }
-    term = reart_wave_sum_d(term);
-    if ((tid & 63) == 0) s_red[tid >> 6] = term;
-    __syncthreads();
+    term = reart_block_sum_d<CL_BS>(term, s_red);
     const int nbx = a.nr[0] + a.nr[1], total = nbx * a.N;
     if (tid == 0) {
-        double t = 0.0;
-        for (int w = 0; w < CL_BS / REART_WAVE; ++w) t += s_red[w];
         // device-scope atomics: the partial and the ticket meet in L2 whichever XCD the workgroups ran on
-        __hip_atomic_store(&a.part[(size_t)n * nbx + blockIdx.x], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&a.part[(size_t)n * nbx + blockIdx.x], term, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const unsigned int k = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
         s_last = (k == (unsigned int)(total - 1));
     }
     __syncthreads();
     if (!s_last) return;
     if (tid < 64) {
-        // fixed order: lane l adds the partials l, l + 64, ... in double, then the butterfly; one rounding to float
-        double t = 0.0;
-        for (int e = tid; e < total; e += 64) t += __hip_atomic_load(&a.part[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        t = reart_wave_sum_d(t);
+        const double t = reart_partials_sum_d(a.part, total);      // fixed order, one rounding to float
         if (tid == 0) a.loss[0] = (float)t;
     }
 }
@@ -398,9 +398,6 @@ __global__ __launch_bounds__(CL_BS) void chamfer_points_bwd_kernel(ChamferPoints
             if (v < INFINITY) mx = fmaxf(mx, v);
         }
     }
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) mx = fmaxf(mx, __shfl_xor(mx, s, 64));
-    if ((tid & 63) == 0) s_mx[tid >> 6] = mx;
     // ---- 2. own term
     const int i = r * CL_BS + tid;
     const bool live = i < Pw;
@@ -415,62 +412,17 @@ __global__ __launch_bounds__(CL_BS) void chamfer_points_bwd_kernel(ChamferPoints
 #pragma unroll
         for (int k = 0; k < 3; ++k) first[k] = ok0 ? g2 * (own[3 * (size_t)ic + k] - oth[3 * j0c + k]) : 0.0f;
     }
-    __syncthreads();
-    mx = s_mx[0];
-#pragma unroll
-    for (int w = 1; w < CL_BS / REART_WAVE; ++w) mx = fmaxf(mx, s_mx[w]);
-    // sums of at most Pmax addends, each of magnitude at most m (1 + 2^-20) < 2^e, Pmax <= 2^c:
-    // |sum| * 2^bits < 2^(c + e + bits) <= 2^61
-    int sbits;
-    {
-        const int Pmax = Pw > Po ? Pw : Po;
-        const int c = 32 - __clz(Pmax > 1 ? Pmax - 1 : 1);                           // Pmax <= 2^c
-        const float m1 = mx * 1.000002f;                                             // > m (1 + 2^-20); INF -> e = 129
-        const int e = (int)((__float_as_uint(m1) >> 23) & 0xffu) - 126;              // m1 < 2^e (denormals: e = -126)
-        const int b = 61 - c - e;
-        sbits = b > 39 ? 39 : (b < 0 ? 0 : b);
-    }
+    // sums of at most Pmax addends, each of magnitude at most m (1 + 2^-20) < m * 1.000002f
+    const int sbits = reart_fx_bits(Pw > Po ? Pw : Po, cl_block_max(mx, s_mx) * 1.000002f);
     if (r == 0 && tid == 0) {
         a.bits[2 * n + d] = sbits;
         if (d == 0 && !a.grad[1]) a.bits[2 * n + 1] = 0;      // no sums into y in this call
     }
     // ---- 3. the other cloud's indices
-    if (go) {
-        const int64_t *io = a.idx[o] + (size_t)n * Po;
-        const float *gg = go + (size_t)n * Po;
-        const int r0 = r * CL_BS;
-        for (int jb = tid; jb < Po; jb += CL_IL * CL_BS) {
-            int jl[CL_IL];
-#pragma unroll
-            for (int u = 0; u < CL_IL; ++u) {
-                const int j = jb + u * CL_BS;
-                const int64_t t = io[j < Po ? j : Po - 1];
-                // in range of the own cloud AND of this workgroup's targets, else no access at all
-                jl[u] = (j < Po && (unsigned long long)t < (unsigned long long)Pw &&
-                         (unsigned long long)(t - r0) < (unsigned long long)CL_BS) ? (int)(t - r0) : -1;
-            }
-#pragma unroll
-            for (int u = 0; u < CL_IL; ++u) {
-                if (jl[u] < 0) continue;
-                const int j = jb + u * CL_BS;
-                const float gj = gg[j];
-                if (gj == 0.0f) continue;        // a masked point adds nothing
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    const float df = own[3 * (size_t)(r0 + jl[u]) + k] - oth[3 * (size_t)j + k];
-                    atomicAdd(&s_acc[3 * jl[u] + k], (unsigned long long)cl_fixed_from_float(gj * df, sbits));
-                }
-            }
-        }
-    }
+    if (go) cl_scatter_walk(own, oth, a.idx[o] + (size_t)n * Po, go + (size_t)n * Po, Pw, Po, r * CL_BS, sbits, s_acc);
     __syncthreads();
     // ---- 4. gradient
-    if (live) {
-        const double inv2 = 2.0 * exp2((double)-sbits);
-        float *G = a.grad[d] + 3 * ow;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) G[k] = first[k] + (float)((double)(long long)s_acc[3 * tid + k] * inv2);
-    }
+    if (live) cl_grad_store(a.grad[d] + 3 * ow, first, s_acc, sbits);
 }
 
 extern "C" int reart_chamfer_points_backward(const float *x, const float *y, int N, int P1, int P2, const int64_t *i_xy,

@@ -4,6 +4,7 @@
 // knn_cuda.KNN(k=3) call at :158) and flow_loss (networks/loss.py:10-21) with its gradient.
 #include "common.h"
 #include "internal.h"
+#include "consumer_dev.h"
 #include "flow_dev.h"
 #include <math.h>
 
@@ -135,14 +136,8 @@ __global__ __launch_bounds__(FL_BS) void flow_loss_kernel(const float *__restric
         const bool m = mask ? (mask[e] != 0) : true;
         acc += reart_flow_point(gt + 3 * e, pred + 3 * e, m, robust, smooth, grad ? grad + 3 * e : nullptr);
     }
-    acc = reart_wave_sum_d(acc);
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int w = 0; w < FL_BS / REART_WAVE; ++w) t += s_red[w];
-        partial[blockIdx.x] = t;
-    }
+    acc = reart_block_sum_d<FL_BS>(acc, s_red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = acc;
 }
 __global__ void flow_loss_final_kernel(const double *__restrict__ partial, int n, float *__restrict__ loss) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {

@@ -1,5 +1,6 @@
 // reart_amd/csrc/flow_dev.h -- the per-point expressions of the flow term, shared by the kernels of flow.hip (blend_kernel,
-// blend_batch_kernel, flow_loss_kernel) and of flow_term.hip: one definition, so that every path rounds alike.
+// blend_batch_kernel, flow_loss_kernel) and of flow_term.hip: one definition, so that every path rounds alike.  The fused
+// step's flow_blend_body (step.hip) takes huber1 / huber1_grad from here and keeps the rest inline (see there).
 #pragma once
 #include "common.h"
 #include <math.h>

@@ -15,6 +15,7 @@
 // search kernel reads them where a wave's 64 lanes are 64 consecutive rows.
 #include "common.h"
 #include "internal.h"
+#include "consumer_dev.h"
 #include "flow_dev.h"
 #include <math.h>
 
@@ -116,10 +117,6 @@ struct FlowTermArgs {
     float *loss;                // nullable
 };
 
-__device__ __forceinline__ const float *flow_term_frame(const FlowTermArgs &a, int f) {
-    // complete_pred = cat(pc_trans[:cano], cano, pc_trans[cano:])   (run_robot.py:206)
-    return f < a.c ? a.X + (size_t)f * a.N * 3 : (f == a.c ? a.cano : a.X + (size_t)(f - 1) * a.N * 3);
-}
 // the point visited at position i; an entry outside [0, N) (never from a permutation) reads as i itself
 __device__ __forceinline__ int flow_term_point(const FlowTermArgs &a, int i) {
     const int p = a.order ? a.order[i] : i;
@@ -133,7 +130,7 @@ __global__ __launch_bounds__(FT_BS) void flow_stage_kernel(FlowTermArgs a) {
         if (i < (int)gridDim.x) a.col[i] = 0u;
         if (i == 0) a.ticket[0] = 0u;
     }
-    const float *s = flow_term_frame(a, f) + 3 * (size_t)flow_term_point(a, i);
+    const float *s = reart_complete_frame(a.X, a.cano, a.N, a.c, f) + 3 * (size_t)flow_term_point(a, i);
     float *d = a.qs + 3 * ((size_t)f * a.N + i);
     d[0] = s[0]; d[1] = s[1]; d[2] = s[2];
 }
@@ -153,13 +150,14 @@ __global__ __launch_bounds__(FT_BS) void flow_term_kernel(FlowTermArgs a) {
     double term = 0.0;
     {
         // the point in both frames of the pair and the records: independent of each other, requested first
-        const float *c0 = flow_term_frame(a, f) + 3 * (size_t)p, *c1 = flow_term_frame(a, f + 1) + 3 * (size_t)p;
+        const float *c0 = reart_complete_frame(a.X, a.cano, a.N, a.c, f) + 3 * (size_t)p;
+        const float *c1 = reart_complete_frame(a.X, a.cano, a.N, a.c, f + 1) + 3 * (size_t)p;
         const float c0v[3] = {c0[0], c0[1], c0[2]}, c1v[3] = {c1[0], c1[1], c1[2]};
-        const float qx = a.qs[ov], qy = a.qs[ov + 1], qz = a.qs[ov + 2];
+        const float q[3] = {a.qs[ov], a.qs[ov + 1], a.qs[ov + 2]};
         const int n2 = a.rlen[f];
         const float *tx = a.rsoa + (size_t)f * 3 * a.Ppad, *ty = tx + a.Ppad, *tz = ty + a.Ppad;
-        int bb[3];
-        float4 X[3][2], Y[3][2], Z[3][2];
+        // a record names a block only if it is finite, in range and 8-aligned; a block is rescanned once, up to the set's length
+        int bb[3], nv[3];
 #pragma unroll
         for (int cb = 0; cb < 3; ++cb) {
             const float m = a.pd[ov + cb];
@@ -167,32 +165,13 @@ __global__ __launch_bounds__(FT_BS) void flow_term_kernel(FlowTermArgs a) {
             const bool ok = m < INFINITY && (unsigned)blk <= (unsigned)(a.Ppad - 8) && (blk & 7) == 0;
             bb[cb] = ok ? blk : -1;
 #pragma unroll
-            for (int cp = 0; cp < cb; ++cp) bb[cb] = bb[cb] == bb[cp] ? -1 : bb[cb];   // a block is rescanned once
-            const int bl = ok ? blk : 0;                  // blocks are 8-aligned: two 16-byte loads per axis
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                X[cb][h] = *(const float4 *)(tx + bl + 4 * h);
-                Y[cb][h] = *(const float4 *)(ty + bl + 4 * h);
-                Z[cb][h] = *(const float4 *)(tz + bl + 4 * h);
-            }
+            for (int cp = 0; cp < cb; ++cp) bb[cb] = bb[cb] == bb[cp] ? -1 : bb[cb];
+            nv[cb] = bb[cb] < 0 ? 0 : min(8, n2 - bb[cb]);
         }
         // the three nearest targets lie inside the three best blocks: one exact rescan with the full (distance, index) key
-        float kd[3] = {INFINITY, INFINITY, INFINITY};
-        int ki[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff};
-#pragma unroll
-        for (int cb = 0; cb < 3; ++cb) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const float4 vx = X[cb][u >> 2], vy = Y[cb][u >> 2], vz = Z[cb][u >> 2];
-                const int c = u & 3;
-                const float px = c == 0 ? vx.x : (c == 1 ? vx.y : (c == 2 ? vx.z : vx.w));
-                const float py = c == 0 ? vy.x : (c == 1 ? vy.y : (c == 2 ? vy.z : vy.w));
-                const float pz = c == 0 ? vz.x : (c == 1 ? vz.y : (c == 2 ? vz.z : vz.w));
-                float d = reart_sqdist3(qx, qy, qz, px, py, pz);
-                if (bb[cb] < 0 || bb[cb] + u >= n2) d = INFINITY;
-                reart_top3_insert(kd, ki, d, d < INFINITY ? bb[cb] + u : 0x7fffffff);
-            }
-        }
+        float kd[3];
+        int ki[3];
+        reart_rescan3(q, tx, ty, tz, bb, nv, kd, ki);
         // fewer than three finite candidates (non-finite coordinates, a set below three points): index 0, as the records of
         // reart_knn_cuda beyond a set's length
         float dk[3];
@@ -223,20 +202,16 @@ __global__ __launch_bounds__(FT_BS) void flow_term_kernel(FlowTermArgs a) {
             if (a.mask) a.mask[(size_t)f * a.N + p] = m ? 1 : 0;
         }
     }
-    term = reart_wave_sum_d(term);
-    if ((tid & 63) == 0) s_red[tid >> 6] = term;
     // The hand-off to the last workgroup of the column and of the launch.  Everything handed off (gp, the partials) is written by
     // agent-scope (write-through) stores and read by agent-scope loads, so no cache has to be written back or invalidated:
-    // every wave waits until its stores have left it (a barrier waits for no memory counter), the workgroup meets, and
+    // every wave waits until its stores have left it (a barrier waits for no memory counter), the workgroup meets in the block sum (which stores to LDS only), and
     // thread 0 -- after its own partial has left too -- signals with relaxed agent-scope adds.  A release here would write back
     // the XCD's whole L2, twice per workgroup.
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
+    term = reart_block_sum_d<FT_BS>(term, s_red);
     const int total = nbx * a.B;
     if (tid == 0) {
-        double t = 0.0;
-        for (int w = 0; w < FT_BS / REART_WAVE; ++w) t += s_red[w];
-        __hip_atomic_store(&a.part[(size_t)f * nbx + bx], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&a.part[(size_t)f * nbx + bx], term, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         const unsigned int kc = __hip_atomic_fetch_add(&a.col[bx], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         s_lastcol = (kc == (unsigned int)(a.B - 1));
@@ -269,10 +244,7 @@ __global__ __launch_bounds__(FT_BS) void flow_term_kernel(FlowTermArgs a) {
     }
     if (!s_last || !a.loss) return;
     if (tid < 64) {
-        // fixed order: lane l adds the partials l, l + 64, ... in double, then the butterfly; one rounding to float
-        double t = 0.0;
-        for (int e = tid; e < total; e += 64) t += __hip_atomic_load(&a.part[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        t = reart_wave_sum_d(t);
+        const double t = reart_partials_sum_d(a.part, total);      // fixed order, one rounding to float
         if (tid == 0) a.loss[0] = a.weight * (float)t;
     }
 }

@@ -9,6 +9,7 @@
 // path; the two loss sums are accumulated in double precision (the former path: torch's fp32 tree sums).
 #include "common.h"
 #include "internal.h"
+#include "consumer_dev.h"
 #include <math.h>
 
 struct KinPostArgs {
@@ -75,16 +76,12 @@ __global__ __launch_bounds__(KP_BS) void kin_grad_kernel(KinPostArgs a) {
         }
         a.G[o] = g0; a.G[o + 1] = g1; a.G[o + 2] = g2;
     }
-    acc = reart_wave_sum_d(acc);
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int w = 0; w < KP_BS / 64; ++w) t += s_red[w];
-        a.partial[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = t;
-    }
+    acc = reart_block_sum_d<KP_BS>(acc, s_red);
+    if (threadIdx.x == 0) a.partial[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = acc;
 }
 
+// The partials come from the launch before this one: plain loads (reart_partials_sum_d's agent-scope loads are for partials
+// written inside the same launch and would change the scope of these)
 __global__ __launch_bounds__(64) void kin_loss_kernel(KinPostArgs a, int blocks) {
     double t = 0.0;
     for (int e = threadIdx.x; e < blocks; e += 64) t += a.partial[e];

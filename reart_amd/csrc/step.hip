@@ -11,6 +11,8 @@
 #include "common.h"
 #include "internal.h"
 #include "blocksort.h"
+#include "consumer_dev.h"
+#include "flow_dev.h"
 #include <math.h>
 #include <string.h>
 
@@ -155,7 +157,9 @@ __global__ void relax_init_kernel(reart_relax_config c, const int *__restrict__ 
     }
     if (t == 0) {
         // sums of up to N differences |x - y| (allow 8 x the data range): N * 8 max|y| * 2^bits < 2^61, and
-        // bits <= 39 so that a 24-bit mantissa never overflows the shift
+        // bits <= 39 so that a 24-bit mantissa never overflows the shift.  Not reart_fx_bits (consumer_dev.h): that rule
+        // rounds N and the bound up to powers of two, this one takes the logarithm of their product, so they give
+        // different bits for the same data -- and the bits decide every rounding of the step's Chamfer gradient
         const double bound = 8.0 * (double)c.N * fmax((double)s_max[0], 1e-30);
         int bits = (int)floor(61.0 - log2(bound));
         fx_bits[0] = bits > 39 ? 39 : (bits < 0 ? 0 : bits);
@@ -279,20 +283,6 @@ struct FlowArgs {
     int *seed_out;                       // nullable [B,N,3]: the 3 neighbour indices, warm start of the next search
 };
 
-__device__ __forceinline__ const float *complete_frame(const FlowArgs &a, int f) {
-    // complete_pred = cat(pc_trans[:cano], cano, pc_trans[cano:])   (run_robot.py:206)
-    return f < a.cano_idx ? a.X + (size_t)f * a.N * 3
-                          : (f == a.cano_idx ? a.cano : a.X + (size_t)(f - 1) * a.N * 3);
-}
-
-__device__ __forceinline__ float huber1s(float x) {
-    const float ax = fabsf(x);
-    return ax <= 1.0f ? 0.5f * x * x : (ax - 0.5f);
-}
-__device__ __forceinline__ float huber1s_grad(float x) {
-    return fabsf(x) <= 1.0f ? x : (x > 0.f ? 1.0f : -1.0f);
-}
-
 // SL: partial lists per query the instantiation is written for -- 1: exactly one (a.S == 1: every pruned path), its
 // record is loaded once; 4: up to four, every partial of a query is loaded before the first compare (clamped slices
 // repeat a record); 0: any number, in batches of four
@@ -310,8 +300,8 @@ __device__ __forceinline__ void flow_blend_body(const FlowArgs &a, const int bx,
         int ki[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff};
         const size_t stride = (size_t)a.B * a.N * 3, o0 = ((size_t)f * a.N + n) * 3;
         // the point in both frames of the pair: independent of the search results, issued first
-        const float *c0 = complete_frame(a, f) + 3 * (size_t)n;
-        const float *c1 = complete_frame(a, f + 1) + 3 * (size_t)n;
+        const float *c0 = reart_complete_frame(a.X, a.cano, a.N, a.cano_idx, f) + 3 * (size_t)n;
+        const float *c1 = reart_complete_frame(a.X, a.cano, a.N, a.cano_idx, f + 1) + 3 * (size_t)n;
         const float c0v[3] = {c0[0], c0[1], c0[2]}, c1v[3] = {c1[0], c1[1], c1[2]};
         const int roff = a.ref_off[f];
         for (int s0 = 0; s0 < (SL ? 1 : a.S); s0 += 4) {
@@ -334,40 +324,14 @@ __device__ __forceinline__ void flow_blend_body(const FlowArgs &a, const int bx,
         if (a.blocks) {
             // kd/ki are the 3 best blocks over all slices (by minimum, then index); the 3 nearest
             // targets lie inside them: one exact rescan of 24 targets with the full (d, index) key
-            const float qx = c0v[0], qy = c0v[1], qz = c0v[2];
             const float *tx = a.rsoa + (size_t)f * 3 * a.Mpad, *ty = tx + a.Mpad, *tz = ty + a.Mpad;
-            int bb[3];
-            float4 X[3][2], Y[3][2], Z[3][2];
+            int bb[3], nv[3];
 #pragma unroll
             for (int cb = 0; cb < 3; ++cb) {
                 bb[cb] = (kd[cb] < INFINITY) ? ki[cb] : -1;
-                const int blk = bb[cb] < 0 ? 0 : bb[cb];          // blocks are 8-aligned: two 16-byte loads per axis
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    X[cb][h] = *(const float4 *)(tx + blk + 4 * h);
-                    Y[cb][h] = *(const float4 *)(ty + blk + 4 * h);
-                    Z[cb][h] = *(const float4 *)(tz + blk + 4 * h);
-                }
+                nv[cb] = bb[cb] < 0 ? 0 : 8;
             }
-            // all 18 loads are in flight before the first compare: left to itself the scheduler sinks the loads of a
-            // block into the insert code of the block before it (fewer live registers), one exposed round trip per group
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) { kd[k] = INFINITY; ki[k] = 0x7fffffff; }
-#pragma unroll
-            for (int cb = 0; cb < 3; ++cb) {
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const float4 vx = X[cb][u >> 2], vy = Y[cb][u >> 2], vz = Z[cb][u >> 2];
-                    const int c = u & 3;
-                    const float px = c == 0 ? vx.x : (c == 1 ? vx.y : (c == 2 ? vx.z : vx.w));
-                    const float py = c == 0 ? vy.x : (c == 1 ? vy.y : (c == 2 ? vy.z : vy.w));
-                    const float pz = c == 0 ? vz.x : (c == 1 ? vz.y : (c == 2 ? vz.z : vz.w));
-                    float d = reart_sqdist3(qx, qy, qz, px, py, pz);
-                    if (bb[cb] < 0) d = INFINITY;
-                    reart_top3_insert(kd, ki, d, d < INFINITY ? bb[cb] + u : 0x7fffffff);
-                }
-            }
+            reart_rescan3(c0v, tx, ty, tz, bb, nv, kd, ki);
         }
 #pragma unroll
         for (int k = 0; k < 3; ++k) ki[k] = ki[k] == 0x7fffffff ? 0 : ki[k];   // fewer than 3 finite candidates
@@ -375,6 +339,10 @@ __device__ __forceinline__ void flow_blend_body(const FlowArgs &a, const int bx,
             int *so = a.seed_out + 3 * ((size_t)f * a.N + n);
             so[0] = ki[0]; so[1] = ki[1]; so[2] = ki[2];
         }
+        // Blend, mask, loss term and gradient: operation for operation reart_blend_point + reart_flow_point (flow_dev.h),
+        // times lambda.  Written out here: with the two calls post_kernel took one more VGPR and the headline's median
+        // fell below the parent's range in the first of two A/B sessions (profiles/consumer_dev_bench.json); only Huber's
+        // two functions are shared.  A change to either side must be made to both.
         const float *rf = a.ref_flow + 3 * (size_t)roff;
         float rfl[3][3];
 #pragma unroll
@@ -404,21 +372,15 @@ __device__ __forceinline__ void flow_blend_body(const FlowArgs &a, const int bx,
         for (int c = 0; c < 3; ++c) {
             const float p = c1v[c] - c0v[c];  // pred_flow (run_robot.py:207)
             const float d = p - gtf[c];
-            fl += a.robust ? huber1s(d) : d * d;
+            fl += a.robust ? huber1(d) : d * d;
             sm += p * p;
-            const float gf = a.robust ? huber1s_grad(d) : 2.0f * d;
+            const float gf = a.robust ? huber1_grad(d) : 2.0f * d;
             go[c] = a.lambda * (m ? gf : a.smooth * (2.0f * p));
         }
         term = m ? (double)fl : (double)(a.smooth * sm);
     }
-    term = reart_wave_sum_d(term);
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = term;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int w = 0; w < FBS / REART_WAVE; ++w) t += s_red[w];
-        a.part[(size_t)f * nbx + bx] = t;
-    }
+    term = reart_block_sum_d<FBS>(term, s_red);
+    if (threadIdx.x == 0) a.part[(size_t)f * nbx + bx] = term;
 }
 
 // ------------------------------------------------------------------------------ Chamfer grad
@@ -430,18 +392,7 @@ __device__ __forceinline__ void flow_blend_body(const FlowArgs &a, const int bx,
 // 64-bit FIXED POINT by integer atomics: exact to 2^-scale, independent of the order in which
 // the sources arrive -> deterministic without sorting, O(N) even when every source picks the same
 // target.  (The stand-alone reart_knn_points_backward keeps the sorted, bit-reproducing gather.)
-// float -> 64-bit fixed point with `sbits` fractional bits, by integer shifts of the mantissa
-// (gfx950 has no f64 -> i64 convert; llrint() is a long emulation).  Truncates toward zero below
-// 2^-sbits: deterministic, error < 2^-sbits per term.
-__device__ __forceinline__ long long fixed_from_float(float v, int sbits) {
-    const unsigned bits = __float_as_uint(v);
-    const int ex = (int)((bits >> 23) & 0xffu);
-    const long long mant = (long long)((bits & 0x7fffffu) | (ex ? 0x800000u : 0u));
-    const int sh = (ex ? ex : 1) - 150 + sbits;
-    const long long mag = sh >= 0 ? (sh < 40 ? (mant << sh) : 0x7fffffffffffffffll) : (sh > -64 ? (mant >> (-sh)) : 0ll);
-    return (bits >> 31) ? -mag : mag;
-}
-
+// The conversion is reart_fixed_from_float (consumer_dev.h), shared with the Chamfer operators of chamfer_loss.hip.
 struct CGradArgs {
     const float *X, *Y;                  // pc_trans, pc_list [B,N,3]
     const float *pd0; const int *pi0;    // x -> y partials [S][B][N]
@@ -540,7 +491,7 @@ __device__ __forceinline__ void chamfer_grad_body(const CGradArgs &a, const int 
                 // quantity to accumulate
 #pragma unroll
                 for (int k = 0; k < 3; ++k)
-                    atomicAdd(&s_acc[3 * jl + k], (unsigned long long)fixed_from_float(df[u][k], sbits));
+                    atomicAdd(&s_acc[3 * jl + k], (unsigned long long)reart_fixed_from_float(df[u][k], sbits));
             }
         }
     }
@@ -555,14 +506,8 @@ __device__ __forceinline__ void chamfer_grad_body(const CGradArgs &a, const int 
         for (int k = 0; k < 3; ++k)
             G[k] = 2.0f * (xo[k] - yn[k]) + (float)((double)(long long)s_acc[3 * tid + k] * inv2);
     }
-    term = reart_wave_sum_d(term);
-    if ((tid & 63) == 0) s_red[tid >> 6] = term;
-    __syncthreads();
-    if (tid == 0) {
-        double t = 0.0;
-        for (int w = 0; w < CG_BS / REART_WAVE; ++w) t += s_red[w];
-        a.loss_part[(size_t)b * nbx + bx] = t;
-    }
+    term = reart_block_sum_d<CG_BS>(term, s_red);
+    if (tid == 0) a.loss_part[(size_t)b * nbx + bx] = term;
 }
 
 // the stand-alone consumers; BATCH: K instances in one launch, instance k on the grid's plane z = k
@@ -726,14 +671,8 @@ __device__ __forceinline__ void assign_grad_body(const AssignArgs &a, int bx, in
 #pragma unroll
         for (int k = 0; k < 3; ++k) a.G[3 * o + k] = g[k];
     }
-    term = reart_wave_sum_d(term);
-    if ((tid & 63) == 0) s_red[tid >> 6] = term;
-    __syncthreads();
-    if (tid == 0) {
-        double t = 0.0;
-        for (int w = 0; w < CG_BS / REART_WAVE; ++w) t += s_red[w];
-        a.loss_part[(size_t)b * gx + bx] = t * (double)a.lambda;
-    }
+    term = reart_block_sum_d<CG_BS>(term, s_red);
+    if (tid == 0) a.loss_part[(size_t)b * gx + bx] = term * (double)a.lambda;
 }
 template <bool BATCH>
 __global__ __launch_bounds__(CG_BS) void assign_grad_kernel(Batched<AssignArgs> ab) {
