@@ -1060,6 +1060,51 @@ size_t reart_rel_trans_backward_workspace_bytes(int T, int P, int E);
 int reart_rel_trans_backward(const float *trans, int T, int P, const int32_t *pairs, int E, const float *grad_rel,
                              float *grad_trans, void *workspace, size_t workspace_bytes, void *stream);
 
+/* The connection term of networks/loss.py compute_connection_loss (:60-78) as two operators of an iteration: the selection of
+ * the pairs in the canonical cloud, and their cost in the predicted frames with its gradient.  No host synchronisation, no
+ * floating-point atomics, the same bits on every run.
+ *
+ * reart_connection_select: cano [N,3], seg [N] i64, pairs [E,2] i32 (src part a, tgt part b) -> src_idx, tgt_idx [E,k] i32
+ * (indices into cano), sel_dist [E,k] (nullable), valid [E] u8.  A label outside [0,P) belongs to no part.  Per edge:
+ *     d_i          = min over j with seg[j] == b of ((dx*dx)+(dy*dy))+(dz*dz), for every i with seg[i] == a   (fp32, no FMA:
+ *                    the rounding of the K-NN searches at D = 3); the neighbour of i is the LOWEST j attaining the minimum
+ *     row r        = the r-th smallest key (bits of d_i, i), r = 0 .. k-1: src_idx = i, tgt_idx = its neighbour, sel_dist = d_i
+ *     valid[e]     = a, b in [0,P), |a| >= k and |b| >= 1 (outside that the reference raises); an invalid edge gets
+ *                    valid = 0, indices 0, distance 0, and contributes nothing to reart_connection_term
+ *   A self edge (a, a) follows from the rule: every d_i = +0, the k lowest indices of the part, each paired with the lowest
+ *   index at its coordinates (itself, unless an earlier point of the part coincides with it).
+ *   Every index written is a member of its part, or the edge is invalid, whatever the coordinates hold: non-finite
+ *   coordinates give a meaningless selection, never an out-of-range access.
+ *   Three launches: the parts' member lists (a stable counting sort by label), the search (the sources of an edge divided
+ *   among up to 16 workgroups of 256, the target members tiled through LDS, a top-k per wave), the merge of the workgroups'
+ *   partial lists.
+ *
+ * reart_connection_term: pc_trans [T,N,3] and the tables above ->
+ *     edge_cost[e] = (1/k) sum_t sum_r |p[t,src(e,r)] - p[t,tgt(e,r)]|^2     (the squared distances in fp32 with the rounding
+ *                    above, added in double in a fixed order, divided by k, rounded once)
+ *     loss         = weight * sum_e edge_cost[e]                             (in double, rounded once)
+ *     grad[t,n]    = sum of +-(2 weight / k)(p[t,src] - p[t,tgt]) over the records that name n, + as a source, - as a target.
+ *   A record is 2 (e k + r) + role (role 0: the source of row r of edge e, 1: its target); a point's records are added in
+ *   ascending record number, in fp32: the order depends on the index tables only.  grad is written completely, zeros where no
+ *   record arrives.  Rows of an edge with valid = 0, and rows with an index outside [0,N), take no part.
+ *   Three launches with grad (the edge costs; the records grouped by point; the gradient and the loss), two without.
+ * Outputs: loss (required), edge_cost [E], grad (both nullable).
+ *
+ * Limits: T <= REART_MAX_POSE_LEN, P <= 64, E <= 4096, 1 <= k <= REART_CONN_MAX_K, N <= REART_CONN_MAX_N (a key carries two
+ * point indices in 32 bits): beyond them the workspace queries return 0 and the calls REART_ERR_UNSUPPORTED.  A NULL required
+ * pointer (the tables and pairs are required when E > 0), a non-positive T, N, P or k, E < 0, a NULL or short workspace:
+ * REART_ERR_INVALID_ARG.  E == 0: nothing selected; loss 0, grad zeros. */
+#define REART_CONN_MAX_N 65536
+#define REART_CONN_MAX_K 64
+size_t reart_connection_select_workspace_bytes(int N, int P, int E, int k);
+int reart_connection_select(const float *cano, const int64_t *seg, int N, int P, const int32_t *pairs, int E, int k,
+                            int32_t *src_idx, int32_t *tgt_idx, float *sel_dist, uint8_t *valid, void *workspace,
+                            size_t workspace_bytes, void *stream);
+size_t reart_connection_term_workspace_bytes(int T, int N, int E, int k);
+int reart_connection_term(const float *pc_trans, const int32_t *src_idx, const int32_t *tgt_idx, const uint8_t *valid, int T,
+                          int N, int E, int k, float weight, float *loss, float *edge_cost, float *grad, void *workspace,
+                          size_t workspace_bytes, void *stream);
+
 /* Replaces fps_sample_cano (utils/graph_utils.py:37-52): farthest point sampling inside every part, one
  * workgroup per part.  cano [N,3], seg [N] i64, labels [Ps] i64 -> idx [Ps,num_fps] i64 (indices into cano,
  * start = the part's first point like the reference's CUDA FPS; -1 when the part has fewer than num_fps

@@ -29,6 +29,8 @@ PART_FPS_MAX_N = 19200   # REART_PART_FPS_MAX_N: reart_part_fps, 8 B of LDS per 
 PC_GRAD_MAX_P = 1024     # parts of reart_compute_pc_transform_backward: one frame's pose rows staged in LDS
 STRUCT_MAX_P = 64        # parts of reart_structure_term / reart_rel_trans_backward, as the kinematic entries
 STRUCT_MAX_E = 4096      # their edges: a part's incidence list is held in LDS
+CONN_MAX_N = 65536       # REART_CONN_MAX_N: points of reart_connection_select / reart_connection_term (two indices in 32 bits of a key)
+CONN_MAX_K = 64          # REART_CONN_MAX_K: pairs per edge, one wave's list
 ADAM_MAX_TENSORS = 32   # REART_ADAM_MAX_TENSORS: records of one reart_adam_groups call, passed by value to its kernel
 
 # name -> (restype, argtypes); mirrors include/reart_hip.h one to one
@@ -144,6 +146,10 @@ PROTOTYPES = {
     "reart_structure_term": (c_int, [P, c_int, c_int, P, c_int, c_float, P, P, P, P, P, c_size_t, P]),
     "reart_rel_trans_backward_workspace_bytes": (c_size_t, [c_int] * 3),
     "reart_rel_trans_backward": (c_int, [P, c_int, c_int, P, c_int, P, P, P, c_size_t, P]),
+    "reart_connection_select_workspace_bytes": (c_size_t, [c_int] * 4),
+    "reart_connection_select": (c_int, [P, P, c_int, c_int, P, c_int, c_int, P, P, P, P, P, c_size_t, P]),
+    "reart_connection_term_workspace_bytes": (c_size_t, [c_int] * 4),
+    "reart_connection_term": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_float, P, P, P, P, c_size_t, P]),
     "reart_part_fps": (c_int, [P, P, c_int, P, c_int, c_int, c_int, P, P, P]),
     "reart_part_pair_cost": (c_int, [P, P, c_int, c_int, c_int, P, P, P, P]),
     "reart_group_temporal_err": (c_int, [P, c_int, c_int, P, P, c_int, P, P, P]),

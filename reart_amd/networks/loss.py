@@ -1,5 +1,6 @@
 """Host-side mirror of the reference's ``networks/loss.py`` (recon_loss ``:24-29``, flow_loss
-``:10-21``, structure_loss ``:32-57``, compute_connection_loss ``:60-78``) over the HIP kernels."""
+``:10-21``, structure_loss ``:32-57``, compute_connection_loss ``:60-78``) over the HIP kernels; ``StructureTerm`` and
+``ConnectionTerm`` are the last two as one native operator each."""
 import torch
 
 from .. import _lib
@@ -191,3 +192,164 @@ def compute_connection_loss(cano_pc, seg_part, joint_connection, pc_trans_list, 
         d = ((pc_trans_list[:, raw_src, :] - pc_trans_list[:, raw_tgt, :]) ** 2).sum(dim=2).mean(dim=1)
         loss = loss + d
     return loss.sum(dim=0)
+
+
+# ----------------------------------------------------------------------------------------------- connection term
+def _connection_select_call(cano, seg, pairs, P, k):
+    """One ``reart_connection_select`` call on contiguous device tensors -> (src_idx [E,k] i32, tgt_idx [E,k] i32, valid [E] u8)."""
+    N, E, dev = cano.shape[0], pairs.shape[0], cano.device
+    src = torch.empty((E, k), dtype=torch.int32, device=dev)
+    tgt = torch.empty((E, k), dtype=torch.int32, device=dev)
+    valid = torch.empty((E,), dtype=torch.uint8, device=dev)
+    L = _lib.lib()
+    ws = _lib.workspace(L.reart_connection_select_workspace_bytes(N, P, E, k), dev)
+    rc = L.reart_connection_select(_lib.ptr(cano), _lib.ptr(seg), N, P, _lib.ptr(pairs), E, k, _lib.ptr(src), _lib.ptr(tgt), None,
+                                   _lib.ptr(valid), _lib.ptr(ws), ws.numel(), _lib.stream())
+    _lib.check(rc, "reart_connection_select")
+    return src, tgt, valid
+
+
+def _connection_term_call(pc, src, tgt, valid, k, weight, want_grad):
+    """One ``reart_connection_term`` call -> (loss, edge_cost [E], grad or None)."""
+    T, N, E, dev = pc.shape[0], pc.shape[1], src.shape[0], pc.device
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    cost = torch.empty((E,), dtype=torch.float32, device=dev)
+    grad = torch.empty_like(pc) if want_grad else None
+    L = _lib.lib()
+    ws = _lib.workspace(L.reart_connection_term_workspace_bytes(T, N, E, k), dev)
+    rc = L.reart_connection_term(_lib.ptr(pc), _lib.ptr(src), _lib.ptr(tgt), _lib.ptr(valid), T, N, E, k, float(weight),
+                                 _lib.ptr(loss), _lib.ptr(cost), _lib.ptr(grad), _lib.ptr(ws), ws.numel(), _lib.stream())
+    _lib.check(rc, "reart_connection_term")
+    return loss, cost, grad
+
+
+class _ConnectionTermFn(torch.autograd.Function):
+    """The _StructureTermFn pattern: the forward has computed the value and its gradient, the backward scales it."""
+
+    @staticmethod
+    def forward(ctx, pc, src, tgt, valid, k, weight, sink):
+        want = ctx.needs_input_grad[0]
+        loss, cost, grad = _connection_term_call(pc.detach().contiguous(), src, tgt, valid, k, weight, want)
+        sink._last = (cost, src, tgt, valid)
+        if want:
+            ctx.save_for_backward(grad)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return grad * g, None, None, None, None, None, None
+
+
+class ConnectionTerm(torch.nn.Module):
+    """``forward(cano_pc [N,3], seg_part [N], pc_trans_list [T,N,3]) -> scalar``: ``weight`` x the reference's
+
+        compute_connection_loss(cano_pc, seg_part, joint_connection, pc_trans_list, chamfer_dist, k)
+
+    (networks/loss.py:60-78) as two native calls on the current stream, ``reart_connection_select`` and
+    ``reart_connection_term`` (six launches, no host synchronisation, the same bits on every run): per edge (a, b) of
+    ``joint_connection`` [E,2] the ``k`` points of part a closest to part b, each with its nearest point of part b, in the
+    canonical cloud; then the mean over those pairs of their squared distance in every frame, summed over frames and edges.
+    Differentiable w.r.t. ``pc_trans_list``; the selection is a constant, as in the reference.  Without
+    ``pc_trans_list.requires_grad`` no gradient buffer is allocated.
+
+    Ties, where ``topk`` and the search of the composition leave the choice open: the nearest point is the one of lowest
+    index, the ``k`` sources are the smallest (distance, index).  An edge whose source part has fewer than ``k`` points or
+    whose target part is empty (the reference raises) is invalid: it costs nothing and has no gradient.  A label outside
+    [0, P) belongs to no part.
+
+    ``select(cano_pc, seg_part)`` computes and keeps the tables; ``forward(pc_trans_list)`` with one argument then reuses
+    them (one native call; a KinematicModel's cloud and labels never change) until ``reset()``.
+    ``.last`` holds ``(edge_cost [E], src_idx [E,k], tgt_idx [E,k], valid [E] bool)`` of the latest call.
+
+    P is the largest edge index + 1 unless ``num_parts`` is given.  Limits: float32 clouds (``TypeError`` otherwise);
+    T <= 1024, P <= 64, E <= 4096, 1 <= k <= 64, N <= 65 536 (``NotImplementedError``); an edge index outside [0, P) or a
+    shape mismatch raises ``ValueError``; host tensors raise ``RuntimeError: ... no CPU fallback``."""
+
+    def __init__(self, joint_connection, k=10, weight=1.0, num_parts=None):
+        super().__init__()
+        el = torch.as_tensor(joint_connection).detach().cpu().to(torch.int64).reshape(-1, 2)
+        self.k, self.weight = int(k), float(weight)
+        self._lo = int(el.min()) if el.numel() else 0
+        self._hi = int(el.max()) if el.numel() else -1
+        self.num_parts = int(num_parts) if num_parts is not None else max(self._hi + 1, 1)
+        self._edges = el.to(torch.int32).contiguous()
+        self._pairs = {}
+        self._kept = None      # (src_idx, tgt_idx, valid, N) of select()
+        self._last = None
+
+    @property
+    def last(self):
+        return None if self._last is None else self._last[:3] + (self._last[3].bool(),)
+
+    def reset(self):
+        self._kept = None
+
+    def _check_static(self):
+        if self._lo < 0 or self._hi >= self.num_parts:
+            raise ValueError(f"ConnectionTerm: edge indices in [{self._lo}, {self._hi}] for P = {self.num_parts} parts")
+
+    def _check_limits(self, N, T=1):
+        E = self._edges.shape[0]
+        if T > _lib.MAX_POSE_LEN:
+            raise NotImplementedError(f"connection term: T = {T} frames above REART_MAX_POSE_LEN = {_lib.MAX_POSE_LEN}")
+        if self.num_parts > _lib.STRUCT_MAX_P:
+            raise NotImplementedError(f"connection term: P = {self.num_parts} parts above {_lib.STRUCT_MAX_P}")
+        if E > _lib.STRUCT_MAX_E:
+            raise NotImplementedError(f"connection term: E = {E} edges above {_lib.STRUCT_MAX_E}")
+        if not 1 <= self.k <= _lib.CONN_MAX_K:
+            raise NotImplementedError(f"connection term: k = {self.k} outside [1, {_lib.CONN_MAX_K}]")
+        if N > _lib.CONN_MAX_N:
+            raise NotImplementedError(f"connection term: N = {N} points above {_lib.CONN_MAX_N}")
+
+    @staticmethod
+    def _check_cloud(cano, seg):
+        if cano.dtype != torch.float32:
+            raise TypeError(f"ConnectionTerm: a float32 canonical cloud, not {cano.dtype}")
+        if seg.dtype.is_floating_point or seg.dtype.is_complex or seg.dtype == torch.bool:
+            raise TypeError(f"ConnectionTerm: integer labels, not {seg.dtype}")
+        if cano.dim() != 2 or cano.shape[1] != 3 or cano.shape[0] < 1 or tuple(seg.shape) != (cano.shape[0],):
+            raise ValueError(f"ConnectionTerm: cano_pc [N,3] and seg_part [N], not {tuple(cano.shape)} and {tuple(seg.shape)}")
+
+    @staticmethod
+    def _check_frames(pc, N):
+        if pc.dtype != torch.float32:
+            raise TypeError(f"ConnectionTerm: float32 frames, not {pc.dtype}")
+        if pc.dim() != 3 or pc.shape[0] < 1 or tuple(pc.shape[1:]) != (N, 3):
+            raise ValueError(f"ConnectionTerm: pc_trans_list [T,{N},3], not {tuple(pc.shape)}")
+
+    def _select(self, cano, seg):
+        pairs = self._pairs.get(cano.device)
+        if pairs is None:
+            pairs = self._pairs[cano.device] = self._edges.to(cano.device)
+        return _connection_select_call(cano.detach().contiguous(), seg.to(torch.int64).contiguous(), pairs, self.num_parts, self.k)
+
+    def select(self, cano_pc, seg_part):
+        self._check_cloud(cano_pc, seg_part)
+        self._check_static()
+        self._check_limits(cano_pc.shape[0])
+        _lib.require_gpu(cano_pc, seg_part)
+        self._kept = self._select(cano_pc, seg_part) + (cano_pc.shape[0],)
+        return self
+
+    def forward(self, *args):
+        if len(args) == 1:
+            (pc,) = args
+            if self._kept is None:
+                raise RuntimeError("ConnectionTerm: forward(pc_trans_list) needs the tables of select(cano_pc, seg_part)")
+            src, tgt, valid, N = self._kept
+            self._check_frames(pc, N)
+            self._check_limits(N, pc.shape[0])
+            _lib.require_gpu(pc)
+            if pc.device != src.device:
+                raise ValueError(f"ConnectionTerm: tables on {src.device}, frames on {pc.device}")
+        else:
+            cano, seg, pc = args
+            self._check_cloud(cano, seg)
+            self._check_frames(pc, cano.shape[0])
+            self._check_static()
+            self._check_limits(cano.shape[0], pc.shape[0])
+            _lib.require_gpu(cano, seg, pc)
+            src, tgt, valid = self._select(cano, seg)
+        return _ConnectionTermFn.apply(pc, src, tgt, valid, self.k, self.weight, self)
