@@ -850,6 +850,11 @@ int reart_lap_auction_large(const float *cost, const float *src, const float *tg
                             int32_t *col4row, int32_t *certified, double *price_out,
                             void *workspace, size_t workspace_bytes, void *stream);
 
+/* Byte offset of the diagnostics block [B][4] i32 in the workspace of every reart_lap_* solver (they all begin with the same two
+ * blocks), for a host that reads the statistics words or hands them to reart_publish_words.  Host only, launches nothing.
+ * 0 unless B >= 0 and 1 <= n <= REART_LAP_LARGE_MAX_N. */
+size_t reart_lap_stats_offset(int B, int n);
+
 /* The same solve warm-started from an earlier solve of a similar batch (the loop re-solves every assign_gap
  * iterations): on entry col4row holds that solve's assignment and price_in (required) its potentials; pairs that are
  * still epsilon-tight under the new costs are kept.  Certified like a cold solve.  Use when the costs move smoothly

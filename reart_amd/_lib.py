@@ -122,6 +122,7 @@ PROTOTYPES = {
     "reart_lap_auction_race_warm": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P, P, P, P, c_size_t, P]),
     "reart_lap_large_workspace_bytes": (c_size_t, [c_int] * 2),
     "reart_lap_auction_large": (c_int, [P, P, P, c_int, c_int, P, P, P, P, c_size_t, P]),
+    "reart_lap_stats_offset": (c_size_t, [c_int] * 2),
     "reart_lap_resolve": (c_int, [P, c_int, c_int, P, P, P, P, P, c_size_t, P]),
     "reart_lap_resolve_large_workspace_bytes": (c_size_t, [c_int] * 2),
     "reart_lap_resolve_large": (c_int, [P, c_int, c_int, c_int, P, P, P, P, P, c_size_t, P]),

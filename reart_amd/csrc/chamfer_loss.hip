@@ -38,19 +38,18 @@ static int chamfer_loss_plan(int N, int P1, int P2, ChamferLossPlan *p) {
     p->nqg = q1 > q2 ? q1 : q2;
     p->nr1 = reart_div_up(P1, CL_BS); p->nr2 = reart_div_up(P2, CL_BS);
     p->nparts = N * (p->nr1 + p->nr2);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += reart_align_up(bytes, 256); return o; };
-    p->o_xsoa = take(sizeof(float) * 3 * (size_t)N * p->Ppad1);
-    p->o_ysoa = take(sizeof(float) * 3 * (size_t)N * p->Ppad2);
-    p->o_xbox = take(sizeof(float) * 8 * (size_t)N * (p->Ppad1 / NN_BOX));
-    p->o_ybox = take(sizeof(float) * 8 * (size_t)N * (p->Ppad2 / NN_BOX));
-    p->o_pd0 = take(sizeof(float) * (size_t)N * P1);
-    p->o_pi0 = take(sizeof(int) * (size_t)N * P1);
-    p->o_pd1 = take(sizeof(float) * (size_t)N * P2);
-    p->o_pi1 = take(sizeof(int) * (size_t)N * P2);
-    p->o_part = take(sizeof(double) * (size_t)(p->nparts > 0 ? p->nparts : 1));
-    p->o_ticket = take(sizeof(unsigned int));
-    p->total = off;
+    reart_arena ws;
+    p->o_xsoa = ws.take_bytes(sizeof(float) * 3 * (size_t)N * p->Ppad1);
+    p->o_ysoa = ws.take_bytes(sizeof(float) * 3 * (size_t)N * p->Ppad2);
+    p->o_xbox = ws.take_bytes(sizeof(float) * 8 * (size_t)N * (p->Ppad1 / NN_BOX));
+    p->o_ybox = ws.take_bytes(sizeof(float) * 8 * (size_t)N * (p->Ppad2 / NN_BOX));
+    p->o_pd0 = ws.take_bytes(sizeof(float) * (size_t)N * P1);
+    p->o_pi0 = ws.take_bytes(sizeof(int) * (size_t)N * P1);
+    p->o_pd1 = ws.take_bytes(sizeof(float) * (size_t)N * P2);
+    p->o_pi1 = ws.take_bytes(sizeof(int) * (size_t)N * P2);
+    p->o_part = ws.take_bytes(sizeof(double) * (size_t)(p->nparts > 0 ? p->nparts : 1));
+    p->o_ticket = ws.take_bytes(sizeof(unsigned int));
+    p->total = ws.off;
     return REART_OK;
 }
 

@@ -35,6 +35,17 @@ typedef float f2 __attribute__((ext_vector_type(2)));
 static inline size_t reart_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 static inline int reart_div_up(int a, int b) { return (a + b - 1) / b; }
 
+// One walk over a caller-owned workspace (host only): a layout function takes its blocks from an arena in order, so the size an
+// operator reports and the pointers it carves come from the same lines.  Blocks are rounded up to 256 bytes (round = 1: a nested
+// operator's workspace, at the size that operator reports).  A null base only sizes: take<T>() gives null, `off` is the total.
+struct reart_arena {
+    char *base;
+    size_t off;
+    explicit reart_arena(void *workspace = nullptr) : base((char *)workspace), off(0) {}
+    size_t take_bytes(size_t bytes, size_t round = 256) { const size_t o = off; off += reart_align_up(bytes, round); return o; }
+    template <class T> T *take(size_t n, size_t round = 256) { const size_t o = take_bytes(sizeof(T) * n, round); return base ? (T *)(base + o) : nullptr; }
+};
+
 // Squared distance with the library-wide rounding contract:
 //   ((dx*dx) + (dy*dy)) + (dz*dz), fp32, no contraction.
 __device__ __forceinline__ float reart_sqdist3(float ax, float ay, float az,

@@ -40,14 +40,24 @@ static bool ct_shape_ok(int T, int N, int E, int k) {
     return T >= 1 && T <= REART_MAX_POSE_LEN && N >= 1 && N <= CS_MAX_N && E >= 0 && E <= CS_MAX_E && k >= 1 && k <= CS_MAX_K;
 }
 static int cs_slots(int N) { const int g = reart_div_up(N, CS_SRC); return g < CS_MAX_G ? g : CS_MAX_G; }
-static size_t cs_members_bytes(int N) { return reart_align_up(sizeof(int) * (size_t)N, 256); }
-static size_t cs_parts_bytes() { return reart_align_up(sizeof(int) * 2 * CS_MAX_P, 256); }
-static size_t cs_partial_bytes(int N, int E, int k) {
-    return reart_align_up(sizeof(u64) * (size_t)(E > 0 ? E : 1) * cs_slots(N) * k, 256);
+// select: the parts' member lists [N], their sizes and first members [2][CS_MAX_P], every slot's k best keys [E][slots][k]
+struct CsWs { int *members, *count; u64 *partial; };
+static size_t cs_ws_layout(int N, int E, int k, void *workspace, CsWs *w) {
+    reart_arena ws(workspace);
+    w->members = ws.take<int>((size_t)N);
+    w->count = ws.take<int>(2 * CS_MAX_P);
+    w->partial = ws.take<u64>((size_t)(E > 0 ? E : 1) * cs_slots(N) * k);
+    return ws.off;
 }
-static size_t ct_cost_bytes(int E) { return reart_align_up(sizeof(double) * (size_t)(E > 0 ? E : 1), 256); }
-static size_t ct_start_bytes(int N) { return reart_align_up(sizeof(int) * ((size_t)N + 1), 256); }
-static size_t ct_list_bytes(int E, int k) { return reart_align_up(sizeof(int) * 2 * (size_t)(E > 0 ? E : 1) * k, 256); }
+// term: the edges' costs in double [E], the points' record lists as offsets [N + 1] and records [2][E][k]
+struct CtWs { double *cost_d; int *start, *list; };
+static size_t ct_ws_layout(int N, int E, int k, void *workspace, CtWs *w) {
+    reart_arena ws(workspace);
+    w->cost_d = ws.take<double>(E > 0 ? E : 1);
+    w->start = ws.take<int>((size_t)N + 1);
+    w->list = ws.take<int>(2 * (size_t)(E > 0 ? E : 1) * k);
+    return ws.off;
+}
 
 // items per wave when CT_WAVES waves share n items in contiguous runs, whole steps of 64
 __device__ __forceinline__ int cs_run(int n) { return (n + CT_WAVES * 64 - 1) / (CT_WAVES * 64) * 64; }
@@ -332,8 +342,8 @@ __global__ __launch_bounds__(256) void ct_grad_kernel(const float *__restrict__ 
 
 // ------------------------------------------------------------------------------------------------------------ host
 extern "C" size_t reart_connection_select_workspace_bytes(int N, int P, int E, int k) {
-    if (!cs_shape_ok(N, P, E, k)) return 0;
-    return cs_members_bytes(N) + cs_parts_bytes() + cs_partial_bytes(N, E, k);
+    CsWs w;
+    return cs_shape_ok(N, P, E, k) ? cs_ws_layout(N, E, k, nullptr, &w) : 0;
 }
 
 extern "C" int reart_connection_select(const float *cano, const int64_t *seg, int N, int P, const int32_t *pairs, int E, int k,
@@ -342,23 +352,22 @@ extern "C" int reart_connection_select(const float *cano, const int64_t *seg, in
     if (!cano || !seg || N <= 0 || P <= 0 || E < 0 || k <= 0 || (E > 0 && (!pairs || !src_idx || !tgt_idx || !valid)))
         return REART_ERR_INVALID_ARG;
     if (!cs_shape_ok(N, P, E, k)) return REART_ERR_UNSUPPORTED;
-    if (!workspace || workspace_bytes < reart_connection_select_workspace_bytes(N, P, E, k)) return REART_ERR_INVALID_ARG;
+    CsWs w;
+    if (!workspace || workspace_bytes < cs_ws_layout(N, E, k, workspace, &w)) return REART_ERR_INVALID_ARG;
     if (E == 0) return REART_OK;
     hipStream_t st = (hipStream_t)stream;
-    int *members = (int *)workspace;
-    int *count = (int *)((char *)workspace + cs_members_bytes(N)), *base = count + CS_MAX_P;
-    u64 *partial = (u64 *)((char *)workspace + cs_members_bytes(N) + cs_parts_bytes());
+    int *count = w.count, *base = count + CS_MAX_P;
     const int G = cs_slots(N);
-    hipLaunchKernelGGL(cs_members_kernel, dim3(P), dim3(CT_WAVES * 64), 0, st, seg, N, P, members, count, base);
-    hipLaunchKernelGGL(cs_search_kernel, dim3(E, G), dim3(CS_SRC), 0, st, cano, pairs, members, count, base, P, k, partial);
-    hipLaunchKernelGGL(cs_merge_kernel, dim3(E), dim3(64), 0, st, pairs, count, P, k, G, partial, src_idx, tgt_idx, sel_dist, valid);
+    hipLaunchKernelGGL(cs_members_kernel, dim3(P), dim3(CT_WAVES * 64), 0, st, seg, N, P, w.members, count, base);
+    hipLaunchKernelGGL(cs_search_kernel, dim3(E, G), dim3(CS_SRC), 0, st, cano, pairs, w.members, count, base, P, k, w.partial);
+    hipLaunchKernelGGL(cs_merge_kernel, dim3(E), dim3(64), 0, st, pairs, count, P, k, G, w.partial, src_idx, tgt_idx, sel_dist, valid);
     REART_CHECK_LAUNCH();
     return REART_OK;
 }
 
 extern "C" size_t reart_connection_term_workspace_bytes(int T, int N, int E, int k) {
-    if (!ct_shape_ok(T, N, E, k)) return 0;
-    return ct_cost_bytes(E) + ct_start_bytes(N) + ct_list_bytes(E, k);
+    CtWs w;
+    return ct_shape_ok(T, N, E, k) ? ct_ws_layout(N, E, k, nullptr, &w) : 0;
 }
 
 extern "C" int reart_connection_term(const float *pc_trans, const int32_t *src_idx, const int32_t *tgt_idx, const uint8_t *valid,
@@ -367,19 +376,17 @@ extern "C" int reart_connection_term(const float *pc_trans, const int32_t *src_i
     if (!pc_trans || !loss || T <= 0 || N <= 0 || E < 0 || k <= 0 || (E > 0 && (!src_idx || !tgt_idx || !valid)))
         return REART_ERR_INVALID_ARG;
     if (!ct_shape_ok(T, N, E, k)) return REART_ERR_UNSUPPORTED;
-    if (!workspace || workspace_bytes < reart_connection_term_workspace_bytes(T, N, E, k)) return REART_ERR_INVALID_ARG;
+    CtWs w;
+    if (!workspace || workspace_bytes < ct_ws_layout(N, E, k, workspace, &w)) return REART_ERR_INVALID_ARG;
     hipStream_t st = (hipStream_t)stream;
-    double *cost_d = (double *)workspace;
-    int *start = (int *)((char *)workspace + ct_cost_bytes(E));
-    int *list = (int *)((char *)workspace + ct_cost_bytes(E) + ct_start_bytes(N));
     const CtTables c{src_idx, tgt_idx, valid, N, E, k};
-    if (E > 0) hipLaunchKernelGGL(ct_cost_kernel, dim3(E), dim3(256), 0, st, pc_trans, c, T, cost_d, edge_cost);
+    if (E > 0) hipLaunchKernelGGL(ct_cost_kernel, dim3(E), dim3(256), 0, st, pc_trans, c, T, w.cost_d, edge_cost);
     if (grad) {     // E == 0: every list is empty, the gradient is written as zeros
-        hipLaunchKernelGGL(ct_index_kernel, dim3(reart_div_up(N, CT_TILE)), dim3(CT_WAVES * 64), 0, st, c, start, list);
+        hipLaunchKernelGGL(ct_index_kernel, dim3(reart_div_up(N, CT_TILE)), dim3(CT_WAVES * 64), 0, st, c, w.start, w.list);
         hipLaunchKernelGGL(ct_grad_kernel, dim3(reart_div_up(N, 256), T), dim3(256), 0, st, pc_trans, c, 2.0f * weight / (float)k,
-                           start, list, grad, cost_d, weight, loss);
+                           w.start, w.list, grad, w.cost_d, weight, loss);
     } else {
-        hipLaunchKernelGGL(ct_loss_kernel, dim3(1), dim3(256), 0, st, cost_d, E, weight, loss);
+        hipLaunchKernelGGL(ct_loss_kernel, dim3(1), dim3(256), 0, st, w.cost_d, E, weight, loss);
     }
     REART_CHECK_LAUNCH();
     return REART_OK;

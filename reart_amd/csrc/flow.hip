@@ -26,18 +26,19 @@ __global__ __launch_bounds__(256) void blend_kernel(const float *__restrict__ di
     mask[n] = m;
 }
 
-static size_t blend_ws_layout(int nq, int nr, int k, size_t *o_d, size_t *o_i, size_t *o_knn) {
-    size_t off = 0;
-    *o_d = off; off += reart_align_up(sizeof(float) * (size_t)nq * k, 256);
-    *o_i = off; off += reart_align_up(sizeof(int64_t) * (size_t)nq * k, 256);
-    *o_knn = off; off += reart_knn_points_workspace_bytes(1, nq, nr, k);
-    return off;
+// the k neighbours' distances and indices [B][nq][k], then the search's own workspace at the size it reports (B = 1: one pair)
+struct BlendWs { float *dist; int64_t *idx; char *knn; size_t knn_bytes; };
+static size_t blend_ws_layout(int B, int nq, int nr, int k, void *workspace, BlendWs *w) {
+    reart_arena ws(workspace);
+    w->dist = ws.take<float>((size_t)B * nq * k);
+    w->idx = ws.take<int64_t>((size_t)B * nq * k);
+    w->knn_bytes = reart_knn_points_workspace_bytes(B, nq, nr, k);
+    w->knn = ws.take<char>(w->knn_bytes, 1);
+    return ws.off;
 }
 
 extern "C" size_t reart_blend_anchor_motion_workspace_bytes(int nq, int nr, int k) {
-    if (nq <= 0 || nr <= 0 || k <= 0) return 0;
-    size_t a, b, c;
-    return blend_ws_layout(nq, nr, k, &a, &b, &c);
+    return reart_blend_anchor_motion_batch_workspace_bytes(1, nq, nr, k);
 }
 
 extern "C" int reart_blend_anchor_motion(const float *query, const float *ref, const float *ref_flow,
@@ -49,17 +50,12 @@ extern "C" int reart_blend_anchor_motion(const float *query, const float *ref, c
     if (k > nr) return REART_ERR_INVALID_ARG;
     if (nq == 0) return REART_OK;
     if (!query || !ref || !ref_flow || !flow || !mask || !workspace) return REART_ERR_INVALID_ARG;
-    size_t o_d, o_i, o_knn;
-    if (workspace_bytes < blend_ws_layout(nq, nr, k, &o_d, &o_i, &o_knn)) return REART_ERR_INVALID_ARG;
-    char *ws = (char *)workspace;
-    float *dist = (float *)(ws + o_d);
-    int64_t *idx = (int64_t *)(ws + o_i);
+    BlendWs w;
+    if (workspace_bytes < blend_ws_layout(1, nq, nr, k, workspace, &w)) return REART_ERR_INVALID_ARG;
     hipStream_t st = (hipStream_t)stream;
-    int rc = reart_knn_run(1, &query, &ref, nullptr, nullptr, 1, &nq, &nr, k, euclidean ? 1 : 0, &dist,
-                           &idx, ws + o_knn, workspace_bytes - o_knn, st);
+    int rc = reart_knn_run(1, &query, &ref, nullptr, nullptr, 1, &nq, &nr, k, euclidean ? 1 : 0, &w.dist, &w.idx, w.knn, w.knn_bytes, st);
     if (rc != REART_OK) return rc;
-    hipLaunchKernelGGL(blend_kernel, dim3(reart_div_up(nq, 256)), dim3(256), 0, st, dist, idx, ref_flow,
-                       nq, k, flow, mask);
+    hipLaunchKernelGGL(blend_kernel, dim3(reart_div_up(nq, 256)), dim3(256), 0, st, w.dist, w.idx, ref_flow, nq, k, flow, mask);
     REART_CHECK_LAUNCH();
     return REART_OK;
 }
@@ -82,18 +78,10 @@ __global__ __launch_bounds__(256) void blend_batch_kernel(const float *__restric
     mask[q] = m;
 }
 
-static size_t blend_batch_ws_layout(int B, int nq, int nr, int k, size_t *o_d, size_t *o_i, size_t *o_knn) {
-    size_t off = 0;
-    *o_d = off; off += reart_align_up(sizeof(float) * (size_t)B * nq * k, 256);
-    *o_i = off; off += reart_align_up(sizeof(int64_t) * (size_t)B * nq * k, 256);
-    *o_knn = off; off += reart_knn_points_workspace_bytes(B, nq, nr, k);
-    return off;
-}
-
 extern "C" size_t reart_blend_anchor_motion_batch_workspace_bytes(int B, int nq, int nr_max, int k) {
     if (B <= 0 || nq <= 0 || nr_max <= 0 || k <= 0) return 0;
-    size_t a, b, c;
-    return blend_batch_ws_layout(B, nq, nr_max, k, &a, &b, &c);
+    BlendWs w;
+    return blend_ws_layout(B, nq, nr_max, k, nullptr, &w);
 }
 
 extern "C" int reart_blend_anchor_motion_batch(const float *query, const float *ref, const float *ref_flow, const int64_t *ref_len,
@@ -104,17 +92,14 @@ extern "C" int reart_blend_anchor_motion_batch(const float *query, const float *
     if (k > nr_max) return REART_ERR_INVALID_ARG;             // (a frame whose ref_len is below k: the caller's error, like nr < k above)
     if (B == 0 || nq == 0) return REART_OK;
     if (!query || !ref || !ref_flow || !flow || !mask || !workspace) return REART_ERR_INVALID_ARG;
-    size_t o_d, o_i, o_knn;
-    if (workspace_bytes < blend_batch_ws_layout(B, nq, nr_max, k, &o_d, &o_i, &o_knn)) return REART_ERR_INVALID_ARG;
-    char *ws = (char *)workspace;
-    float *dist = (float *)(ws + o_d);
-    int64_t *idx = (int64_t *)(ws + o_i);
+    BlendWs w;
+    if (workspace_bytes < blend_ws_layout(B, nq, nr_max, k, workspace, &w)) return REART_ERR_INVALID_ARG;
     hipStream_t st = (hipStream_t)stream;
     const int64_t *lent = ref_len;
-    int rc = reart_knn_run(1, &query, &ref, nullptr, ref_len ? &lent : nullptr, B, &nq, &nr_max, k, euclidean ? 1 : 0, &dist, &idx,
-                           ws + o_knn, workspace_bytes - o_knn, st);
+    int rc = reart_knn_run(1, &query, &ref, nullptr, ref_len ? &lent : nullptr, B, &nq, &nr_max, k, euclidean ? 1 : 0, &w.dist, &w.idx,
+                           w.knn, w.knn_bytes, st);
     if (rc != REART_OK) return rc;
-    hipLaunchKernelGGL(blend_batch_kernel, dim3(reart_div_up(nq, 256), B), dim3(256), 0, st, dist, idx, ref_flow, nq, nr_max, k, flow, mask);
+    hipLaunchKernelGGL(blend_batch_kernel, dim3(reart_div_up(nq, 256), B), dim3(256), 0, st, w.dist, w.idx, ref_flow, nq, nr_max, k, flow, mask);
     REART_CHECK_LAUNCH();
     return REART_OK;
 }

@@ -39,13 +39,12 @@ struct FlowTermCall { int nbx; size_t o_q, o_pd, o_pi, o_gp, o_part, o_col, o_ti
 static void flow_term_call_layout(int B, int N, FlowTermCall *c) {
     c->nbx = reart_div_up(N, FT_BS);
     const size_t rows = sizeof(float) * 3 * (size_t)B * N;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += reart_align_up(bytes, 256); return o; };
-    c->o_q = take(rows); c->o_pd = take(rows); c->o_pi = take(rows); c->o_gp = take(rows);
-    c->o_part = take(sizeof(double) * (size_t)B * c->nbx);
-    c->o_col = take(sizeof(unsigned int) * (size_t)c->nbx);
-    c->o_ticket = take(sizeof(unsigned int));
-    c->total = off;
+    reart_arena ws;
+    c->o_q = ws.take_bytes(rows); c->o_pd = ws.take_bytes(rows); c->o_pi = ws.take_bytes(rows); c->o_gp = ws.take_bytes(rows);
+    c->o_part = ws.take_bytes(sizeof(double) * (size_t)B * c->nbx);
+    c->o_col = ws.take_bytes(sizeof(unsigned int) * (size_t)c->nbx);
+    c->o_ticket = ws.take_bytes(sizeof(unsigned int));
+    c->total = ws.off;
 }
 static bool flow_term_served(int B, int N, int nr_max) {
     return B >= 1 && B <= REART_MAX_POSE_LEN && N >= 1 && N <= FT_MAX_POINTS && nr_max >= 3 && nr_max <= FT_MAX_POINTS &&

@@ -965,9 +965,15 @@ extern "C" int reart_three_nn(const float *xyz1, const float *xyz2, int B, int N
     return REART_OK;
 }
 
+struct Interp3Ws { float *dist; int64_t *idx; };      // the three neighbours [B][N][3]
+static size_t interp3_ws_layout(int B, int N, void *workspace, Interp3Ws *w) {
+    reart_arena ws(workspace);
+    w->dist = ws.take<float>((size_t)B * N * 3); w->idx = ws.take<int64_t>((size_t)B * N * 3);
+    return ws.off;
+}
 extern "C" size_t reart_three_interpolate_workspace_bytes(int B, int N, int S2) {
-    if (B <= 0 || N <= 0 || S2 <= 0) return 0;
-    return reart_align_up(sizeof(float) * (size_t)B * N * 3, 256) + reart_align_up(sizeof(int64_t) * (size_t)B * N * 3, 256);
+    Interp3Ws w;
+    return (B <= 0 || N <= 0 || S2 <= 0) ? 0 : interp3_ws_layout(B, N, nullptr, &w);
 }
 
 extern "C" int reart_three_interpolate(const float *xyz1, const float *xyz2, const float *points2, int B,
@@ -976,14 +982,12 @@ extern "C" int reart_three_interpolate(const float *xyz1, const float *xyz2, con
     if (B < 0 || N < 0 || S2 < 3 || D < 1 || ldo < col0 + D) return REART_ERR_INVALID_ARG;
     if (B == 0 || N == 0) return REART_OK;
     if (!xyz1 || !xyz2 || !points2 || !out || !workspace) return REART_ERR_INVALID_ARG;
-    if (workspace_bytes < reart_three_interpolate_workspace_bytes(B, N, S2)) return REART_ERR_INVALID_ARG;
-    char *ws = (char *)workspace;
-    float *dist = (float *)ws;
-    int64_t *idx = (int64_t *)(ws + reart_align_up(sizeof(float) * (size_t)B * N * 3, 256));
+    Interp3Ws w;
+    if (workspace_bytes < interp3_ws_layout(B, N, workspace, &w)) return REART_ERR_INVALID_ARG;
     hipStream_t st = (hipStream_t)stream;
-    const int rc = reart_three_nn(xyz1, xyz2, B, N, S2, dist, idx, stream);
+    const int rc = reart_three_nn(xyz1, xyz2, B, N, S2, w.dist, w.idx, stream);
     if (rc != REART_OK) return rc;
-    hipLaunchKernelGGL(interp3_kernel, dim3(N, B), dim3(256), 0, st, dist, idx, points2, N, S2, D, out, ldo, col0);
+    hipLaunchKernelGGL(interp3_kernel, dim3(N, B), dim3(256), 0, st, w.dist, w.idx, points2, N, S2, D, out, ldo, col0);
     REART_CHECK_LAUNCH();
     return REART_OK;
 }

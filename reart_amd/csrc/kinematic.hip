@@ -198,10 +198,17 @@ __global__ __launch_bounds__(256) void lm_reduce_kernel(const float *__restrict_
     else g_moment[3 * e + c - 3] = acc;
 }
 
+struct FkBwdWs { float *gpose, *g_lm, *pg_partial; };
+static size_t fk_bwd_ws_layout(int P, int B, int E, void *workspace, FkBwdWs *w) {
+    reart_arena ws(workspace);
+    w->gpose = ws.take<float>(12 * (size_t)B * P);
+    w->g_lm = ws.take<float>(6 * (size_t)B * (E > 0 ? E : 1));
+    w->pg_partial = ws.take<float>(12 * (size_t)B * P * PG_SLICES);      // the slices' partial pose gradients
+    return ws.off;
+}
 extern "C" size_t reart_fk_backward_workspace_bytes(int P, int B, int E) {
-    if (P <= 0 || B <= 0 || E < 0) return 0;
-    return reart_align_up(sizeof(float) * 12 * (size_t)B * P, 256) + reart_align_up(sizeof(float) * 6 * (size_t)B * (E > 0 ? E : 1), 256) +
-           reart_align_up(sizeof(float) * 12 * (size_t)B * P * PG_SLICES, 256);      // gpose | g_lm | the slices' partial pose gradients
+    FkBwdWs w;
+    return (P <= 0 || B <= 0 || E < 0) ? 0 : fk_bwd_ws_layout(P, B, E, nullptr, &w);
 }
 
 int reart_pose_grad_launch(const float *x, const int64_t *part, const float *G, int N, int P, int B, float *partial, hipStream_t st) {
@@ -235,20 +242,18 @@ int reart_fk_backward_launch(const float *x, const int64_t *part, const float *G
     if ((N > 0 && (!x || !part || !G)) || !parent || !edge_of_part || !order || !trans || !workspace) return REART_ERR_INVALID_ARG;
     if (E == 0 && P == 1) return REART_OK;                     // a single part: no joint, every joint gradient is empty
     if (!axis || !moment || !theta || !g_axis || !g_moment || !g_theta) return REART_ERR_INVALID_ARG;
-    if (workspace_bytes < reart_fk_backward_workspace_bytes(P, B, E)) return REART_ERR_INVALID_ARG;
-    float *gpose = (float *)workspace;
-    float *g_lm = (float *)((char *)workspace + reart_align_up(sizeof(float) * 12 * (size_t)B * P, 256));
-    float *pg_partial = (float *)((char *)g_lm + reart_align_up(sizeof(float) * 6 * (size_t)B * (E > 0 ? E : 1), 256));
+    FkBwdWs w;
+    if (workspace_bytes < fk_bwd_ws_layout(P, B, E, workspace, &w)) return REART_ERR_INVALID_ARG;
     if (N > 0) {
-        const int rc = reart_pose_grad_launch(x, part, G, N, P, B, pg_partial, st);
+        const int rc = reart_pose_grad_launch(x, part, G, N, P, B, w.pg_partial, st);
         if (rc != REART_OK) return rc;
     }
-    hipLaunchKernelGGL(pose_grad_sum_kernel, dim3(B), dim3(256), 0, st, N > 0 ? pg_partial : (const float *)nullptr, P, gpose, E,
-                       g_theta, g_distance, g_lm, g_trans);
+    hipLaunchKernelGGL(pose_grad_sum_kernel, dim3(B), dim3(256), 0, st, N > 0 ? w.pg_partial : (const float *)nullptr, P, w.gpose, E,
+                       g_theta, g_distance, w.g_lm, g_trans);
     hipLaunchKernelGGL(fk_bwd_kernel, dim3(reart_div_up(B, 64)), dim3(64), 0, st, parent, edge_of_part, order, P,
-                       axis, moment, theta, distance, B, E, trans, gpose, g_theta, g_distance, g_lm);
+                       axis, moment, theta, distance, B, E, trans, w.gpose, g_theta, g_distance, w.g_lm);
     if (E > 0)
-        hipLaunchKernelGGL(lm_reduce_kernel, dim3(reart_div_up(E * 6, 256)), dim3(256), 0, st, g_lm, B, E, g_axis,
+        hipLaunchKernelGGL(lm_reduce_kernel, dim3(reart_div_up(E * 6, 256)), dim3(256), 0, st, w.g_lm, B, E, g_axis,
                            g_moment);
     REART_CHECK_LAUNCH();
     return REART_OK;

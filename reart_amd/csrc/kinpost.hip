@@ -93,26 +93,25 @@ __global__ __launch_bounds__(64) void kin_loss_kernel(KinPostArgs a, int blocks)
     }
 }
 
-static size_t kp_layout(int B, int N, int nr_max, int k, bool flow, size_t *o_comp, size_t *o_pred, size_t *o_gt, size_t *o_mask, size_t *o_gp,
-                        size_t *o_lf, size_t *o_part, size_t *o_fl, size_t *o_blend) {
-    size_t off = 0;
-    const size_t per = sizeof(float) * (size_t)N * 3;
-    *o_comp = off; off += reart_align_up(per * (B + 1), 256);
-    *o_pred = off; off += reart_align_up(per * B, 256);
-    *o_gt = off; off += reart_align_up(per * B, 256);
-    *o_mask = off; off += reart_align_up((size_t)B * N, 256);
-    *o_gp = off; off += reart_align_up(per * B, 256);
-    *o_lf = off; off += 256;
-    *o_part = off; off += reart_align_up(sizeof(double) * (size_t)B * reart_div_up(N, KP_BS), 256);
-    *o_fl = off; off += flow ? reart_align_up(reart_flow_loss_workspace_bytes(), 256) : 0;
-    *o_blend = off; off += flow ? reart_blend_anchor_motion_batch_workspace_bytes(B, N, nr_max, k) : 0;
-    return off;
+// the flow loss's and the batched blend's own workspaces come last, each at the size its operator reports (flow only)
+struct KinPostWs { float *comp, *pred, *gt, *gp, *loss_flow; uint8_t *mask; double *partial; char *fl, *blend; size_t blend_bytes; };
+static size_t kp_layout(int B, int N, int nr_max, int k, bool flow, void *workspace, KinPostWs *w) {
+    reart_arena ws(workspace);
+    const size_t pts = (size_t)N * 3;
+    w->comp = ws.take<float>(pts * (B + 1)); w->pred = ws.take<float>(pts * B);
+    w->gt = ws.take<float>(pts * B); w->mask = ws.take<uint8_t>((size_t)B * N);
+    w->gp = ws.take<float>(pts * B); w->loss_flow = ws.take<float>(1);
+    w->partial = ws.take<double>((size_t)B * reart_div_up(N, KP_BS));
+    w->fl = ws.take<char>(flow ? reart_flow_loss_workspace_bytes() : 0);
+    w->blend_bytes = flow ? reart_blend_anchor_motion_batch_workspace_bytes(B, N, nr_max, k) : 0;
+    w->blend = ws.take<char>(w->blend_bytes, 1);
+    return ws.off;
 }
 
 extern "C" size_t reart_kin_post_workspace_bytes(int B, int N, int nr_max, int k) {
     if (B <= 0 || N <= 0) return 0;
-    size_t o[9];
-    return kp_layout(B, N, nr_max > 0 ? nr_max : 1, k > 0 ? k : 1, nr_max > 0, o, o + 1, o + 2, o + 3, o + 4, o + 5, o + 6, o + 7, o + 8);
+    KinPostWs w;
+    return kp_layout(B, N, nr_max > 0 ? nr_max : 1, k > 0 ? k : 1, nr_max > 0, nullptr, &w);
 }
 
 extern "C" int reart_kin_post(const float *pc_trans, const float *cano, int B, int N, int cano_idx, const float *pc_src, const float *tgt,
@@ -125,28 +124,24 @@ extern "C" int reart_kin_post(const float *pc_trans, const float *cano, int B, i
     if (n > 0 && (!pc_src || !tgt || !cols || !slot_of_point)) return REART_ERR_INVALID_ARG;
     const bool flow = ref != nullptr;
     if (flow && (!ref_flow || nr_max < k || k < 1)) return REART_ERR_INVALID_ARG;
-    size_t o_comp, o_pred, o_gt, o_mask, o_gp, o_lf, o_part, o_fl, o_blend;
-    if (workspace_bytes < kp_layout(B, N, flow ? nr_max : 1, flow ? k : 1, flow, &o_comp, &o_pred, &o_gt, &o_mask, &o_gp, &o_lf, &o_part, &o_fl, &o_blend))
-        return REART_ERR_INVALID_ARG;
-    char *ws = (char *)workspace;
+    KinPostWs w;
+    if (workspace_bytes < kp_layout(B, N, flow ? nr_max : 1, flow ? k : 1, flow, workspace, &w)) return REART_ERR_INVALID_ARG;
     hipStream_t st = (hipStream_t)stream;
     KinPostArgs a{};
     a.pc_trans = pc_trans; a.cano = cano; a.B = B; a.N = N; a.c = cano_idx;
-    a.comp = (float *)(ws + o_comp); a.pred = (float *)(ws + o_pred);
+    a.comp = w.comp; a.pred = w.pred;
     a.pc_src = pc_src; a.tgt = tgt; a.cols = cols; a.slot = n > 0 ? slot_of_point : nullptr; a.n = n;
     a.two_lambda = (float)(2.0 * (double)lambda_assign); a.lambda_assign = lambda_assign;
-    a.gp = flow ? (const float *)(ws + o_gp) : nullptr; a.loss_flow = (const float *)(ws + o_lf); a.lambda_flow = lambda_flow;
-    a.G = G; a.matched = matched; a.partial = (double *)(ws + o_part); a.losses = losses;
+    a.gp = flow ? w.gp : nullptr; a.loss_flow = w.loss_flow; a.lambda_flow = lambda_flow;
+    a.G = G; a.matched = matched; a.partial = w.partial; a.losses = losses;
     if (flow) {
         const size_t total = (size_t)(B + 1) * N * 3;
         hipLaunchKernelGGL(kin_comp_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a);
         REART_CHECK_LAUNCH();
-        float *gt = (float *)(ws + o_gt);
-        uint8_t *mask = (uint8_t *)(ws + o_mask);
-        int rc = reart_blend_anchor_motion_batch(a.comp, ref, ref_flow, ref_len, B, N, nr_max, k, euclidean, gt, mask, ws + o_blend,
-                                                 workspace_bytes - o_blend, stream);
+        int rc = reart_blend_anchor_motion_batch(a.comp, ref, ref_flow, ref_len, B, N, nr_max, k, euclidean, w.gt, w.mask, w.blend,
+                                                 w.blend_bytes, stream);
         if (rc != REART_OK) return rc;
-        rc = reart_flow_loss(gt, a.pred, mask, B, N, robust, smooth_weight, (float *)(ws + o_lf), (float *)(ws + o_gp), ws + o_fl,
+        rc = reart_flow_loss(w.gt, a.pred, w.mask, B, N, robust, smooth_weight, w.loss_flow, w.gp, w.fl,
                              reart_flow_loss_workspace_bytes(), stream);
         if (rc != REART_OK) return rc;
     }

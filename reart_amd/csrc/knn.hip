@@ -335,24 +335,21 @@ static int knn_plan(int njobs, int N, const int *P1, const int *P2, int K, KnnPl
         minP2 = P2[j] < minP2 ? P2[j] : minP2;
     }
     pl->S = knn_pick_split(waves, minP2, K);
-    size_t off = 0;
+    reart_arena ws;
     for (int j = 0; j < njobs; ++j) {
         pl->L[j] = (int)reart_align_up((size_t)reart_div_up(P2[j], pl->S), NN_UB);
         pl->Ppad[j] = pl->L[j] * pl->S;
-        pl->off_soa[j] = off;
-        off += reart_align_up((size_t)N * 3 * pl->Ppad[j] * sizeof(float), 256);
+        pl->off_soa[j] = ws.take_bytes((size_t)N * 3 * pl->Ppad[j] * sizeof(float));
     }
     for (int j = 0; j < njobs; ++j) {
         pl->off_pd[j] = pl->off_pi[j] = 0;
         if (pl->S > 1) {
             const size_t n = (size_t)pl->S * N * P1[j] * pl->KK;
-            pl->off_pd[j] = off;
-            off += reart_align_up(n * sizeof(float), 256);
-            pl->off_pi[j] = off;
-            off += reart_align_up(n * sizeof(int), 256);
+            pl->off_pd[j] = ws.take_bytes(n * sizeof(float));
+            pl->off_pi[j] = ws.take_bytes(n * sizeof(int));
         }
     }
-    pl->total = off;
+    pl->total = ws.off;
     return REART_OK;
 }
 

@@ -738,21 +738,62 @@ __global__ __launch_bounds__(LAP_BS) void lap_auction_kernel(LapArgs a) {
     if (tid == 0 && a.stats) { int *o = a.stats + 4 * b; o[0] = st_phases + (race ? racer << 16 : 0); o[1] = st_rounds; o[2] = st_bids; o[3] = st_cert; }
 }
 
-extern "C" size_t reart_lap_workspace_bytes(int B, int n);
-// workspace of reart_lap_auction_race: the plain layout, one row-bid array per racer, the `done` flags
-extern "C" size_t reart_lap_race_workspace_bytes(int B, int n, int racers) {
-    if (B < 0 || n < 1 || n > LAP_NMAX || racers < 1 || racers > (LAP_RACE_MAX > JV_RACE_MAX ? LAP_RACE_MAX : JV_RACE_MAX)) return 0;
-    return reart_lap_workspace_bytes(B, n) + reart_align_up(sizeof(double) * (size_t)B * n, 256) * (size_t)racers +
-           reart_align_up(sizeof(int) * (size_t)B, 256);
+// The solvers' workspace: ONE walk.  Every form begins with the potentials and the diagnostics; the race layout continues the
+// plain one, the mc layout the race one (also for one racer), the large re-solve's the plain one.  A form's size is where its
+// walk ends, and the launchers fill their arguments from this struct and from nothing else.
+struct LapWs {
+    double *price; int *stats; size_t stats_off;      // [B][n] potentials (no price_out given) | [B][4] diagnostics, read by the host
+    double *bids, *v1, *cur; int *j1;                 // plain: [B][n] the auction's row bids (n > LAP_NLDS) | the re-solve's pass results
+    double *scale; int *cert_bad;                     //        [B] each
+    double *racer[2]; int *done;                      // race: a [B][n] f64 array per racer (the first two) | [B] the racers' flags
+    double *mc_price;                                 // mc: state of the many-compute-unit row reduction, [B][n] each,
+    int *mc_owner, *mc_assigned, *mc_list, *mc_next, *mc_tree, *mc_tpar, *mc_cnt;      // and [B + 1][8] counters (the problems', the launch's)
+    double *u_ws;                                     // large re-solve: [B][n] row potentials
+    char *large;      // large cold solve, [B][n] each: rows' bids f64 | columns' highest bids u64 | winning rows, rows' bid columns, unassigned rows i32
+};
+enum LapForm { LAP_WS_PLAIN, LAP_WS_RACE, LAP_WS_MC, LAP_WS_RESOLVE_LARGE, LAP_WS_LARGE };
+static size_t lap_ws_layout(LapForm form, int B, int n, int racers, void *workspace, LapWs *w) {
+    reart_arena ws(workspace);
+    const size_t bn = (size_t)B * n;
+    w->price = ws.take<double>(bn);
+    w->stats_off = ws.off;
+    w->stats = ws.take<int>(4 * (size_t)B);
+    if (form == LAP_WS_LARGE) { w->large = ws.take<char>(bn * (8 + 8 + 3 * 4)); return ws.off; }
+    w->bids = ws.take<double>(bn); w->v1 = ws.take<double>(bn); w->cur = ws.take<double>(bn); w->j1 = ws.take<int>(bn);
+    w->scale = ws.take<double>(B); w->cert_bad = ws.take<int>(B);
+    if (form == LAP_WS_RESOLVE_LARGE) w->u_ws = ws.take<double>(bn);
+    if (form == LAP_WS_RACE || form == LAP_WS_MC) {
+        w->racer[0] = ws.take<double>(bn);
+        w->racer[1] = racers > 1 ? ws.take<double>(bn) : nullptr;
+        for (int r = 2; r < racers; ++r) ws.take<double>(bn);
+        w->done = ws.take<int>(B);
+    }
+    if (form == LAP_WS_MC) {
+        w->mc_price = ws.take<double>(bn);
+        w->mc_owner = ws.take<int>(bn); w->mc_assigned = ws.take<int>(bn); w->mc_list = ws.take<int>(bn); w->mc_next = ws.take<int>(bn);
+        w->mc_tree = ws.take<int>(bn); w->mc_tpar = ws.take<int>(bn); w->mc_cnt = ws.take<int>(8 * ((size_t)B + 1));
+    }
+    return ws.off;
 }
 
 extern "C" size_t reart_lap_workspace_bytes(int B, int n) {
-    if (B < 0 || n < 1 || n > LAP_NMAX) return 0;
-    // potentials | diagnostics [B][4] | row bids (n > LAP_NLDS; always reserved) | the re-solve's pass results: v1, cur [B][n] f64,
-    // j1 [B][n] i32, scale [B] f64, cert_bad [B] i32
-    return reart_align_up(sizeof(double) * (size_t)B * n, 256) * 4 + reart_align_up(sizeof(int) * 4 * (size_t)B, 256) +
-           reart_align_up(sizeof(int) * (size_t)B * n, 256) + reart_align_up(sizeof(double) * (size_t)B, 256) +
-           reart_align_up(sizeof(int) * (size_t)B, 256);
+    LapWs w;
+    return (B < 0 || n < 1 || n > LAP_NMAX) ? 0 : lap_ws_layout(LAP_WS_PLAIN, B, n, 1, nullptr, &w);
+}
+extern "C" size_t reart_lap_race_workspace_bytes(int B, int n, int racers) {
+    LapWs w;
+    if (B < 0 || n < 1 || n > LAP_NMAX || racers < 1 || racers > (LAP_RACE_MAX > JV_RACE_MAX ? LAP_RACE_MAX : JV_RACE_MAX)) return 0;
+    return lap_ws_layout(LAP_WS_RACE, B, n, racers, nullptr, &w);
+}
+extern "C" size_t reart_lap_mc_workspace_bytes(int B, int n, int racers) {
+    LapWs w;
+    return reart_lap_race_workspace_bytes(B, n, racers) ? lap_ws_layout(LAP_WS_MC, B, n, racers, nullptr, &w) : 0;
+}
+extern "C" size_t reart_lap_stats_offset(int B, int n) {
+    LapWs w;
+    if (B < 0 || n < 1 || n > REART_LAP_LARGE_MAX_N) return 0;
+    lap_ws_layout(LAP_WS_LARGE, B, n, 1, nullptr, &w);
+    return w.stats_off;
 }
 
 // cost [B,n,n] fp32 (row-major: rows = sources), n <= 4096.  col4row [B,n] i32: column assigned to each row
@@ -766,10 +807,11 @@ static int lap_launch(const float *cost, int B, int n, int32_t *col4row, int32_t
     if (B < 0 || n < 1 || n > LAP_NMAX) return REART_ERR_INVALID_ARG;
     if (B == 0) return REART_OK;
     if (!cost || !col4row || !certified) return REART_ERR_INVALID_ARG;
-    if (!workspace || workspace_bytes < reart_lap_workspace_bytes(B, n)) return REART_ERR_INVALID_ARG;
+    LapWs w;
+    if (!workspace || workspace_bytes < lap_ws_layout(LAP_WS_PLAIN, B, n, 1, workspace, &w)) return REART_ERR_INVALID_ARG;
     LapArgs a = {};
     a.cost = cost; a.B = B; a.n = n; a.col4row = col4row; a.certified = certified;
-    a.price_out = price_out ? price_out : (double *)workspace; a.price_in = price_in;
+    a.price_out = price_out ? price_out : w.price; a.price_in = price_in;
     a.warm_assign = warm_assign;
     a.src = src; a.tgt = tgt;
     a.max_rounds_cert = 4 * n;
@@ -778,8 +820,8 @@ static int lap_launch(const float *cost, int B, int n, int32_t *col4row, int32_t
         a.theta_inv = 1.0 / LAP_THETA;
         a.eps_final = 1e-11;
     }
-    a.stats = (int *)((char *)workspace + reart_align_up(sizeof(double) * (size_t)B * n, 256));   // diagnostics, after the potentials
-    a.pbval_ws = (double *)((char *)a.stats + reart_align_up(sizeof(int) * 4 * (size_t)B, 256));
+    a.stats = w.stats;
+    a.pbval_ws = w.bids;
     const size_t lds = (size_t)n * ((n <= LAP_NLDS ? 3 : 2) * 8 + 5 * 4);
     if (lds > REART_LDS_DEFAULT_CAP &&
         hipFuncSetAttribute((const void *)lap_auction_kernel<LAP_NMAX>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024) != hipSuccess)
@@ -792,10 +834,9 @@ static int lap_launch(const float *cost, int B, int n, int32_t *col4row, int32_t
         if (racers - a.warm_racers > LAP_RACE_COLD) return REART_ERR_INVALID_ARG;
         if (a.warm_racers && (price_in == a.price_out || col_in == col4row || !col_in)) return REART_ERR_INVALID_ARG;
         a.col_in = col_in;
-        if (workspace_bytes < reart_lap_race_workspace_bytes(B, n, racers)) return REART_ERR_INVALID_ARG;
-        char *w = (char *)workspace + reart_lap_workspace_bytes(B, n);
-        a.pbval_ws = (double *)w;                                             // [racers][B][n]
-        a.done = (int *)(w + reart_align_up(sizeof(double) * (size_t)B * n, 256) * (size_t)racers);
+        if (workspace_bytes < lap_ws_layout(LAP_WS_RACE, B, n, racers, workspace, &w)) return REART_ERR_INVALID_ARG;
+        a.pbval_ws = w.racer[0];                                              // [racers][B][n]
+        a.done = w.done;
         if (hipMemsetAsync(a.done, 0, sizeof(int) * (size_t)B, (hipStream_t)stream) != hipSuccess ||
             hipMemsetAsync(certified, 0, sizeof(int32_t) * (size_t)B, (hipStream_t)stream) != hipSuccess)
             return REART_ERR_LAUNCH;
@@ -817,12 +858,9 @@ static_assert((size_t)REART_LAP_LARGE_MAX_N * 18 <= 152 * 1024 - 4096 && REART_L
 // and solved by the caller on the host, like any other whose certificate does not close.
 #define LAP_LARGE_CERT_ROUNDS 256
 
-// potentials [B][n] f64 | diagnostics [B][4] (both where reart_lap_workspace_bytes has them) | rows' bids [B][n] f64 |
-// columns' highest bids [B][n] u64 | per matrix: winning rows, rows' bid columns, unassigned rows [B][3][n] i32
 extern "C" size_t reart_lap_large_workspace_bytes(int B, int n) {
-    if (B < 0 || n < 1 || n > REART_LAP_LARGE_MAX_N) return 0;
-    return reart_align_up(sizeof(double) * (size_t)B * n, 256) + reart_align_up(sizeof(int) * 4 * (size_t)B, 256) +
-           reart_align_up((size_t)B * n * (8 + 8 + 3 * 4), 256);
+    LapWs w;
+    return (B < 0 || n < 1 || n > REART_LAP_LARGE_MAX_N) ? 0 : lap_ws_layout(LAP_WS_LARGE, B, n, 1, nullptr, &w);
 }
 
 extern "C" int reart_lap_auction_large(const float *cost, const float *src, const float *tgt, int B, int n, int32_t *col4row,
@@ -830,14 +868,15 @@ extern "C" int reart_lap_auction_large(const float *cost, const float *src, cons
     if (B < 0 || n < 1 || n > REART_LAP_LARGE_MAX_N || (src == nullptr) != (tgt == nullptr)) return REART_ERR_INVALID_ARG;
     if (B == 0) return REART_OK;
     if (!cost || !col4row || !certified || !price_out) return REART_ERR_INVALID_ARG;
-    if (!workspace || workspace_bytes < reart_lap_large_workspace_bytes(B, n)) return REART_ERR_INVALID_ARG;
+    LapWs w;
+    if (!workspace || workspace_bytes < lap_ws_layout(LAP_WS_LARGE, B, n, 1, workspace, &w)) return REART_ERR_INVALID_ARG;
     LapArgs a = {};
     a.cost = cost; a.B = B; a.n = n; a.col4row = col4row; a.certified = certified; a.price_out = price_out;
     a.src = src; a.tgt = tgt;            // accepted for the callers' sake; the large instance's chains read the matrix
     a.max_rounds_cert = 4 * n < LAP_LARGE_CERT_ROUNDS ? 4 * n : LAP_LARGE_CERT_ROUNDS;
     a.eps0 = LAP_EPS0; a.theta_inv = 1.0 / LAP_THETA; a.eps_final = 1e-11;
-    a.stats = (int *)((char *)workspace + reart_align_up(sizeof(double) * (size_t)B * n, 256));
-    a.pbval_ws = (double *)((char *)a.stats + reart_align_up(sizeof(int) * 4 * (size_t)B, 256));
+    a.stats = w.stats;
+    a.pbval_ws = (double *)w.large;
     const size_t lds = (size_t)n * 18;
     if (lds > REART_LDS_DEFAULT_CAP &&
         hipFuncSetAttribute((const void *)lap_auction_kernel<REART_LAP_LARGE_MAX_N>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1563,21 +1602,8 @@ static_assert((size_t)REART_LAP_LARGE_MAX_N * JV_LARGE_LDS_PER_COL <= 152 * 1024
 // is 54.5 / 35.2 / 42.4 x n steps; the smallest, rounded down.  The timings of that file were taken with this limit.
 #define LAP_LARGE_STEPS_PER_N 35
 extern "C" size_t reart_lap_resolve_large_workspace_bytes(int B, int n) {
-    if (B < 0 || n < 1 || n > REART_LAP_LARGE_MAX_N) return 0;
-    // the layout of reart_lap_workspace_bytes (potentials | diagnostics [B][4] | unused [B][n] f64 | v1, cur [B][n] f64 | j1 [B][n]
-    // i32 | scale [B] f64 | cert_bad [B] i32) and behind it the row potentials [B][n] f64
-    return reart_align_up(sizeof(double) * (size_t)B * n, 256) * 5 + reart_align_up(sizeof(int) * 4 * (size_t)B, 256) +
-           reart_align_up(sizeof(int) * (size_t)B * n, 256) + reart_align_up(sizeof(double) * (size_t)B, 256) +
-           reart_align_up(sizeof(int) * (size_t)B, 256);
-}
-// the state arrays of the many-compute-unit row reduction, behind the race layout
-static size_t jv_mc_extra_bytes(int B, int n) {
-    return reart_align_up(sizeof(double) * (size_t)B * n, 256) + 6 * reart_align_up(sizeof(int) * (size_t)B * n, 256) +
-           reart_align_up(sizeof(int) * 8 * ((size_t)B + 1), 256);      // (+ one block of launch-wide counters behind the problems')
-}
-extern "C" size_t reart_lap_mc_workspace_bytes(int B, int n, int racers) {
-    const size_t r = reart_lap_race_workspace_bytes(B, n, racers);
-    return r ? r + jv_mc_extra_bytes(B, n) : 0;
+    LapWs w;
+    return (B < 0 || n < 1 || n > REART_LAP_LARGE_MAX_N) ? 0 : lap_ws_layout(LAP_WS_RESOLVE_LARGE, B, n, 1, nullptr, &w);
 }
 
 // per_wave: 0 = one row at a time (lap_jv_kernel), 1 = row reduction one chain per wave (lap_mw.hip), 2 = row reduction on
@@ -1595,12 +1621,13 @@ static int jv_launch(JvArgs a, void *workspace, size_t workspace_bytes, void *st
     if (!a.col4row || !a.certified || !a.price_in) return REART_ERR_INVALID_ARG;
     if (per_wave && (!PTS || a.n < JV_SPLIT_NMIN || a.n > reart_internal_jvmw_nmax())) return REART_ERR_UNSUPPORTED;
     if (a.n < JV_SPLIT_NMIN) racers = 1;       // one launch does everything there: nothing worth racing
-    if (!workspace || workspace_bytes < (LARGE ? reart_lap_resolve_large_workspace_bytes(a.B, a.n)
-                                               : racers > 1 ? reart_lap_race_workspace_bytes(a.B, a.n, racers) : reart_lap_workspace_bytes(a.B, a.n)))
+    LapWs w;
+    if (!workspace || workspace_bytes < lap_ws_layout(LARGE ? LAP_WS_RESOLVE_LARGE : racers > 1 ? LAP_WS_RACE : LAP_WS_PLAIN, a.B, a.n, racers,
+                                                      workspace, &w))
         return REART_ERR_INVALID_ARG;
-    if (!a.price_out) a.price_out = (double *)workspace;
+    if (!a.price_out) a.price_out = w.price;
     a.max_rounds_cert = LARGE && 4 * a.n > LAP_LARGE_CERT_ROUNDS ? LAP_LARGE_CERT_ROUNDS : 4 * a.n; a.keep_tol = 1e-12;
-    a.stats = (int *)((char *)workspace + reart_align_up(sizeof(double) * (size_t)a.B * a.n, 256));
+    a.stats = w.stats;
     const size_t lds = LARGE ? (size_t)a.n * JV_LARGE_LDS_PER_COL : (size_t)a.n * (2 * 8 + 4 * 4 + (PTS ? 6 * 4 : 0));
     constexpr int JVBS = LARGE ? JV_LARGE_BS : (PTS ? JV_PTS_BS : 256);
     if constexpr (LARGE) {
@@ -1620,16 +1647,8 @@ static int jv_launch(JvArgs a, void *workspace, size_t workspace_bytes, void *st
         return REART_OK;
     }
     }
-    {
-        const size_t bn = reart_align_up(sizeof(double) * (size_t)a.B * a.n, 256);
-        char *w = (char *)a.stats + reart_align_up(sizeof(int) * 4 * (size_t)a.B, 256) + bn;      // past the auction's row bids
-        a.pre_v1 = (double *)w; w += bn;
-        a.pre_cur = (double *)w; w += bn;
-        a.pre_j1 = (int *)w; w += reart_align_up(sizeof(int) * (size_t)a.B * a.n, 256);
-        a.scale = (double *)w; w += reart_align_up(sizeof(double) * (size_t)a.B, 256);
-        a.cert_bad = (int *)w; w += reart_align_up(sizeof(int) * (size_t)a.B, 256);
-        if (LARGE) a.u_ws = (double *)w;                                                          // [B][n], behind the layout below the limit
-    }
+    a.pre_v1 = w.v1; a.pre_cur = w.cur; a.pre_j1 = w.j1; a.scale = w.scale; a.cert_bad = w.cert_bad;
+    if (LARGE) a.u_ws = w.u_ws;
     int per = PTS ? (256 + a.B - 1) / a.B : (2 * 256 + a.B - 1) / a.B;   // workgroups per matrix: one of 16 waves (points) / two of 4 per compute unit over the batch
     const int pass_waves = (PTS ? JV_PASSP_BS : JV_PASS_BS) / 64;
     const int per_max = (a.n + pass_waves - 1) / pass_waves;
@@ -1649,28 +1668,19 @@ static int jv_launch(JvArgs a, void *workspace, size_t workspace_bytes, void *st
     if (racers > 1) {
         // the racers' common start: copies of the assignment and the potentials (the winner overwrites the originals while
         // a late racer may still be loading), and the flags they meet in -- in the race layout's per-racer arrays
-        const size_t bn = reart_align_up(sizeof(double) * (size_t)a.B * a.n, 256);
-        char *w = (char *)workspace + reart_lap_workspace_bytes(a.B, a.n);
-        double *pc = (double *)w;
-        int *cc = (int *)(w + bn);
-        a.done = (int *)(w + bn * (size_t)racers);
+        a.price_start = w.racer[0]; a.col_start = (int *)w.racer[1]; a.done = w.done;
         // (the form of lap_mw.hip with the row reduction on many compute units hands its racers the state of that launch: they
         // read neither copy, and its set-up launch clears the flags -- three launches less per refresh)
         if (per_wave != 2 &&
-            (hipMemcpyAsync(pc, a.price_in, sizeof(double) * (size_t)a.B * a.n, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess ||
-             hipMemcpyAsync(cc, a.col4row, sizeof(int) * (size_t)a.B * a.n, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess ||
+            (hipMemcpyAsync(w.racer[0], a.price_in, sizeof(double) * (size_t)a.B * a.n, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess ||
+             hipMemcpyAsync(w.racer[1], a.col4row, sizeof(int) * (size_t)a.B * a.n, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess ||
              hipMemsetAsync(a.done, 0, sizeof(int) * (size_t)a.B, (hipStream_t)stream) != hipSuccess))
             return REART_ERR_LAUNCH;
-        a.price_start = pc; a.col_start = cc;
     }
     if (per_wave == 2) {                        // lap_mw.hip: set-up | row reduction on arr_wgs workgroups per problem | searches
-        if (workspace_bytes < reart_lap_mc_workspace_bytes(a.B, a.n, racers)) return REART_ERR_INVALID_ARG;
-        char *w = (char *)workspace + reart_lap_race_workspace_bytes(a.B, a.n, racers);
-        const size_t bi = reart_align_up(sizeof(int) * (size_t)a.B * a.n, 256);
-        a.mc_price = (double *)w; w += reart_align_up(sizeof(double) * (size_t)a.B * a.n, 256);
-        a.mc_owner = (int *)w; w += bi; a.mc_assigned = (int *)w; w += bi; a.mc_list = (int *)w; w += bi; a.mc_next = (int *)w; w += bi;
-        a.mc_tree = (int *)w; w += bi; a.mc_tpar = (int *)w; w += bi;
-        a.mc_cnt = (int *)w;
+        if (workspace_bytes < lap_ws_layout(LAP_WS_MC, a.B, a.n, racers, workspace, &w)) return REART_ERR_INVALID_ARG;
+        a.mc_price = w.mc_price; a.mc_owner = w.mc_owner; a.mc_assigned = w.mc_assigned; a.mc_list = w.mc_list; a.mc_next = w.mc_next;
+        a.mc_tree = w.mc_tree; a.mc_tpar = w.mc_tpar; a.mc_cnt = w.mc_cnt;
         const int rc = reart_internal_jvmc_launch(a, racers, arr_wgs, (hipStream_t)stream);
         if (rc != REART_OK) return rc;
     } else if (per_wave) {                      // lap_mw.hip: the row reduction one chain per wave

@@ -1093,18 +1093,19 @@ __global__ __launch_bounds__(256) void base_bwd_finalize_kernel(Batched<BaseBwdA
 #endif
 }
 
-static size_t base_bwd_ws_layout(int N, int P, int B, int H, size_t *o_rt, size_t *o_part) {
+// offsets, not pointers: the K instances of a launch carve the same layout out of K workspaces
+struct BaseBwdWs { size_t o_rt, o_part; };
+static size_t base_bwd_ws_layout(int N, int P, int B, int H, BaseBwdWs *w) {
     const int nchunk = reart_div_up(N, 16);   // room for the 16-point form (four times the partial rows of the 64-point form)
-    size_t off = 0;
-    *o_rt = off; off += reart_align_up(sizeof(float) * 12 * (size_t)B * P, 256);
-    *o_part = off; off += reart_align_up(sizeof(float) * (size_t)nchunk * n_out(P, H, B), 256);
-    return off;
+    reart_arena ws;
+    w->o_rt = ws.take_bytes(sizeof(float) * 12 * (size_t)B * P);
+    w->o_part = ws.take_bytes(sizeof(float) * (size_t)nchunk * n_out(P, H, B));
+    return ws.off;
 }
 
 extern "C" size_t reart_base_backward_workspace_bytes(int N, int P, int B, int H) {
-    if (N <= 0 || P <= 0 || B <= 0 || H <= 0) return 0;
-    size_t a, b;
-    return base_bwd_ws_layout(N, P, B, H, &a, &b);
+    BaseBwdWs w;
+    return (N <= 0 || P <= 0 || B <= 0 || H <= 0) ? 0 : base_bwd_ws_layout(N, P, B, H, &w);
 }
 
 template <int PP>
@@ -1128,8 +1129,8 @@ int reart_base_backward_launch(const BaseBwdArgs *args, const FinalizeAdam *adam
     for (int k = 0; k < K; ++k) ak[k] = args[k];
     const BaseBwdArgs &a0 = ak[0];
     if (a0.P > 32) return REART_ERR_UNSUPPORTED;
-    size_t o_rt, o_part;
-    const size_t need = base_bwd_ws_layout(a0.N, a0.P, a0.B, a0.H, &o_rt, &o_part);
+    BaseBwdWs w;
+    const size_t need = base_bwd_ws_layout(a0.N, a0.P, a0.B, a0.H, &w);
     if (!workspaces || workspace_bytes < need) return REART_ERR_INVALID_ARG;
     for (int k = 0; k < K; ++k) {
         BaseBwdArgs &a = ak[k];
@@ -1138,9 +1139,9 @@ int reart_base_backward_launch(const BaseBwdArgs *args, const FinalizeAdam *adam
         if (a.N != a0.N || a.P != a0.P || a.B != a0.B || a.H != a0.H || a.cpts != a0.cpts || !workspaces[k]) return REART_ERR_INVALID_ARG;
         if (!a.hT && (!a.W1 || !a.b1)) return REART_ERR_INVALID_ARG;   // no saved hidden layer: it is re-evaluated from W1 | b1
         char *ws = (char *)workspaces[k];
-        a.partial = (float *)(ws + o_part);
+        a.partial = (float *)(ws + w.o_part);
         if (!a.rt_table) {
-            float *table = (float *)(ws + o_rt);
+            float *table = (float *)(ws + w.o_rt);
             hipLaunchKernelGGL(rt_table_kernel, dim3(reart_div_up(a.B * a.P, 256)), dim3(256), 0, st, a.p6d, a.pt,
                                a.B * a.P, table);
             a.rt_table = table;

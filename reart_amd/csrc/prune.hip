@@ -933,12 +933,12 @@ static int warm_plan(int N, int P1, int P2, int K, WarmPlan *p) {
     p->S = 4;                                                             // waves per search workgroup
     while (p->S > 1 && reart_div_up(P2, p->S) < 64) p->S -= 1;
     p->Ppad = (int)reart_align_up((size_t)(P2 > 0 ? P2 : 1), NN_BOX);
-    size_t off = 0;
-    p->o_soa = off; off += reart_align_up(sizeof(float) * 3 * (size_t)N * p->Ppad, 256);
-    p->o_box = off; off += reart_align_up(sizeof(float) * 8 * (size_t)N * (p->Ppad / NN_BOX), 256);
-    p->o_pd = off; off += reart_align_up(sizeof(float) * (size_t)N * P1 * K, 256);
-    p->o_pi = off; off += reart_align_up(sizeof(int) * (size_t)N * P1 * K, 256);
-    p->total = off;
+    reart_arena ws;
+    p->o_soa = ws.take_bytes(sizeof(float) * 3 * (size_t)N * p->Ppad);
+    p->o_box = ws.take_bytes(sizeof(float) * 8 * (size_t)N * (p->Ppad / NN_BOX));
+    p->o_pd = ws.take_bytes(sizeof(float) * (size_t)N * P1 * K);
+    p->o_pi = ws.take_bytes(sizeof(int) * (size_t)N * P1 * K);
+    p->total = ws.off;
     return REART_OK;
 }
 

@@ -64,10 +64,17 @@ __global__ __launch_bounds__(256) void smnn_kernel(const float *__restrict__ dA,
     tgt[a] = j;
 }
 
+// per direction: the two smallest distances [E][N][2] and the nearest index [E][N]
+struct SmnnWs { float *dA, *dB; int *iA, *iB; };
+static size_t smnn_ws_layout(int E, int NA, int NB, void *workspace, SmnnWs *w) {
+    reart_arena ws(workspace);
+    w->dA = ws.take<float>(2 * (size_t)E * NA); w->iA = ws.take<int>((size_t)E * NA);
+    w->dB = ws.take<float>(2 * (size_t)E * NB); w->iB = ws.take<int>((size_t)E * NB);
+    return ws.off;
+}
 extern "C" size_t reart_match_smnn_workspace_bytes(int E, int NA, int NB) {
-    if (E <= 0 || NA <= 0 || NB <= 0) return 0;
-    return reart_align_up(sizeof(float) * 2 * (size_t)E * NA, 256) + reart_align_up(sizeof(int) * (size_t)E * NA, 256) +
-           reart_align_up(sizeof(float) * 2 * (size_t)E * NB, 256) + reart_align_up(sizeof(int) * (size_t)E * NB, 256);
+    SmnnWs w;
+    return (E <= 0 || NA <= 0 || NB <= 0) ? 0 : smnn_ws_layout(E, NA, NB, nullptr, &w);
 }
 
 extern "C" int reart_match_smnn(const float *desc1, const float *desc2, int E, int N1, int N2, int D, float th,
@@ -78,16 +85,12 @@ extern "C" int reart_match_smnn(const float *desc1, const float *desc2, int E, i
     if (D != SM_D) return REART_ERR_UNSUPPORTED;
     if (E == 0) return REART_OK;
     if (!desc1 || !desc2 || !keep || !tgt || !workspace) return REART_ERR_INVALID_ARG;
-    if (workspace_bytes < reart_match_smnn_workspace_bytes(E, N1, N2)) return REART_ERR_INVALID_ARG;
-    char *ws = (char *)workspace;
-    float *dA = (float *)ws; ws += reart_align_up(sizeof(float) * 2 * (size_t)E * N1, 256);
-    int *iA = (int *)ws; ws += reart_align_up(sizeof(int) * (size_t)E * N1, 256);
-    float *dB = (float *)ws; ws += reart_align_up(sizeof(float) * 2 * (size_t)E * N2, 256);
-    int *iB = (int *)ws;
+    SmnnWs w;
+    if (workspace_bytes < smnn_ws_layout(E, N1, N2, workspace, &w)) return REART_ERR_INVALID_ARG;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(top2_kernel, dim3(reart_div_up(N1, 64), E), dim3(64), 0, st, desc1, desc2, N1, N2, dA, iA);
-    hipLaunchKernelGGL(top2_kernel, dim3(reart_div_up(N2, 64), E), dim3(64), 0, st, desc2, desc1, N2, N1, dB, iB);
-    hipLaunchKernelGGL(smnn_kernel, dim3(reart_div_up(N1, 256), E), dim3(256), 0, st, dA, iA, dB, iB, N1, N2, th, keep, tgt);
+    hipLaunchKernelGGL(top2_kernel, dim3(reart_div_up(N1, 64), E), dim3(64), 0, st, desc1, desc2, N1, N2, w.dA, w.iA);
+    hipLaunchKernelGGL(top2_kernel, dim3(reart_div_up(N2, 64), E), dim3(64), 0, st, desc2, desc1, N2, N1, w.dB, w.iB);
+    hipLaunchKernelGGL(smnn_kernel, dim3(reart_div_up(N1, 256), E), dim3(256), 0, st, w.dA, w.iA, w.dB, w.iB, N1, N2, th, keep, tgt);
     REART_CHECK_LAUNCH();
     return REART_OK;
 }

@@ -42,12 +42,6 @@ struct StepPlan {
     size_t bwd_bytes, total;
 };
 
-static size_t take(size_t &off, size_t bytes) {
-    const size_t o = off;
-    off += reart_align_up(bytes, 256);
-    return o;
-}
-
 #define FLOW_BS 256    // stand-alone flow_blend_kernel; inside post_kernel the blend uses POST_FBS of the CG_BS threads
 #define CG_BS 1024
 // points (= live threads) of a flow-blend workgroup inside post_kernel.  Same-box A/B of the headline (tools/ab_headline.sh),
@@ -79,52 +73,52 @@ static int step_plan(const reart_relax_config *c, StepPlan *p) {
     }
     p->nchunk = reart_div_up(c->N, 64);
     p->nparams = 3 * c->H + c->H + c->P * c->H + 6 * c->B * c->P + 3 * c->B * c->P;
-    size_t off = 0;
+    reart_arena ws;
     const size_t BN = (size_t)c->B * c->N;
-    p->o_ysoa = take(off, sizeof(float) * 3 * c->B * (size_t)p->Npad);
-    p->o_xsoa = take(off, sizeof(float) * 3 * c->B * (size_t)p->Npad);
-    p->o_rsoa = take(off, sizeof(float) * 3 * c->B * (size_t)p->Mpad);
-    p->o_rlen = take(off, sizeof(int) * c->B);
-    p->o_qmap = take(off, sizeof(int) * (c->B + 1));
-    p->o_pd0 = take(off, sizeof(float) * p->S1 * BN);
-    p->o_pi0 = take(off, sizeof(int) * p->S1 * BN);
-    p->o_pd1 = take(off, sizeof(float) * p->S1 * BN);
-    p->o_pi1 = take(off, sizeof(int) * p->S1 * BN);
-    p->o_pd3 = take(off, c->use_flow ? sizeof(float) * p->S3 * BN * 3 : 0);
-    p->o_pi3 = take(off, c->use_flow ? sizeof(int) * p->S3 * BN * 3 : 0);
-    p->o_yT = take(off, sizeof(float) * (size_t)c->P * c->N);
+    p->o_ysoa = ws.take_bytes(sizeof(float) * 3 * c->B * (size_t)p->Npad);
+    p->o_xsoa = ws.take_bytes(sizeof(float) * 3 * c->B * (size_t)p->Npad);
+    p->o_rsoa = ws.take_bytes(sizeof(float) * 3 * c->B * (size_t)p->Mpad);
+    p->o_rlen = ws.take_bytes(sizeof(int) * c->B);
+    p->o_qmap = ws.take_bytes(sizeof(int) * (c->B + 1));
+    p->o_pd0 = ws.take_bytes(sizeof(float) * p->S1 * BN);
+    p->o_pi0 = ws.take_bytes(sizeof(int) * p->S1 * BN);
+    p->o_pd1 = ws.take_bytes(sizeof(float) * p->S1 * BN);
+    p->o_pi1 = ws.take_bytes(sizeof(int) * p->S1 * BN);
+    p->o_pd3 = ws.take_bytes(c->use_flow ? sizeof(float) * p->S3 * BN * 3 : 0);
+    p->o_pi3 = ws.take_bytes(c->use_flow ? sizeof(int) * p->S3 * BN * 3 : 0);
+    p->o_yT = ws.take_bytes(sizeof(float) * (size_t)c->P * c->N);
     // hidden activations [H][N]: only for the long kernels.  The in-LDS backward re-evaluates them from the points and W1 | b1
     // (hidden_unit, model_dev.h), so the forward neither writes nor the backward reads 4 H N bytes per iteration
     p->keep_hT = (c->tune_long > 0 || reart_base_path(c->P, c->B, c->H, 0) != 0 || reart_base_path(c->P, c->B, c->H, 1) != 0) ? 1 : 0;
-    p->o_hT = take(off, p->keep_hT ? sizeof(float) * (size_t)c->H * c->N : 0);
-    p->o_hard = take(off, sizeof(int) * (size_t)c->N);
-    p->o_rt = take(off, sizeof(float) * 12 * (size_t)c->B * c->P);
-    p->o_G = take(off, sizeof(float) * 3 * BN);
-    p->o_gpf = take(off, sizeof(float) * 3 * BN);
-    p->o_fx = take(off, sizeof(double));
-    p->o_floss = take(off, sizeof(double) * (size_t)c->B * reart_div_up(c->N, CG_RANGE));
-    p->o_fpart = take(off, sizeof(double) * (size_t)c->B * reart_div_up(c->N, FLOW_BS));
-    p->o_grads = take(off, sizeof(float) * p->nparams);
+    p->o_hT = ws.take_bytes(p->keep_hT ? sizeof(float) * (size_t)c->H * c->N : 0);
+    p->o_hard = ws.take_bytes(sizeof(int) * (size_t)c->N);
+    p->o_rt = ws.take_bytes(sizeof(float) * 12 * (size_t)c->B * c->P);
+    p->o_G = ws.take_bytes(sizeof(float) * 3 * BN);
+    p->o_gpf = ws.take_bytes(sizeof(float) * 3 * BN);
+    p->o_fx = ws.take_bytes(sizeof(double));
+    p->o_floss = ws.take_bytes(sizeof(double) * (size_t)c->B * reart_div_up(c->N, CG_RANGE));
+    p->o_fpart = ws.take_bytes(sizeof(double) * (size_t)c->B * reart_div_up(c->N, FLOW_BS));
+    p->o_grads = ws.take_bytes(sizeof(float) * p->nparams);
     p->bwd_bytes = reart_base_backward_workspace_bytes(c->N, c->P, c->B, c->H);
-    p->o_bwd = take(off, p->bwd_bytes);
-    p->o_bc = take(off, 8 * sizeof(float));
-    p->o_ticket = take(off, 4 * sizeof(unsigned int));   // [2..3] persistent-search counters
-    p->o_boxY = take(off, sizeof(float) * 8 * (size_t)c->B * (p->Npad / NN_BOX));
-    p->o_boxX = take(off, sizeof(float) * 8 * (size_t)c->B * (p->Npad / NN_BOX));
-    p->o_boxR = take(off, sizeof(float) * 8 * (size_t)c->B * (p->Mpad / NN_BOX + 1));
-    p->o_seed3 = take(off, (p->pruned && c->use_flow) ? sizeof(int) * BN * 3 : 0);
+    p->o_bwd = ws.take_bytes(p->bwd_bytes);
+    p->o_bc = ws.take_bytes(8 * sizeof(float));
+    p->o_ticket = ws.take_bytes(4 * sizeof(unsigned int));   // [2..3] persistent-search counters
+    p->o_boxY = ws.take_bytes(sizeof(float) * 8 * (size_t)c->B * (p->Npad / NN_BOX));
+    p->o_boxX = ws.take_bytes(sizeof(float) * 8 * (size_t)c->B * (p->Npad / NN_BOX));
+    p->o_boxR = ws.take_bytes(sizeof(float) * 8 * (size_t)c->B * (p->Mpad / NN_BOX + 1));
+    p->o_seed3 = ws.take_bytes((p->pruned && c->use_flow) ? sizeof(int) * BN * 3 : 0);
     const size_t G = (size_t)c->B * reart_div_up(c->N, NN_BS);
-    p->o_border = take(off, sizeof(int) * 3 * G);
-    p->o_cost = take(off, sizeof(unsigned int) * 3 * G);
+    p->o_border = ws.take_bytes(sizeof(int) * 3 * G);
+    p->o_cost = ws.take_bytes(sizeof(unsigned int) * 3 * G);
     const size_t nprof = (c->profile && p->pruned) ? (size_t)reart_search_grid(2, 1, (int)G) : 0;
-    p->o_prof = take(off, sizeof(unsigned long long) * 2 * nprof);
-    p->o_prof_pairs = take(off, sizeof(unsigned int) * nprof);
-    p->o_prof_acc = take(off, sizeof(unsigned long long) * 4);
+    p->o_prof = ws.take_bytes(sizeof(unsigned long long) * 2 * nprof);
+    p->o_prof_pairs = ws.take_bytes(sizeof(unsigned int) * nprof);
+    p->o_prof_acc = ws.take_bytes(sizeof(unsigned long long) * 4);
     p->gstrideY = (int)reart_align_up((size_t)c->N, 64);
     p->gstrideR = (int)reart_align_up((size_t)(c->M_max > 0 ? c->M_max : 1), 64);
-    p->o_gridY = take(off, c->use_grid ? reart_grid_bytes(c->B, p->gstrideY) : 0);
-    p->o_gridR = take(off, (c->use_grid && c->use_flow) ? reart_grid_bytes(c->B, p->gstrideR) : 0);
-    p->total = off;
+    p->o_gridY = ws.take_bytes(c->use_grid ? reart_grid_bytes(c->B, p->gstrideY) : 0);
+    p->o_gridR = ws.take_bytes((c->use_grid && c->use_flow) ? reart_grid_bytes(c->B, p->gstrideR) : 0);
+    p->total = ws.off;
     return REART_OK;
 }
 

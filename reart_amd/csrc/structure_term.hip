@@ -28,8 +28,14 @@
 static bool st_shape_ok(int T, int P, int E) {
     return T >= 1 && T <= REART_MAX_POSE_LEN && P >= 1 && P <= ST_MAX_P && E >= 0 && E <= ST_MAX_E;
 }
-static size_t st_cost_bytes(int E) { return reart_align_up(sizeof(double) * (size_t)(E > 0 ? E : 1), 256); }
-static size_t st_ends_bytes(int T, int E) { return reart_align_up(sizeof(float) * 24 * (size_t)T * (size_t)E, 256); }
+// the edges' costs in double [E], then (ends: a gradient through the pairs is wanted) the two ends' rows per (frame, edge) [T][E][24]
+struct StWs { double *cost_d; float *ends; };
+static size_t st_ws_layout(int T, int E, bool ends, void *workspace, StWs *w) {
+    reart_arena ws(workspace);
+    w->cost_d = ws.take<double>(E > 0 ? E : 1);
+    w->ends = ends ? ws.take<float>(24 * (size_t)T * (size_t)E) : nullptr;
+    return ws.off;
+}
 
 // frob_cost(M, G) with its derivative: err = M inv(G) - I (rows 0..2), cost = |err|^2, dM = scale * err * inv(G)^T.
 __device__ __forceinline__ float frob_cost_grad(const float *M, const float *G, float scale, float *dM) {
@@ -300,8 +306,8 @@ static void st_launch_edges(const StArgs &a, hipStream_t st) {
 }
 
 extern "C" size_t reart_structure_term_workspace_bytes(int T, int P, int E) {
-    if (!st_shape_ok(T, P, E)) return 0;
-    return st_cost_bytes(E) + st_ends_bytes(T, E);
+    StWs w;
+    return st_shape_ok(T, P, E) ? st_ws_layout(T, E, true, nullptr, &w) : 0;
 }
 
 extern "C" int reart_structure_term(const float *trans, int T, int P, const int32_t *pairs, int E, float weight, float *loss,
@@ -309,28 +315,24 @@ extern "C" int reart_structure_term(const float *trans, int T, int P, const int3
                                     void *stream) {
     if (!trans || !loss || T <= 0 || P <= 0 || E < 0) return REART_ERR_INVALID_ARG;
     if (!st_shape_ok(T, pairs ? P : 1, E)) return REART_ERR_UNSUPPORTED;
-    const bool ends = pairs && grad && E > 0;
-    const size_t need = st_cost_bytes(E) + (ends ? st_ends_bytes(T, E) : 0);
-    if (!workspace || workspace_bytes < need) return REART_ERR_INVALID_ARG;
+    StWs w;
+    if (!workspace || workspace_bytes < st_ws_layout(T, E, pairs && grad && E > 0, workspace, &w)) return REART_ERR_INVALID_ARG;
     hipStream_t st = (hipStream_t)stream;
-    double *cost_d = (double *)workspace;
-    float *ws_ends = ends ? (float *)((char *)workspace + st_cost_bytes(E)) : nullptr;
     if (E > 0) {
-        StArgs a{trans, pairs, T, P, E, weight, edge_cost, prismatic, cost_d, ws_ends, pairs ? nullptr : grad};
+        StArgs a{trans, pairs, T, P, E, weight, edge_cost, prismatic, w.cost_d, w.ends, pairs ? nullptr : grad};
         st_launch_edges(a, st);
     }
     if (pairs && grad)    // E == 0: every list is empty, the gradient is written as zeros
-        hipLaunchKernelGGL(st_gather_kernel, dim3(P, reart_div_up(T, ST_GT)), dim3(256), 0, st, ws_ends, pairs, T, P, E, grad, cost_d,
+        hipLaunchKernelGGL(st_gather_kernel, dim3(P, reart_div_up(T, ST_GT)), dim3(256), 0, st, w.ends, pairs, T, P, E, grad, w.cost_d,
                            weight, loss);
     else
-        hipLaunchKernelGGL(st_loss_kernel, dim3(1), dim3(256), 0, st, cost_d, E, weight, loss);
+        hipLaunchKernelGGL(st_loss_kernel, dim3(1), dim3(256), 0, st, w.cost_d, E, weight, loss);
     REART_CHECK_LAUNCH();
     return REART_OK;
 }
 
-extern "C" size_t reart_rel_trans_backward_workspace_bytes(int T, int P, int E) {
-    if (!st_shape_ok(T, P, E)) return 0;
-    return st_ends_bytes(T, E > 0 ? E : 1);
+extern "C" size_t reart_rel_trans_backward_workspace_bytes(int T, int P, int E) {      // one block: the two ends' rows
+    return st_shape_ok(T, P, E) ? reart_align_up(sizeof(float) * 24 * (size_t)T * (size_t)(E > 0 ? E : 1), 256) : 0;
 }
 
 extern "C" int reart_rel_trans_backward(const float *trans, int T, int P, const int32_t *pairs, int E, const float *grad_rel,

@@ -239,7 +239,7 @@ def _host_lists(col, flags, state, **costs):
 def stats_words(B, n, ws=None):
     """The solvers' statistics, [B][4] int32 words behind the potentials of a workspace: their byte offset, or (``ws`` given) a
     host copy of them."""
-    off = ((8 * B * n + 255) // 256) * 256
+    off = _lib.lib().reart_lap_stats_offset(B, n)
     return off if ws is None else ws[off:off + 16 * B].view(torch.int32).reshape(B, 4).cpu().numpy().copy()
 
 

@@ -22,6 +22,9 @@ class _FakeLib:
     def reart_lap_race_workspace_bytes(self, B, n, racers):
         return self.reart_lap_workspace_bytes(B, n) * racers
 
+    def reart_lap_stats_offset(self, B, n):
+        return ((8 * B * n + 255) // 256) * 256
+
     def _solve(self, name, col_ptr, cert_ptr):
         import ctypes
 
