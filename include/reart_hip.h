@@ -755,6 +755,39 @@ int reart_chamfer_points_backward(const float *x, const float *y, int N, int P1,
                                   const int64_t *i_yx, const float *d_xy, const float *d_yx, const float *g_xy,
                                   const float *g_yx, float *grad_x, float *grad_y, int32_t *fx_bits, void *stream);
 
+/* The three entries above for batches whose clouds differ in length, padded to [N,P1,3] and [N,P2,3]: the arguments of the dense
+ * sibling, then len_x, len_y [N] i32 (device; either may be NULL = every element has P1, respectively P2, points; both NULL is
+ * the dense entry, which is implemented as exactly that call).  Per batch element n with lx = len_x[n], ly = len_y[n] this is
+ * reart_knn_points_idx(x, y, lengths1, lengths2, K = 1) in both directions:
+ *   rows i < lx of d_xy / i_xy: distance and lowest index of the nearest of y's first ly points, bit for bit; rows i >= lx,
+ *       and every row when ly = 0: distance 0, index 0, next seed -1.  Likewise for d_yx / i_yx;
+ *   loss: the live rows' distances of both directions, added in double in the fixed order, rounded once;
+ *   gradients: the dense formula over live points only; rows of padding points are exactly 0, grad is written completely;
+ *       an upstream (g_xy, g_yx) at a padding row is never read;
+ *   fx_bits: from max(lx, ly) and the live points alone, so element n equals a dense call on the two trimmed clouds in every
+ *       output bit (distances, indices, gradients, fx_bits).
+ * The contents of padding rows of x and y are never part of a result (zeros, NaN, +-INF, anything).  A length outside [0, P]
+ * reads as clamped.  A seed that names a padding target is unusable like any other garbage seed.  Limits as the dense entries.
+ * Workspace of reart_chamfer_loss_ragged and reart_chamfer_points_ragged with a length given: reart_chamfer_ragged_bytes(N, P1,
+ * P2) -- the dense layout at the dense offsets (y's image serves both), then a staged query image of each cloud, in which the
+ * padding rows repeat the element's last live point, and the clamped lengths (the search kernels take no query count: padding
+ * lanes cost one coherent query and their records are ignored).  During the call the padding rows of a searched direction's
+ * seed array hold a copy of the last live row's seed.  y_unchanged != 0 also asserts that len_y is unchanged.  One more
+ * launch than the dense sibling (the staging); the backward has none and no workspace. */
+size_t reart_chamfer_ragged_bytes(int N, int P1, int P2);
+int reart_chamfer_loss_ragged(const float *x, const float *y, int N, int P1, int P2, int32_t *seed_xy, int32_t *seed_yx,
+                              int y_unchanged, float *d_xy, int64_t *i_xy, float *d_yx, int64_t *i_yx, float *loss,
+                              float *grad_x, float *grad_y, int32_t *fx_bits, void *workspace, size_t workspace_bytes,
+                              void *stream, const int32_t *len_x, const int32_t *len_y);
+int reart_chamfer_points_ragged(const float *x, const float *y, int N, int P1, int P2, int directions, int32_t *seed_xy,
+                                int32_t *seed_yx, int y_unchanged, float *d_xy, int64_t *i_xy, float *d_yx, int64_t *i_yx,
+                                void *workspace, size_t workspace_bytes, void *stream, const int32_t *len_x,
+                                const int32_t *len_y);
+int reart_chamfer_points_backward_ragged(const float *x, const float *y, int N, int P1, int P2, const int64_t *i_xy,
+                                         const int64_t *i_yx, const float *d_xy, const float *d_yx, const float *g_xy,
+                                         const float *g_yx, float *grad_x, float *grad_y, int32_t *fx_bits, void *stream,
+                                         const int32_t *len_x, const int32_t *len_y);
+
 /* One iteration's flow term (run_robot.py:194-209: blend_anchor_motion of every frame pair, flow_loss, and the gradient that
  * autograd carries through the cat and the subtraction) as ONE call over reference sets prepared once, warm-started from its own
  * previous call (csrc/flow_term.hip).  K = 3 only.

@@ -110,6 +110,10 @@ PROTOTYPES = {
     "reart_chamfer_loss": (c_int, [P, P, c_int, c_int, c_int, P, P, c_int, P, P, P, P, P, P, P, P, P, c_size_t, P]),
     "reart_chamfer_points": (c_int, [P, P, c_int, c_int, c_int, c_int, P, P, c_int, P, P, P, P, P, c_size_t, P]),
     "reart_chamfer_points_backward": (c_int, [P, P, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P]),
+    "reart_chamfer_ragged_bytes": (c_size_t, [c_int] * 3),
+    "reart_chamfer_loss_ragged": (c_int, [P, P, c_int, c_int, c_int, P, P, c_int, P, P, P, P, P, P, P, P, P, c_size_t, P, P, P]),
+    "reart_chamfer_points_ragged": (c_int, [P, P, c_int, c_int, c_int, c_int, P, P, c_int, P, P, P, P, P, c_size_t, P, P, P]),
+    "reart_chamfer_points_backward_ragged": (c_int, [P, P, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P, P, P]),
     "reart_flow_term_workspace_bytes": (c_size_t, [c_int] * 3),
     "reart_flow_term_prepare": (c_int, [P, P, P, c_int, c_int, P, c_size_t, P]),
     "reart_flow_term": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, P, P, P, P, P, P, P, c_int, P, c_size_t, P]),

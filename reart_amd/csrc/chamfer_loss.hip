@@ -12,6 +12,9 @@
 // not: the step's merges slice partials over a 1024-target range and captures its own d1; here P1 != P2, there is a
 // gradient for y, a fixed-point scale per batch element taken from the boxes the prep has just computed, and the loss is
 // reduced inside the same launch by the last workgroup to finish.
+// Clouds of differing lengths in one padded batch (the _ragged entries; the dense ones are these with both lengths NULL): the
+// targets' lengths go to the prep and the search (SoaJob.len, KnnJob.tlen), the queries are staged once per call
+// (chamfer_stage_kernel), and the consumers treat rows beyond a length as padding (cl_len).
 #include "common.h"
 #include "internal.h"
 #include "consumer_dev.h"
@@ -24,8 +27,11 @@
 struct ChamferLossPlan {
     int S, Ppad1, Ppad2, nqg, nr1, nr2, nparts;
     size_t o_xsoa, o_ysoa, o_xbox, o_ybox, o_pd0, o_pi0, o_pd1, o_pi1, o_part, o_ticket, total;
+    size_t o_xq, o_yq, o_len64, o_len32;     // ragged entries only, behind the dense layout
 };
-static int chamfer_loss_plan(int N, int P1, int P2, ChamferLossPlan *p) {
+// ragged: the layout of the _ragged entries -- the dense one (same offsets: an image of y serves both) followed by the staged
+// query images and the clamped lengths
+static int chamfer_loss_plan(int N, int P1, int P2, ChamferLossPlan *p, bool ragged = false) {
     if (N < 0 || N > 65535 || P1 < 0 || P2 < 0) return REART_ERR_INVALID_ARG;   // N is a grid dimension
     // record and gradient offsets are 64-bit, the per-batch products below stay in int
     if ((long long)N * ((long long)(P1 > P2 ? P1 : P2) + 2 * CL_BS) >= (1ll << 30)) return REART_ERR_INVALID_ARG;
@@ -49,12 +55,27 @@ static int chamfer_loss_plan(int N, int P1, int P2, ChamferLossPlan *p) {
     p->o_pi1 = ws.take_bytes(sizeof(int) * (size_t)N * P2);
     p->o_part = ws.take_bytes(sizeof(double) * (size_t)(p->nparts > 0 ? p->nparts : 1));
     p->o_ticket = ws.take_bytes(sizeof(unsigned int));
+    p->o_xq = p->o_yq = p->o_len64 = p->o_len32 = 0;
+    if (ragged) {
+        p->o_xq = ws.take_bytes(sizeof(float) * 3 * (size_t)N * P1);
+        p->o_yq = ws.take_bytes(sizeof(float) * 3 * (size_t)N * P2);
+        p->o_len64 = ws.take_bytes(sizeof(int64_t) * 2 * (size_t)N);
+        p->o_len32 = ws.take_bytes(sizeof(int) * 2 * (size_t)N);
+    }
     p->total = ws.off;
     return REART_OK;
 }
 
 // ---- what the two gradient kernels below (chamfer_loss_kernel, chamfer_points_bwd_kernel) share.  A workgroup (r, n) of
 // cloud d owns the points r0 = r * CL_BS .. of cloud d ("own", Pw points) of batch element n; the other cloud has Po points.
+
+// Ragged batches: live points of cloud d of batch element n = len[d][n] clamped into [0, P] (uniform; NULL: all P).  Every
+// kernel below takes it as "Lw" (own cloud) and "Lo" (other cloud): rows beyond it are padding, which is never read as a
+// coordinate, an index or an upstream, and is written as distance 0, index 0, seed -1, gradient 0.
+__device__ __forceinline__ int cl_len(const int *len, int n, int P) {
+    const int l = len ? len[n] : P;
+    return l < 0 ? 0 : (l > P ? P : l);
+}
 
 // largest of the threads' values over the workgroup (fmaxf drops NaN); contains one barrier
 __device__ __forceinline__ float cl_block_max(float mx, float *s_mx) {
@@ -112,6 +133,7 @@ struct ChamferLossArgs {
     const float *pd[2];         // search records of cloud d's points against the other cloud [N,P[d]]
     const int *pi[2];
     int P[2], nbox[2], nr[2];   // points, boxes and consumer ranges per batch element
+    const int *len[2];          // nullable [N]: live points of cloud d (cl_len)
     float *od[2];               // nullable outputs [N,P[d]]
     int64_t *oi[2];
     int *seed[2];               // [N,P[d]] next seeds
@@ -151,29 +173,31 @@ __global__ __launch_bounds__(CL_BS) void chamfer_loss_kernel(ChamferLossArgs a) 
             if ((e & 7) < 6 && v < INFINITY) mx = fmaxf(mx, v);
         }
     }
-    // ---- 2. own record
+    // ---- 2. own record (a padding row reads the last live row's, and uses none of it)
+    const int Lw = cl_len(a.len[d], n, Pw), Lo = cl_len(a.len[o], n, Po);      // uniform
     const int i = r * CL_BS + tid;
-    const bool live = i < Pw;
-    const int ic = live ? i : Pw - 1;
+    const bool live = i < Lw;
+    const int ic = live ? i : (Lw > 0 ? Lw - 1 : 0);
     const size_t ow = (size_t)n * Pw + ic;
     float d0 = a.pd[d][ow];
     int j0 = a.pi[d][ow];
-    const bool ok0 = (unsigned)j0 < (unsigned)Po;
+    const bool ok0 = live && (unsigned)j0 < (unsigned)Lo;
     d0 = ok0 ? d0 : 0.0f;
     const int j0c = ok0 ? j0 : 0;
     float xo[3], yn[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) { xo[k] = own[3 * (size_t)ic + k]; yn[k] = oth[3 * (size_t)j0c + k]; }
-    // sums of at most Pmax differences, each of magnitude at most 2 mx
-    const int sbits = reart_fx_bits(Pw > Po ? Pw : Po, cl_block_max(mx, s_mx));
+    // sums of at most max(Lw, Lo) differences, each of magnitude at most 2 mx
+    const int sbits = reart_fx_bits(Lw > Lo ? Lw : Lo, cl_block_max(mx, s_mx));
     if (blockIdx.x == 0 && tid == 0) a.bits[n] = sbits;
-    if (live) {
-        if (a.od[d]) a.od[d][ow] = d0;
-        if (a.oi[d]) a.oi[d][ow] = (int64_t)j0c;
-        a.seed[d][ow] = ok0 ? j0 : -1;
+    const size_t os = (size_t)n * Pw + i;        // the row this thread writes (live or padding)
+    if (i < Pw) {
+        if (a.od[d]) a.od[d][os] = d0;
+        if (a.oi[d]) a.oi[d][os] = (int64_t)j0c;
+        a.seed[d][os] = ok0 ? j0 : -1;
     }
-    // ---- 3. the other cloud's records
-    if (want) cl_scatter_walk(own, oth, a.pi[o] + (size_t)n * Po, nullptr, Pw, Po, r * CL_BS, sbits, s_acc);
+    // ---- 3. the other cloud's live records (none can name a target of a range beyond the live points)
+    if (want && r * CL_BS < Lw) cl_scatter_walk(own, oth, a.pi[o] + (size_t)n * Po, nullptr, Lw, Lo, r * CL_BS, sbits, s_acc);
     __syncthreads();
     // ---- 4. gradient and loss
     double term = 0.0;
@@ -183,8 +207,11 @@ __global__ __launch_bounds__(CL_BS) void chamfer_loss_kernel(ChamferLossArgs a) 
             float first[3];
 #pragma unroll
             for (int k = 0; k < 3; ++k) first[k] = ok0 ? 2.0f * (xo[k] - yn[k]) : 0.0f;
-            cl_grad_store(a.grad[d] + 3 * ow, first, s_acc, sbits);
+            cl_grad_store(a.grad[d] + 3 * os, first, s_acc, sbits);
         }
+    } else if (i < Pw && want) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) a.grad[d][3 * os + k] = 0.0f;
     }
     term = reart_block_sum_d<CL_BS>(term, s_red);
     const int nbx = a.nr[0] + a.nr[1], total = nbx * a.N;
@@ -202,18 +229,70 @@ __global__ __launch_bounds__(CL_BS) void chamfer_loss_kernel(ChamferLossArgs a) 
     }
 }
 
+// ---- ragged batches: what the _ragged entries put in front of the dense prep.  The search kernels have no per-element query
+// count, so they get a STAGED query image of each searched direction's query cloud in which the padding rows repeat the
+// element's last live point (zeros where it has none) and, in the caller's seed array, that point's seed: padding lanes are
+// one coherent, bounded query that widens no row's bounds, and nothing a caller left in its padding rows reaches the search.
+// Their records are ignored by the consumers, which write the padding rows' seeds back to -1.  The clamped lengths go to
+// the workspace in the two widths the prep (SoaJob.len, int64) and the search (KnnJob.tlen, int) read.
+struct ChamferStageArgs {
+    const float *c[2];          // the clouds [N,P[d],3]
+    const int *len[2];          // nullable [N]
+    float *q[2];                // staged image [N,P[d],3]; NULL: cloud d is no query cloud of this call
+    int *seed[2];               // [N,P[d]] with q[d]
+    int64_t *len64;             // [2][N]
+    int *len32;                 // [2][N]
+    int P[2], N;
+};
+__global__ __launch_bounds__(CL_BS) void chamfer_stage_kernel(ChamferStageArgs a) {
+    const int n = blockIdx.y, d = blockIdx.z;
+    const int i = blockIdx.x * CL_BS + threadIdx.x;
+    const int P = a.P[d], l = cl_len(a.len[d], n, P);
+    if (i == 0) { a.len64[(size_t)d * a.N + n] = (int64_t)l; a.len32[(size_t)d * a.N + n] = l; }
+    if (i >= P || !a.q[d]) return;
+    const size_t row = (size_t)n * P;
+    float v[3] = {0.f, 0.f, 0.f};
+    if (l > 0) {
+        const float *s = a.c[d] + 3 * (row + (i < l ? i : l - 1));
+        v[0] = s[0]; v[1] = s[1]; v[2] = s[2];
+    }
+    float *q = a.q[d] + 3 * (row + i);
+    q[0] = v[0]; q[1] = v[1]; q[2] = v[2];
+    // rows >= l are written here and read by nobody in this launch; row l - 1 is only read
+    if (i >= l) a.seed[d][row + i] = l > 0 ? a.seed[d][row + l - 1] : -1;
+}
+// queries: bit d set = cloud d is the query cloud of a searched direction
+static int chamfer_stage_launch(const float *x, const float *y, const int32_t *len_x, const int32_t *len_y, int N, int P1, int P2,
+                                int queries, int32_t *seed_xy, int32_t *seed_yx, char *ws, const ChamferLossPlan &p, hipStream_t st) {
+    ChamferStageArgs a = {};
+    a.c[0] = x; a.c[1] = y; a.len[0] = len_x; a.len[1] = len_y; a.P[0] = P1; a.P[1] = P2; a.N = N;
+    a.q[0] = (queries & 1) ? (float *)(ws + p.o_xq) : nullptr; a.q[1] = (queries & 2) ? (float *)(ws + p.o_yq) : nullptr;
+    a.seed[0] = seed_xy; a.seed[1] = seed_yx;
+    a.len64 = (int64_t *)(ws + p.o_len64); a.len32 = (int *)(ws + p.o_len32);
+    hipLaunchKernelGGL(chamfer_stage_kernel, dim3(reart_div_up(P1 > P2 ? P1 : P2, CL_BS), N, 2), dim3(CL_BS), 0, st, a);
+    REART_CHECK_LAUNCH();
+    return REART_OK;
+}
+
 extern "C" size_t reart_chamfer_loss_workspace_bytes(int N, int P1, int P2) {
     ChamferLossPlan p;
     if (N < 1 || P1 < 1 || P2 < 1) return 0;
     return chamfer_loss_plan(N, P1, P2, &p) == REART_OK ? p.total : 0;
 }
-
-extern "C" int reart_chamfer_loss(const float *x, const float *y, int N, int P1, int P2, int32_t *seed_xy, int32_t *seed_yx,
-                                  int y_unchanged, float *d_xy, int64_t *i_xy, float *d_yx, int64_t *i_yx, float *loss,
-                                  float *grad_x, float *grad_y, int32_t *fx_bits, void *workspace, size_t workspace_bytes,
-                                  void *stream) {
+extern "C" size_t reart_chamfer_ragged_bytes(int N, int P1, int P2) {
     ChamferLossPlan p;
-    int rc = chamfer_loss_plan(N, P1, P2, &p);
+    if (N < 1 || P1 < 1 || P2 < 1) return 0;
+    return chamfer_loss_plan(N, P1, P2, &p, true) == REART_OK ? p.total : 0;
+}
+
+// reart_chamfer_loss is this with both lengths NULL: no staging launch, the callers' clouds as queries, the dense layout
+extern "C" int reart_chamfer_loss_ragged(const float *x, const float *y, int N, int P1, int P2, int32_t *seed_xy, int32_t *seed_yx,
+                                         int y_unchanged, float *d_xy, int64_t *i_xy, float *d_yx, int64_t *i_yx, float *loss,
+                                         float *grad_x, float *grad_y, int32_t *fx_bits, void *workspace, size_t workspace_bytes,
+                                         void *stream, const int32_t *len_x, const int32_t *len_y) {
+    const bool ragged = len_x || len_y;
+    ChamferLossPlan p;
+    int rc = chamfer_loss_plan(N, P1, P2, &p, ragged);
     if (rc != REART_OK) return rc;
     if (N == 0 || P1 == 0 || P2 == 0) return REART_OK;
     if (!x || !y || !seed_xy || !seed_yx || !loss || !grad_x || !fx_bits) return REART_ERR_INVALID_ARG;
@@ -222,13 +301,21 @@ extern "C" int reart_chamfer_loss(const float *x, const float *y, int N, int P1,
     char *ws = (char *)workspace;
     float *xsoa = (float *)(ws + p.o_xsoa), *ysoa = (float *)(ws + p.o_ysoa);
     float *xbox = (float *)(ws + p.o_xbox), *ybox = (float *)(ws + p.o_ybox);
+    const int64_t *len64 = ragged ? (const int64_t *)(ws + p.o_len64) : nullptr;
+    const int *len32 = ragged ? (const int *)(ws + p.o_len32) : nullptr;
+    if (ragged) {
+        rc = chamfer_stage_launch(x, y, len_x, len_y, N, P1, P2, 3, seed_xy, seed_yx, ws, p, st);
+        if (rc != REART_OK) return rc;
+    }
     // ---- prep: x always; y's image and boxes only when y is new to this workspace.  The ticket of the consumer's last-
     // workgroup test is cleared in front of every call (4 bytes): a call never depends on how an earlier one ended
     if (hipMemsetAsync(ws + p.o_ticket, 0, sizeof(unsigned int), st) != hipSuccess) return REART_ERR_LAUNCH;
     SoaArgs sa = {};
-    sa.job[0].src = x; sa.job[0].dst = xsoa; sa.job[0].P = P1; sa.job[0].Ppad = p.Ppad1;
+    sa.job[0].src = x; sa.job[0].len = len64; sa.job[0].dst = xsoa; sa.job[0].P = P1; sa.job[0].Ppad = p.Ppad1;
     sa.job[1] = sa.job[0];
-    if (!y_unchanged) { sa.job[1].src = y; sa.job[1].dst = ysoa; sa.job[1].P = P2; sa.job[1].Ppad = p.Ppad2; }
+    if (!y_unchanged) {
+        sa.job[1].src = y; sa.job[1].len = ragged ? len64 + N : nullptr; sa.job[1].dst = ysoa; sa.job[1].P = P2; sa.job[1].Ppad = p.Ppad2;
+    }
     rc = reart_soa_launch(sa, p.Ppad1 > p.Ppad2 ? p.Ppad1 : p.Ppad2, N, y_unchanged ? 1 : 2, st);
     if (rc != REART_OK) return rc;
     rc = reart_boxes_launch(xsoa, N, p.Ppad1, xbox, st);
@@ -243,6 +330,7 @@ extern "C" int reart_chamfer_loss(const float *x, const float *y, int N, int P1,
     for (int j = 0; j < 2; ++j) {
         KnnJob &jb = sr.k1[j];
         jb.q = j ? y : x; jb.tsoa = j ? xsoa : ysoa; jb.boxes = j ? xbox : ybox;
+        if (ragged) { jb.q = (const float *)(ws + (j ? p.o_yq : p.o_xq)); jb.tlen = len32 + (j ? 0 : N); }
         jb.seed = j ? seed_yx : seed_xy;
         jb.P1 = j ? P2 : P1; jb.P2 = j ? P1 : P2; jb.Ppad = j ? p.Ppad1 : p.Ppad2; jb.L = 0; jb.nqg = p.nqg;
         jb.pd = (float *)(ws + (j ? p.o_pd1 : p.o_pd0)); jb.pi = (int *)(ws + (j ? p.o_pi1 : p.o_pi0));
@@ -255,12 +343,20 @@ extern "C" int reart_chamfer_loss(const float *x, const float *y, int N, int P1,
     a.c[0] = x; a.c[1] = y; a.box[0] = xbox; a.box[1] = ybox;
     a.pd[0] = sr.k1[0].pd; a.pd[1] = sr.k1[1].pd; a.pi[0] = sr.k1[0].pi; a.pi[1] = sr.k1[1].pi;
     a.P[0] = P1; a.P[1] = P2; a.nbox[0] = p.Ppad1 / NN_BOX; a.nbox[1] = p.Ppad2 / NN_BOX; a.nr[0] = p.nr1; a.nr[1] = p.nr2;
+    a.len[0] = len_x; a.len[1] = len_y;
     a.od[0] = d_xy; a.od[1] = d_yx; a.oi[0] = i_xy; a.oi[1] = i_yx; a.seed[0] = seed_xy; a.seed[1] = seed_yx;
     a.grad[0] = grad_x; a.grad[1] = grad_y; a.bits = fx_bits;
     a.part = (double *)(ws + p.o_part); a.ticket = (unsigned int *)(ws + p.o_ticket); a.loss = loss; a.N = N;
     hipLaunchKernelGGL(chamfer_loss_kernel, dim3(p.nr1 + p.nr2, N), dim3(CL_BS), 0, st, a);
     REART_CHECK_LAUNCH();
     return REART_OK;
+}
+extern "C" int reart_chamfer_loss(const float *x, const float *y, int N, int P1, int P2, int32_t *seed_xy, int32_t *seed_yx,
+                                  int y_unchanged, float *d_xy, int64_t *i_xy, float *d_yx, int64_t *i_yx, float *loss,
+                                  float *grad_x, float *grad_y, int32_t *fx_bits, void *workspace, size_t workspace_bytes,
+                                  void *stream) {
+    return reart_chamfer_loss_ragged(x, y, N, P1, P2, seed_xy, seed_yx, y_unchanged, d_xy, i_xy, d_yx, i_yx, loss, grad_x, grad_y,
+                                     fx_bits, workspace, workspace_bytes, stream, nullptr, nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -272,6 +368,7 @@ struct ChamferPointsArgs {
     const float *pd[2];         // search records of direction d (0: x -> y, 1: y -> x) [N,P[d]]
     const int *pi[2];
     int P[2], nr[2];            // points of the query cloud; consumer ranges (0: the direction was not searched)
+    const int *len[2];          // nullable [N]: live points of cloud d (cl_len)
     float *od[2];               // [N,P[d]]
     int64_t *oi[2];
     int *seed[2];
@@ -286,17 +383,20 @@ __global__ __launch_bounds__(CL_BS) void chamfer_points_kernel(ChamferPointsArgs
     const size_t ow = (size_t)n * a.P[d] + i;
     const float d0 = a.pd[d][ow];
     const int j0 = a.pi[d][ow];
-    const bool ok0 = (unsigned)j0 < (unsigned)a.P[o];
+    const bool ok0 = i < cl_len(a.len[d], n, a.P[d]) && (unsigned)j0 < (unsigned)cl_len(a.len[o], n, a.P[o]);
     a.od[d][ow] = ok0 ? d0 : 0.0f;
     a.oi[d][ow] = (int64_t)(ok0 ? j0 : 0);
     a.seed[d][ow] = ok0 ? j0 : -1;
 }
 
-extern "C" int reart_chamfer_points(const float *x, const float *y, int N, int P1, int P2, int directions, int32_t *seed_xy,
-                                    int32_t *seed_yx, int y_unchanged, float *d_xy, int64_t *i_xy, float *d_yx, int64_t *i_yx,
-                                    void *workspace, size_t workspace_bytes, void *stream) {
+// reart_chamfer_points is this with both lengths NULL
+extern "C" int reart_chamfer_points_ragged(const float *x, const float *y, int N, int P1, int P2, int directions, int32_t *seed_xy,
+                                           int32_t *seed_yx, int y_unchanged, float *d_xy, int64_t *i_xy, float *d_yx, int64_t *i_yx,
+                                           void *workspace, size_t workspace_bytes, void *stream, const int32_t *len_x,
+                                           const int32_t *len_y) {
+    const bool ragged = len_x || len_y;
     ChamferLossPlan p;
-    int rc = chamfer_loss_plan(N, P1, P2, &p);
+    int rc = chamfer_loss_plan(N, P1, P2, &p, ragged);
     if (rc != REART_OK) return rc;
     if (directions < 1 || directions > 3) return REART_ERR_INVALID_ARG;
     if (N == 0 || P1 == 0 || P2 == 0) return REART_OK;
@@ -309,17 +409,24 @@ extern "C" int reart_chamfer_points(const float *x, const float *y, int N, int P
     char *ws = (char *)workspace;
     float *xsoa = (float *)(ws + p.o_xsoa), *ysoa = (float *)(ws + p.o_ysoa);
     float *xbox = (float *)(ws + p.o_xbox), *ybox = (float *)(ws + p.o_ybox);
+    const int64_t *len64 = ragged ? (const int64_t *)(ws + p.o_len64) : nullptr;
+    const int *len32 = ragged ? (const int *)(ws + p.o_len32) : nullptr;
+    if (ragged) {
+        rc = chamfer_stage_launch(x, y, len_x, len_y, N, P1, P2, directions, seed_xy, seed_yx, ws, p, st);
+        if (rc != REART_OK) return rc;
+    }
     // ---- prep: only the TARGET cloud of a searched direction needs an image: y for x -> y (unless unchanged), x for y -> x
     const bool prep_x = yx, prep_y = xy && !y_unchanged;
     SoaArgs sa = {};
     int njobs = 0, maxPpad = 0;
     if (prep_x) {
         SoaJob &jb = sa.job[njobs++];
-        jb.src = x; jb.dst = xsoa; jb.P = P1; jb.Ppad = p.Ppad1; maxPpad = p.Ppad1;
+        jb.src = x; jb.len = len64; jb.dst = xsoa; jb.P = P1; jb.Ppad = p.Ppad1; maxPpad = p.Ppad1;
     }
     if (prep_y) {
         SoaJob &jb = sa.job[njobs++];
-        jb.src = y; jb.dst = ysoa; jb.P = P2; jb.Ppad = p.Ppad2; maxPpad = p.Ppad2 > maxPpad ? p.Ppad2 : maxPpad;
+        jb.src = y; jb.len = ragged ? len64 + N : nullptr; jb.dst = ysoa; jb.P = P2; jb.Ppad = p.Ppad2;
+        maxPpad = p.Ppad2 > maxPpad ? p.Ppad2 : maxPpad;
     }
     if (njobs) {
         if (njobs == 1) sa.job[1] = sa.job[0];
@@ -343,6 +450,7 @@ extern "C" int reart_chamfer_points(const float *x, const float *y, int N, int P
         if (!(directions & (1 << j))) continue;
         KnnJob &jb = sr.k1[sr.n1++];
         jb.q = j ? y : x; jb.tsoa = j ? xsoa : ysoa; jb.boxes = j ? xbox : ybox;
+        if (ragged) { jb.q = (const float *)(ws + (j ? p.o_yq : p.o_xq)); jb.tlen = len32 + (j ? 0 : N); }
         jb.seed = j ? seed_yx : seed_xy;
         jb.P1 = j ? P2 : P1; jb.P2 = j ? P1 : P2; jb.Ppad = j ? p.Ppad1 : p.Ppad2; jb.L = 0; jb.nqg = nqg;
         jb.pd = (float *)(ws + (j ? p.o_pd1 : p.o_pd0)); jb.pi = (int *)(ws + (j ? p.o_pi1 : p.o_pi0));
@@ -353,11 +461,17 @@ extern "C" int reart_chamfer_points(const float *x, const float *y, int N, int P
     rc = reart_search_launch(sr, st);
     if (rc != REART_OK) return rc;
     // ---- consumer
-    a.P[0] = P1; a.P[1] = P2;
+    a.P[0] = P1; a.P[1] = P2; a.len[0] = len_x; a.len[1] = len_y;
     a.od[0] = d_xy; a.od[1] = d_yx; a.oi[0] = i_xy; a.oi[1] = i_yx; a.seed[0] = seed_xy; a.seed[1] = seed_yx;
     hipLaunchKernelGGL(chamfer_points_kernel, dim3(a.nr[0] + a.nr[1], N), dim3(CL_BS), 0, st, a);
     REART_CHECK_LAUNCH();
     return REART_OK;
+}
+extern "C" int reart_chamfer_points(const float *x, const float *y, int N, int P1, int P2, int directions, int32_t *seed_xy,
+                                    int32_t *seed_yx, int y_unchanged, float *d_xy, int64_t *i_xy, float *d_yx, int64_t *i_yx,
+                                    void *workspace, size_t workspace_bytes, void *stream) {
+    return reart_chamfer_points_ragged(x, y, N, P1, P2, directions, seed_xy, seed_yx, y_unchanged, d_xy, i_xy, d_yx, i_yx, workspace,
+                                       workspace_bytes, stream, nullptr, nullptr);
 }
 
 struct ChamferPointsBwdArgs {
@@ -368,6 +482,7 @@ struct ChamferPointsBwdArgs {
     float *grad[2];             // [N,P[d],3]; grad[1] nullable
     int *bits;                  // [N,2] fractional bits of the fixed-point sums into cloud d of batch element n
     int P[2], nr[2];
+    const int *len[2];          // nullable [N]: live points of cloud d (cl_len)
 };
 
 // Workgroup (r, n) of cloud d owns the points r*CL_BS .. of cloud d ("own"); o = 1 - d is the other cloud.
@@ -387,46 +502,52 @@ __global__ __launch_bounds__(CL_BS) void chamfer_points_bwd_kernel(ChamferPoints
     const int Pw = a.P[d], Po = a.P[o];
     const float *own = a.c[d] + (size_t)n * Pw * 3, *oth = a.c[o] + (size_t)n * Po * 3;
     const float *gw = a.g[d], *go = a.g[o];      // uniform
+    const int Lw = cl_len(a.len[d], n, Pw), Lo = cl_len(a.len[o], n, Po);      // uniform
     for (int e = tid; e < CL_BS * 3; e += CL_BS) s_acc[e] = 0ull;
-    // ---- 1. scale (fmaxf drops NaN, non-finite products are skipped)
+    // ---- 1. scale over the other cloud's live points (fmaxf drops NaN, non-finite products are skipped)
     float mx = 0.f;
     if (go) {
         const float *gg = go + (size_t)n * Po, *dj = a.dd[o] + (size_t)n * Po;
-        for (int j = tid; j < Po; j += CL_BS) {
+        for (int j = tid; j < Lo; j += CL_BS) {
             const float v = fabsf(gg[j]) * sqrtf(dj[j]);
             if (v < INFINITY) mx = fmaxf(mx, v);
         }
     }
     // ---- 2. own term
     const int i = r * CL_BS + tid;
-    const bool live = i < Pw;
-    const int ic = live ? i : Pw - 1;
-    const size_t ow = (size_t)n * Pw + ic;
+    const bool live = i < Lw;
+    const size_t ow = (size_t)n * Pw + i;        // used where i < Pw only
     float first[3] = {0.f, 0.f, 0.f};
-    if (gw) {
+    if (gw && live) {                            // a padding row's index and upstream are never read
         const int64_t j0 = a.idx[d][ow];
-        const bool ok0 = (unsigned long long)j0 < (unsigned long long)Po;
+        const bool ok0 = (unsigned long long)j0 < (unsigned long long)Lo;
         const size_t j0c = ok0 ? (size_t)j0 : 0;
         const float g2 = 2.0f * gw[ow];
 #pragma unroll
-        for (int k = 0; k < 3; ++k) first[k] = ok0 ? g2 * (own[3 * (size_t)ic + k] - oth[3 * j0c + k]) : 0.0f;
+        for (int k = 0; k < 3; ++k) first[k] = ok0 ? g2 * (own[3 * (size_t)i + k] - oth[3 * j0c + k]) : 0.0f;
     }
-    // sums of at most Pmax addends, each of magnitude at most m (1 + 2^-20) < m * 1.000002f
-    const int sbits = reart_fx_bits(Pw > Po ? Pw : Po, cl_block_max(mx, s_mx) * 1.000002f);
+    // sums of at most max(Lw, Lo) addends, each of magnitude at most m (1 + 2^-20) < m * 1.000002f
+    const int sbits = reart_fx_bits(Lw > Lo ? Lw : Lo, cl_block_max(mx, s_mx) * 1.000002f);
     if (r == 0 && tid == 0) {
         a.bits[2 * n + d] = sbits;
         if (d == 0 && !a.grad[1]) a.bits[2 * n + 1] = 0;      // no sums into y in this call
     }
     // ---- 3. the other cloud's indices
-    if (go) cl_scatter_walk(own, oth, a.idx[o] + (size_t)n * Po, go + (size_t)n * Po, Pw, Po, r * CL_BS, sbits, s_acc);
+    if (go && r * CL_BS < Lw) cl_scatter_walk(own, oth, a.idx[o] + (size_t)n * Po, go + (size_t)n * Po, Lw, Lo, r * CL_BS, sbits, s_acc);
     __syncthreads();
     // ---- 4. gradient
     if (live) cl_grad_store(a.grad[d] + 3 * ow, first, s_acc, sbits);
+    else if (i < Pw) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) a.grad[d][3 * ow + k] = 0.0f;
+    }
 }
 
-extern "C" int reart_chamfer_points_backward(const float *x, const float *y, int N, int P1, int P2, const int64_t *i_xy,
-                                             const int64_t *i_yx, const float *d_xy, const float *d_yx, const float *g_xy,
-                                             const float *g_yx, float *grad_x, float *grad_y, int32_t *fx_bits, void *stream) {
+// reart_chamfer_points_backward is this with both lengths NULL
+extern "C" int reart_chamfer_points_backward_ragged(const float *x, const float *y, int N, int P1, int P2, const int64_t *i_xy,
+                                                    const int64_t *i_yx, const float *d_xy, const float *d_yx, const float *g_xy,
+                                                    const float *g_yx, float *grad_x, float *grad_y, int32_t *fx_bits, void *stream,
+                                                    const int32_t *len_x, const int32_t *len_y) {
     ChamferLossPlan p;
     const int rc = chamfer_loss_plan(N, P1, P2, &p);
     if (rc != REART_OK) return rc;
@@ -438,7 +559,14 @@ extern "C" int reart_chamfer_points_backward(const float *x, const float *y, int
     a.c[0] = x; a.c[1] = y; a.idx[0] = i_xy; a.idx[1] = i_yx; a.dd[0] = d_xy; a.dd[1] = d_yx; a.g[0] = g_xy; a.g[1] = g_yx;
     a.grad[0] = grad_x; a.grad[1] = grad_y; a.bits = fx_bits;
     a.P[0] = P1; a.P[1] = P2; a.nr[0] = p.nr1; a.nr[1] = grad_y ? p.nr2 : 0;
+    a.len[0] = len_x; a.len[1] = len_y;
     hipLaunchKernelGGL(chamfer_points_bwd_kernel, dim3(a.nr[0] + a.nr[1], N), dim3(CL_BS), 0, (hipStream_t)stream, a);
     REART_CHECK_LAUNCH();
     return REART_OK;
+}
+extern "C" int reart_chamfer_points_backward(const float *x, const float *y, int N, int P1, int P2, const int64_t *i_xy,
+                                             const int64_t *i_yx, const float *d_xy, const float *d_yx, const float *g_xy,
+                                             const float *g_yx, float *grad_x, float *grad_y, int32_t *fx_bits, void *stream) {
+    return reart_chamfer_points_backward_ragged(x, y, N, P1, P2, i_xy, i_yx, d_xy, d_yx, g_xy, g_yx, grad_x, grad_y, fx_bits, stream,
+                                                nullptr, nullptr);
 }

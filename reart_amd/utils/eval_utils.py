@@ -44,11 +44,45 @@ def eval_seg(gt_segm, pd_segm, as_tensor=False, num_labels=128):
     return (agree / (n * n)).float().cpu().numpy()
 
 
+def _frame_lengths(points_set):
+    """Point counts of a list of frames whose lengths differ, else None (the set stacks into one tensor)."""
+    if not isinstance(points_set, (list, tuple)) or not all(hasattr(f, "shape") and len(f.shape) == 2 for f in points_set):
+        return None
+    lengths = [int(f.shape[0]) for f in points_set]
+    return lengths if len(set(lengths)) > 1 else None
+
+
+def _pad_frames(points_set):
+    """Frames [n_t,3] -> ([T,max n_t,3] float32 padded with zeros, lengths)."""
+    frames = [torch.as_tensor(f).float() for f in points_set]
+    lengths = [int(f.shape[0]) for f in frames]
+    out = torch.zeros((len(frames), max(lengths), 3), dtype=torch.float32, device=frames[0].device)
+    for t, f in enumerate(frames):
+        out[t, :lengths[t]] = f.to(out.device)
+    return out, lengths
+
+
 def compute_chamfer_list(points_set1, points_set2, reduction="sum", chamfer=None):
     """utils/eval_utils.py:39-66 (KD-tree Chamfer per frame) on the GPU search: per frame the sum / mean of the squared
     nearest-neighbour distances of both directions; "mean" / "sum" reduce over frames like the reference.
     ``chamfer``: a ``utils.chamfer.ChamferPoints`` the caller keeps between snapshots -- both directions then come from one
-    call of it, warm from the previous snapshot (same distances); None: two cold ``ChamferDistance`` searches."""
+    call of it, warm from the previous snapshot (same distances); None: two cold ``ChamferDistance`` searches.
+    Lists whose frames differ in length (the reference takes any) are padded to the longest frame and go through ONE
+    ``ChamferPoints`` call with lengths (``chamfer``, or a temporary one); "mean" is over each frame's own points."""
+    if _frame_lengths(points_set1) is not None or _frame_lengths(points_set2) is not None:
+        from .chamfer import ChamferPoints
+
+        if len(points_set1) != len(points_set2):
+            raise ValueError("compute_chamfer_list: the two lists must hold the same number of frames")
+        (a, la), (b, lb) = _pad_frames(points_set1), _pad_frames(points_set2)
+        d12, d21 = (chamfer if chamfer is not None else ChamferPoints())(a, b, x_lengths=la, y_lengths=lb)
+        # padding rows are exactly 0: the row sums are the live points'
+        s12, s21 = d12.double().sum(1), d21.double().sum(1)
+        if reduction == "mean":
+            na, nb = (torch.tensor(l, dtype=torch.float64, device=a.device) for l in (la, lb))
+            return float((s12 / na + s21 / nb).mean())
+        per = s12 + s21
+        return float(per.sum()) if reduction == "sum" else per.cpu().numpy()
     a, b = torch.as_tensor(points_set1).float(), torch.as_tensor(points_set2).float()
     if chamfer is not None:
         d12, d21 = chamfer(a, b)
