@@ -250,7 +250,11 @@ __device__ __forceinline__ void knn_pruned_wave(const KnnJob &jb, const int S, c
     for (int k = 0; k < KK; ++k) { bm[k] = INFINITY; bb[k] = -1; }
     const float *tx_g = tx;
     // ONE uniform counter for both statistics (a scalar register less, one s_add per event): bits 0..19 the distance
-    // evaluations (< 2^20 per wave), bits 20..31 the work count that orders the next launch (a heuristic: overflow is harmless)
+    // evaluations, bits 20..31 the work count that orders the next launch (a heuristic: overflow is harmless).  `pairs` is
+    // the evaluation count only while a wave stays below 2^20 of them, i.e. while it scans or drains fewer than 16 384 targets:
+    // every cloud of the headline shapes, warm or cold.  A cold wave over a larger slice (65 536 targets at S = 4) carries into
+    // the work count and reports the count modulo 2^20; no result depends on either field (the order of the next launch does,
+    // through buckets clamped to 255 -- tests/test_search_large_gpu.py runs such clouds, profiled and not, bit for bit)
     wp |= PR_WORK(16);                                                   // prologue ~ 16 tests
 
     const int queue_max = a.sparse;   // boxes needed by at most this many queries go through the (query, box) queue (0: off)

@@ -30,7 +30,27 @@ round beyond 1024 S targets).
 
 The model functions are float32 with the kernel's order of operations, ``(dx dx + dy dy) + dz dz`` and
 ``e = max(lo - q, q - hi, 0)``; numpy rounds every operation once (no fused multiply-add) and keeps denormal numbers.
-A slot for which no target exists (P2 < K) holds distance 0 and index 0, as ``oracle.knn_points`` leaves it."""
+A slot for which no target exists (P2 < K) holds distance 0 and index 0, as ``oracle.knn_points`` leaves it.
+
+``large_case(name)`` gives the cases of a second table, ``LARGE``, by the same conventions; they reach what the sizes
+above cannot: a third and later coarse round, box numbers above 4096, target indices above 65 535, more than 2^20 distance
+evaluations by one cold wave.  ``NAMES`` does not contain them.
+
+    case          queries                                    targets                          what it is for
+    round3        1000, as `jump`                            8208 uniform (2 x 4096 + 16)     third coarse round of one box at S = 4; nine
+                                                                                              rounds at S = 1
+    coincident8k  130 uniform                                8208 copies of one point         every distance tied, nothing prunable: every
+                                                                                              wave scans or queues every box of three rounds
+    lattice27k    every 7th cell centre, every 11th          30^3 lattice, step 0.05          exact ties between distinct targets in different
+                  lattice point (6313)                                                        boxes, slices and coarse rounds (7 at S = 4)
+    scan70k       the targets permuted + N(0, 2e-3), every   70 000 on a closed bumpy         indices above 65 535, box numbers above 4096,
+                  5th re-drawn uniformly (70 000)            surface + N(0, 1e-3)             18 coarse rounds at S = 4, more than 2^20
+                                                                                              evaluations per cold wave; free of ties
+    fanin70k      chamfer_loss_ref.cluster_case(70 000):     its 8 x points                   70 000 addends in one target's fixed-point sum
+                  the 70 000 y points
+
+The model functions above build full P1 x P2 matrices; for the large cases use ``brute_chunked`` / ``kth_chunked`` / ``blocks``
+(256 queries at a time) or pass the rows of ``sample(name)`` -- no matrix above 64 M entries (``MAX_ENTRIES``)."""
 import functools
 
 import numpy as np
@@ -102,7 +122,7 @@ _TABLE.update({f"small_{p1}x{p2}": functools.partial(_small, p1, p2) for p1, p2 
 NAMES = tuple(_TABLE)
 
 
-def _stored(c):
+def stored(c):
     """float32, in the leaf order of its own k-d tree."""
     import torch
 
@@ -116,7 +136,7 @@ def _stored(c):
 def case(name, seed=0):
     """(queries [P1,3], targets [P2,3]) float32 in k-d leaf order, read-only.  ``seed`` draws another instance of the case."""
     rng = np.random.default_rng([NAMES.index(name), seed, 2024])
-    q, t = (_stored(c) for c in _TABLE[name](rng))
+    q, t = (stored(c) for c in _TABLE[name](rng))
     q.setflags(write=False)
     t.setflags(write=False)
     return q, t
@@ -176,3 +196,113 @@ def violations(q, t):
     """Number of (query, target) pairs with ``lower_bound(query, box of target) > distance`` in float32."""
     lb = lower_bound(q, *boxes(t))
     return int((lb[:, np.arange(t.shape[0]) // BOX] > sqdist(q, t)).sum())
+
+
+# ---- the large cases --------------------------------------------------------------------------------------------------
+MAX_ENTRIES = 64 * 2 ** 20      # no model matrix above this many entries
+BLOCK = 256                     # queries per block of the chunked forms
+
+
+def _round3(rng, seed=0):
+    t = _uniform(rng, 8208)
+    q = t[rng.integers(0, 8208, 1000)] + rng.normal(0, 2e-3, (1000, 3))
+    q[::5] = _uniform(rng, 200)
+    return q, t
+
+
+def _coincident8k(rng, seed=0):
+    p = rng.uniform(-0.4, 0.4, (1, 3))
+    return rng.uniform(-0.4, 0.4, (130, 3)), np.repeat(p, 8208, 0)
+
+
+def _lattice27k(rng, seed=0):
+    lat = np.stack(np.meshgrid(*[np.arange(30) * 0.05] * 3, indexing="ij"), -1).reshape(-1, 3)
+    return np.concatenate([lat[::7] + 0.025, lat[::11]]), lat
+
+
+def _scan70k(rng, seed=0, n=70000):
+    u = rng.normal(size=(n, 3))
+    u /= np.linalg.norm(u, axis=-1, keepdims=True)
+    t = u * (0.3 + 0.05 * np.sin(7 * u[:, :1]) * np.cos(5 * u[:, 1:2])) + rng.normal(0, 1e-3, (n, 3))
+    q = t[rng.permutation(n)] + rng.normal(0, 2e-3, (n, 3))
+    q[::5] = _uniform(rng, q[::5].shape[0])
+    return q, t
+
+
+def _fanin70k(rng, seed=0):      # the only construction that draws from a generator of its own
+    from tests.chamfer_loss_ref import cluster_case
+
+    x, y = cluster_case(n_cluster=70000, seed=3 + seed)
+    return y[0], x[0]
+
+
+#         case: (first word of the generator's seed, construction(rng, seed))
+LARGE = {"round3": (101, _round3), "coincident8k": (102, _coincident8k), "lattice27k": (103, _lattice27k),
+         "scan70k": (100, _scan70k), "fanin70k": (104, _fanin70k)}
+LARGE_NAMES = tuple(LARGE)
+ROUNDS3 = ("round3", "coincident8k", "lattice27k", "scan70k")       # the cases that claim a third coarse round at S = 4
+
+
+@functools.lru_cache(maxsize=None)
+def large_case(name, seed=0):
+    """As ``case``, for the table ``LARGE``."""
+    key, make = LARGE[name]
+    rng = np.random.default_rng([key, seed, 2024])
+    q, t = (stored(c) for c in make(rng, seed))
+    q.setflags(write=False)
+    t.setflags(write=False)
+    return q, t
+
+
+def sample(P1, n=512):
+    """``n`` fixed rows out of P1 (all of them when P1 <= n), ascending."""
+    return np.arange(P1) if P1 <= n else np.sort(np.random.default_rng(P1).choice(P1, n, replace=False))
+
+
+def coarse_rounds(P2, S):
+    """(boxes, coarse rounds of 64 S boxes) of P2 targets."""
+    nbox = (P2 + BOX - 1) // BOX
+    return nbox, (nbox + 64 * S - 1) // (64 * S)
+
+
+def blocks(q, t):
+    """(first row, float32 distances [<= 256, P2]) of every block of 256 queries; the rows are the caller's to overwrite."""
+    assert BLOCK * t.shape[0] <= MAX_ENTRIES
+    for r in range(0, q.shape[0], BLOCK):
+        yield r, sqdist(q[r:r + BLOCK], t)
+
+
+def brute_chunked(q, t, K):
+    """``brute`` without the full matrix: per block of 256 queries, K times the first minimum of the row (the lowest index
+    among equal distances), which is then struck out -- the first K entries of the stable sort."""
+    n = min(K, t.shape[0])
+    dists, idx = np.zeros((q.shape[0], K), np.float32), np.zeros((q.shape[0], K), np.int64)
+    for r, d in blocks(q, t):
+        rows = np.arange(d.shape[0])
+        for k in range(n):
+            j = d.argmin(1)
+            dists[r:r + d.shape[0], k], idx[r:r + d.shape[0], k] = d[rows, j], j
+            d[rows, j] = np.inf
+    return dists, idx
+
+
+def kth_chunked(q, t, K):
+    """``kth`` without the full matrix -> (K-th distance [P1], number of targets at exactly that distance [P1])."""
+    n = min(K, t.shape[0])
+    out, cnt = np.zeros(q.shape[0], np.float32), np.zeros(q.shape[0], np.int64)
+    for r, d in blocks(q, t):
+        out[r:r + d.shape[0]] = np.partition(d, n - 1, axis=1)[:, n - 1]
+        cnt[r:r + d.shape[0]] = (d == out[r:r + d.shape[0], None]).sum(1)
+    return out, cnt
+
+
+def tie_fraction_chunked(q, t, K):
+    """``tie_fraction`` without the full matrix."""
+    return float((kth_chunked(q, t, K)[1] > 1).mean())
+
+
+def violations_chunked(q, t):
+    """``violations`` without the full matrices."""
+    lo, hi = boxes(t)
+    box_of = np.arange(t.shape[0]) // BOX
+    return sum(int((lower_bound(q[r:r + BLOCK], lo, hi)[:, box_of] > d).sum()) for r, d in blocks(q, t))

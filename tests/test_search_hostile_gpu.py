@@ -32,11 +32,13 @@ def _ref(name, K, swapped=False, seed=0):
 
 
 # ---- a. knn_points_idx_warm -------------------------------------------------------------------------------------------
-def _regimes(q, t, i_ref, rng):
-    """Seed arrays [N,P1,K] (None: cold) by name, for batched clouds q [N,P1,3], t [N,P2,3] with exact neighbours i_ref."""
+def _regimes(q, t, i_ref, rng, far=None):
+    """Seed arrays [N,P1,K] (None: cold) by name, for batched clouds q [N,P1,3], t [N,P2,3] with exact neighbours i_ref.
+    ``far`` [N,P1]: the farthest target of every query where the caller has it already (large clouds: a chunked arg-max)."""
     N, P1, K = i_ref.shape
     P2 = t.shape[1]
-    far = np.stack([sc.sqdist(q[n], t[n]).argmax(1) for n in range(N)])            # [N,P1]
+    if far is None:
+        far = np.stack([sc.sqdist(q[n], t[n]).argmax(1) for n in range(N)])        # [N,P1]
     garbage = rng.integers(-5, P2 + 5, (N, P1, K))
     garbage[:, ::3, :] = 0                                                         # repeats inside a query
     mixed = rng.integers(-5, P2 + 5, (N, P1, K))
@@ -61,14 +63,14 @@ def _warm(dev, tq, tt, K, seed, d_ref, i_ref, what):
     return ts
 
 
-def _warm_all_regimes(dev, q, t, refs, label):
-    """q [N,P1,3], t [N,P2,3]; refs {K: (d [N,P1,K], i [N,P1,K])}."""
+def _warm_all_regimes(dev, q, t, refs, label, far=None):
+    """q [N,P1,3], t [N,P2,3]; refs {K: (d [N,P1,K], i [N,P1,K])}; far: see _regimes."""
     tq, tt = _up(q, dev), _up(t, dev)
     for K in (1, 3):
         d_ref, i_ref = refs[K]
         rng = np.random.default_rng(K)
         own = None
-        for regime, seed in _regimes(q, t, i_ref, rng).items():
+        for regime, seed in _regimes(q, t, i_ref, rng, far).items():
             ts = _warm(dev, tq, tt, K, seed, d_ref, i_ref, f"{label} K={K} seeds: {regime}")
             own = ts if own is None else own
         _warm(dev, tq, tt, K, own.cpu().numpy(), d_ref, i_ref, f"{label} K={K} seeds: the call's own")
