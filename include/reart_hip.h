@@ -605,6 +605,10 @@ int reart_mlp_layer(const float *X, int ldx, const int64_t *gather_idx, int K, i
                     const float *F, int D, const float *Q, const float *C, int xyz_first,
                     const float *Wt, const float *bias, int rows, int Cin, int Cout, int relu,
                     int pool_k, float *Y, int ldy, int ycol0, void *stream);
+/* Host only, no device needed: the kernel instantiation reart_mlp_layer launches for these sizes, packed as
+ * NB | BK << 8 | ANY << 16 -- NB accumulators of 32 columns per wave (1, 2, 3 or 7), a K step of BK (8 or 16), ANY = 1 for
+ * group sizes pooled through LDS; 0 where Cin < 1, Cout < 1 or pool_k < 0.  The launcher decides by this function. */
+int reart_mlp_layer_kernel(int Cin, int Cout, int pool_k);
 
 /* Three such layers in ONE launch for a scale of the first set-abstraction level (PointNetSetAbstractionMsg,
  * networks/pointnet2_utils.py:257-295): gathered input [F (3) | Q - C] (6 columns) -> C1 -> C2 -> C3 (each with bias and

@@ -90,6 +90,7 @@ PROTOTYPES = {
     "reart_ik_fit": (c_int, [P, P, P, c_int, P, P, c_int, P, P, c_int, P, c_int, P, c_int, c_float, c_float, c_float, c_float, P, P, P]),
     "reart_mlp_layer": (c_int, [P, c_int, P, c_int, c_int, c_int, P, c_int, P, P, c_int, P, P, c_int, c_int, c_int,
                                 c_int, c_int, P, c_int, c_int, P]),
+    "reart_mlp_layer_kernel": (c_int, [c_int] * 3),
     "reart_mlp_chain3": (c_int, [P, c_int, c_int, c_int, P, P, P, P, P, c_int, P, P, c_int, P, P, c_int, c_int, P, c_int, c_int, P]),
     "reart_mlp_chain3_wide_workspace_bytes": (c_size_t, [c_int] * 4),
     "reart_mlp_chain3_wide": (c_int, [P, c_int, c_int, c_int, P, c_int, P, P, P, P, c_int, P, P, c_int, P, P, c_int, c_int, P, c_int,

@@ -252,6 +252,20 @@ __global__ __launch_bounds__(256) void mlp_gemm_kernel(GemmArgs a) {
     }
 }
 
+// The mlp_gemm_kernel<NB, BK, ANY> a layer of these sizes runs, as NB | BK << 8 | ANY << 16 (0: sizes out of range): the one
+// place that decides it.  reart_mlp_layer asks it, and tests/test_pointnet_range_cpu.py holds its table of cases to it.
+extern "C" int reart_mlp_layer_kernel(int Cin, int Cout, int pool_k) {
+    if (Cin < 1 || Cout < 1 || pool_k < 0) return 0;
+    // measured: NB = 4 for ALL wide layers is slower (7.5 vs 6.7 ms: half the resident waves), and for the gathered wide-K
+    // first layers of sa2 (323 -> 128, whose A tile NB = 2 stages twice) alone as well (5.69 vs 5.57 ms per forward)
+    // Cout = 196 (sa2's 128 -> 196): four 64-column blocks compute 256 columns for 196; ONE block of seven 32-column
+    // accumulators computes 224 and stages the A tile once
+    const int NB = Cout <= 32 ? 1 : (Cout <= 64 ? 2 : (Cout <= 96 ? 3 : ((Cout > 192 && Cout <= 224) ? 7 : 2)));
+    const int BK = Cin <= 8 ? 8 : 16;   // measured: 32 for the wide layers is slower (7.76 vs 6.72 ms for the extractor)
+    const int any = pool_k > 1 && pool_k != 32 && pool_k != 64 && pool_k != 128;   // groups of one row: the un-pooled call
+    return NB | (BK << 8) | (any << 16);
+}
+
 extern "C" int reart_mlp_layer(const float *X, int ldx, const int64_t *gather_idx, int K, int S, int Npts,
                                const float *F, int D, const float *Q, const float *C, int xyz_first,
                                const float *Wt, const float *bias, int rows, int Cin, int Cout, int relu,
@@ -266,18 +280,14 @@ extern "C" int reart_mlp_layer(const float *X, int ldx, const int64_t *gather_id
     }
     if (pool_k < 0 || (pool_k && rows % pool_k != 0)) return REART_ERR_INVALID_ARG;
     if (pool_k == 1) pool_k = 0;                       // groups of one row: the un-pooled call
-    const bool any = pool_k && pool_k != 32 && pool_k != 64 && pool_k != 128;
+    const int kern = reart_mlp_layer_kernel(Cin, Cout, pool_k);
+    const int NB = kern & 255, BK = (kern >> 8) & 255;
+    const bool any = (kern >> 16) != 0;
     GemmArgs a = {};
     a.X = X; a.ldx = ldx; a.idx = gather_idx; a.K = K; a.S = S; a.Npts = Npts; a.F = F; a.D = D; a.Q = Q; a.C = C;
     a.xyz_first = xyz_first; a.Wt = Wt; a.bias = bias; a.rows = rows; a.Cin = Cin; a.Cout = Cout; a.relu = relu;
     a.pool_k = pool_k; a.Y = Y; a.ldy = ldy; a.ycol0 = ycol0;
     a.tile_rows = any ? (pool_k <= GM_BM ? (GM_BM / pool_k) * pool_k : pool_k) : GM_BM;
-    // measured: NB = 4 for ALL wide layers is slower (7.5 vs 6.7 ms: half the resident waves), and for the gathered wide-K
-    // first layers of sa2 (323 -> 128, whose A tile NB = 2 stages twice) alone as well (5.69 vs 5.57 ms per forward)
-    // Cout = 196 (sa2's 128 -> 196): four 64-column blocks compute 256 columns for 196; ONE block of seven 32-column
-    // accumulators computes 224 and stages the A tile once
-    const int NB = Cout <= 32 ? 1 : (Cout <= 64 ? 2 : (Cout <= 96 ? 3 : ((Cout > 192 && Cout <= 224) ? 7 : 2)));
-    const int BK = Cin <= 8 ? 8 : 16;   // measured: 32 for the wide layers is slower (7.76 vs 6.72 ms for the extractor)
     const dim3 grid(reart_div_up(rows, a.tile_rows), reart_div_up(Cout, 32 * NB));
     hipStream_t st = (hipStream_t)stream;
 #define GM_LAUNCH(NBv, BKv) do { if (any) hipLaunchKernelGGL((mlp_gemm_kernel<NBv, BKv, true>), grid, dim3(256), 0, st, a); \
@@ -286,7 +296,6 @@ extern "C" int reart_mlp_layer(const float *X, int ldx, const int64_t *gather_id
     switch (NB) {
         case 1: GM_PICK(1); break;
         case 2: GM_PICK(2); break;
-        case 4: GM_PICK(4); break;
         case 7: GM_PICK(7); break;
         default: GM_PICK(3); break;
     }

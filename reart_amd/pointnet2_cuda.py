@@ -22,13 +22,12 @@ def furthest_point_sampling_wrapper(b, n, m, points_tensor, temp_tensor, idx_ten
     if n > _lib.FPS_MAX_N:
         raise NotImplementedError(f"furthest_point_sampling_wrapper: n = {n} > {_lib.FPS_MAX_N} points (REART_FPS_MAX_N)")
     if n <= _lib.FPS_MAX_N_LDS:
-        _lib.require_gpu(points_tensor, idx_tensor)
+        _check(f32=(points_tensor, temp_tensor), i32=(idx_tensor,))   # ``temp`` is unused here, but held to the same contract
         rc = _lib.lib().reart_fps(_lib.ptr(points_tensor), b, n, m, None, 1, _lib.ptr(idx_tensor), None, _lib.stream())
         _lib.check(rc, "reart_fps")
         return 1
-    _lib.require_gpu(points_tensor, temp_tensor, idx_tensor)
-    _contig(points_tensor, temp_tensor, idx_tensor)
-    if temp_tensor.dtype != torch.float32 or temp_tensor.numel() < b * n:
+    _check(f32=(points_tensor, temp_tensor), i32=(idx_tensor,))
+    if temp_tensor.numel() < b * n:
         raise RuntimeError("temp_tensor must be float32 [B,N]")
     rc = _lib.lib().reart_fps_temp(_lib.ptr(points_tensor), b, n, m, None, 1, _lib.ptr(temp_tensor),
                                    _lib.ptr(idx_tensor), None, _lib.stream())
@@ -38,9 +37,7 @@ def furthest_point_sampling_wrapper(b, n, m, points_tensor, temp_tensor, idx_ten
 
 def ball_query_wrapper(b, n, m, radius, nsample, new_xyz_tensor, xyz_tensor, idx_tensor):
     """new_xyz f32 [B,M,3], xyz f32 [B,N,3], idx i32 [B,M,nsample]; CUDA-kernel semantics."""
-    _lib.require_gpu(new_xyz_tensor, xyz_tensor, idx_tensor)
-    if not new_xyz_tensor.is_contiguous() or not xyz_tensor.is_contiguous():
-        raise RuntimeError("tensors must be contiguous")  # CHECK_CONTIGUOUS, ball_query.cpp:12
+    _check(f32=(new_xyz_tensor, xyz_tensor), i32=(idx_tensor,))   # CHECK_INPUT, ball_query.cpp:12
     rc = _lib.lib().reart_ball_query(_lib.ptr(xyz_tensor), _lib.ptr(new_xyz_tensor), b, n, m, float(radius), nsample,
                                      1, _lib.ptr(idx_tensor), None, _lib.stream())
     _lib.check(rc, "reart_ball_query")
@@ -53,7 +50,7 @@ def three_nn_wrapper(b, n, m, unknown_tensor, known_tensor, dist2_tensor, idx_te
     (ux-x)^2 + (uy-y)^2 + (uz-z)^2, scanning k ascending with strict `<` (ties keep the lower index)."""
     from .chamferdist_C import knn_points_idx
 
-    _lib.require_gpu(unknown_tensor, known_tensor, dist2_tensor, idx_tensor)
+    _check(f32=(unknown_tensor, known_tensor, dist2_tensor), i32=(idx_tensor,))
     idx, dists = knn_points_idx(unknown_tensor.reshape(b, n, 3), known_tensor.reshape(b, m, 3), None, None, 3)
     dist2_tensor.reshape(b, n, 3).copy_(dists)
     idx_tensor.reshape(b, n, 3).copy_(idx)
@@ -69,7 +66,7 @@ def knn_wrapper(b, n, m, k, unknown_tensor, known_tensor, dist2_tensor, idx_tens
 
     if k > 16:
         raise NotImplementedError("pointnet2_cuda.knn_wrapper: k <= 16 (REART_MAX_K)")
-    _lib.require_gpu(unknown_tensor, known_tensor, dist2_tensor, idx_tensor)
+    _check(f32=(unknown_tensor, known_tensor, dist2_tensor), i32=(idx_tensor,))
     idx, dists = knn_points_idx(unknown_tensor.reshape(b, n, 3), known_tensor.reshape(b, m, 3), None, None, k)
     dist2_tensor.reshape(b, n, k).copy_(dists)
     idx_tensor.reshape(b, n, k).copy_(idx)
@@ -82,10 +79,23 @@ def _contig(*ts):
             raise RuntimeError("tensors must be contiguous")       # CHECK_CONTIGUOUS in every wrapper of the reference
 
 
+def _check(f32=(), i32=()):
+    """CHECK_INPUT of the reference's wrappers, before anything is launched: the kernels read float32 and int32 through raw
+    pointers, so another dtype (an int64 index tensor, torch's default, would be read as pairs of int32) or a strided
+    tensor is refused here.  Layout and dtype come first, the device last: what is refused is refused on any device."""
+    _contig(*f32, *i32)
+    for t_ in f32:
+        if t_.dtype != torch.float32:
+            raise RuntimeError(f"tensor must be float32, not {t_.dtype}")
+    for t_ in i32:
+        if t_.dtype != torch.int32:
+            raise RuntimeError(f"index tensor must be int32, not {t_.dtype}")
+    _lib.require_gpu(*f32, *i32)
+
+
 def gather_points_wrapper(b, c, n, npoints, points_tensor, idx_tensor, out_tensor):
     """sampling.cpp:11-22 / sampling_gpu.cu:8-24: points f32 [B,C,N], idx i32 [B,npoints] -> out f32 [B,C,npoints]."""
-    _lib.require_gpu(points_tensor, idx_tensor, out_tensor)
-    _contig(points_tensor, idx_tensor, out_tensor)
+    _check(f32=(points_tensor, out_tensor), i32=(idx_tensor,))
     _lib.check(_lib.lib().reart_pn2_gather_points(_lib.ptr(points_tensor), _lib.ptr(idx_tensor), b, c, n, npoints, _lib.ptr(out_tensor),
                                                   _lib.stream()), "reart_pn2_gather_points")
     return 1
@@ -94,8 +104,7 @@ def gather_points_wrapper(b, c, n, npoints, points_tensor, idx_tensor, out_tenso
 def gather_points_grad_wrapper(b, c, n, npoints, grad_out_tensor, idx_tensor, grad_points_tensor):
     """sampling.cpp:24-35 / sampling_gpu.cu:46-63: grad_out f32 [B,C,npoints] accumulated into grad_points f32 [B,C,N] (zeroed
     by the caller, pointnet_lib/pointnet2_utils.py:70)."""
-    _lib.require_gpu(grad_out_tensor, idx_tensor, grad_points_tensor)
-    _contig(grad_out_tensor, idx_tensor, grad_points_tensor)
+    _check(f32=(grad_out_tensor, grad_points_tensor), i32=(idx_tensor,))
     _lib.check(_lib.lib().reart_pn2_gather_points_grad(_lib.ptr(grad_out_tensor), _lib.ptr(idx_tensor), b, c, n, npoints,
                                                        _lib.ptr(grad_points_tensor), _lib.stream()), "reart_pn2_gather_points_grad")
     return 1
@@ -104,8 +113,7 @@ def gather_points_grad_wrapper(b, c, n, npoints, grad_out_tensor, idx_tensor, gr
 def group_points_wrapper(b, c, n, npoints, nsample, points_tensor, idx_tensor, out_tensor):
     """group_points.cpp:26-38 / group_points_gpu.cu:39-54: points f32 [B,C,N], idx i32 [B,npoints,nsample] -> out f32
     [B,C,npoints,nsample]: the gather above over npoints * nsample indices per batch."""
-    _lib.require_gpu(points_tensor, idx_tensor, out_tensor)
-    _contig(points_tensor, idx_tensor, out_tensor)
+    _check(f32=(points_tensor, out_tensor), i32=(idx_tensor,))
     _lib.check(_lib.lib().reart_pn2_gather_points(_lib.ptr(points_tensor), _lib.ptr(idx_tensor), b, c, n, npoints * nsample,
                                                   _lib.ptr(out_tensor), _lib.stream()), "reart_pn2_gather_points")
     return 1
@@ -113,8 +121,7 @@ def group_points_wrapper(b, c, n, npoints, nsample, points_tensor, idx_tensor, o
 
 def group_points_grad_wrapper(b, c, n, npoints, nsample, grad_out_tensor, idx_tensor, grad_points_tensor):
     """group_points.cpp:12-23 / group_points_gpu.cu:8-21: grad_out f32 [B,C,npoints,nsample] accumulated into grad_points."""
-    _lib.require_gpu(grad_out_tensor, idx_tensor, grad_points_tensor)
-    _contig(grad_out_tensor, idx_tensor, grad_points_tensor)
+    _check(f32=(grad_out_tensor, grad_points_tensor), i32=(idx_tensor,))
     _lib.check(_lib.lib().reart_pn2_gather_points_grad(_lib.ptr(grad_out_tensor), _lib.ptr(idx_tensor), b, c, n, npoints * nsample,
                                                        _lib.ptr(grad_points_tensor), _lib.stream()), "reart_pn2_gather_points_grad")
     return 1
@@ -122,8 +129,7 @@ def group_points_grad_wrapper(b, c, n, npoints, nsample, grad_out_tensor, idx_te
 
 def three_interpolate_wrapper(b, c, m, n, points_tensor, idx_tensor, weight_tensor, out_tensor):
     """interpolate.cpp:40-54 / interpolate_gpu.cu:149-169: points f32 [B,C,M], idx i32 / weight f32 [B,N,3] -> out f32 [B,C,N]."""
-    _lib.require_gpu(points_tensor, idx_tensor, weight_tensor, out_tensor)
-    _contig(points_tensor, idx_tensor, weight_tensor, out_tensor)
+    _check(f32=(points_tensor, weight_tensor, out_tensor), i32=(idx_tensor,))
     _lib.check(_lib.lib().reart_pn2_three_interpolate(_lib.ptr(points_tensor), _lib.ptr(idx_tensor), _lib.ptr(weight_tensor), b, c, m, n,
                                                       _lib.ptr(out_tensor), _lib.stream()), "reart_pn2_three_interpolate")
     return None
@@ -131,8 +137,7 @@ def three_interpolate_wrapper(b, c, m, n, points_tensor, idx_tensor, weight_tens
 
 def three_interpolate_grad_wrapper(b, c, n, m, grad_out_tensor, idx_tensor, weight_tensor, grad_points_tensor):
     """interpolate.cpp:56-70 / interpolate_gpu.cu:192-214: grad_out f32 [B,C,N] accumulated into grad_points f32 [B,C,M]."""
-    _lib.require_gpu(grad_out_tensor, idx_tensor, weight_tensor, grad_points_tensor)
-    _contig(grad_out_tensor, idx_tensor, weight_tensor, grad_points_tensor)
+    _check(f32=(grad_out_tensor, weight_tensor, grad_points_tensor), i32=(idx_tensor,))
     _lib.check(_lib.lib().reart_pn2_three_interpolate_grad(_lib.ptr(grad_out_tensor), _lib.ptr(idx_tensor), _lib.ptr(weight_tensor), b, c, n,
                                                            m, _lib.ptr(grad_points_tensor), _lib.stream()), "reart_pn2_three_interpolate_grad")
     return None
