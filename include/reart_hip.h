@@ -351,6 +351,14 @@ typedef struct reart_relax_config {
     float beta1, beta2, eps; /* Adam defaults 0.9, 0.999, 1e-8                            */
     float start_tau, end_tau;/* --start_tau, --end_tau                                    */
     float fixed_tau;         /* > 0: frozen temperature (resume, run_robot.py:96-97)      */
+    /* The newest field stands in the four bytes of padding in front of the 8-byte `seed`, where a caller that zeroes the */
+    /* struct has always left 0: every older field keeps its offset and the struct its size.                             */
+    int recon_with_assign;   /* 1: with use_assign, the Chamfer loss stays and the assignment loss is added to it, as the   */
+                             /*    reference's run_real.py:175-203 / run_sapien.py:174-203 do: the searches and the Chamfer */
+                             /*    consumer run as with use_assign = 0, and that consumer adds the term of `assign_map` in   */
+                             /*    the same launch: G = fl(G_chamfer + fl(lambda_assign * fl(2 (x - y_map)))) per component, */
+                             /*    G_chamfer itself where the map holds -1 (or anything outside [0, N)).  Without use_assign */
+                             /*    it means nothing.  Sizes the workspace: fixed for an instance's life.  0: the default      */
     uint64_t seed;           /* Philox key of the Gumbel noise                            */
     int use_grid;            /* 1: exact grid search for the static targets (pc_list, flow */
                              /*    references); 0: brute force everywhere (same results)   */
@@ -358,7 +366,8 @@ typedef struct reart_relax_config {
                              /*    (exact; pays off when the clouds are stored in Morton order) */
     int use_assign;          /* 1: the assignment loss replaces the Chamfer loss (run_robot.py:164-187, */
                              /*    i >= assign_iter): lambda_assign * sum |x_src - y_assigned|^2 over   */
-                             /*    the pairs of `assign_map`                                            */
+                             /*    the pairs of `assign_map`.  With recon_with_assign (below) the term  */
+                             /*    is ADDED to the Chamfer loss instead                                 */
     float lambda_assign;     /* --lambda_assign                                           */
     float weight_decay;      /* --weight_decay: torch.optim.Adam's L2 form g += wd * p (run_robot.py:146-148) */
     /* Tuning and measurement switches.  0 = the library default everywhere.  The library reads NO environment
@@ -399,7 +408,8 @@ typedef struct reart_relax_buffers {
     float *adam_m, *adam_v;  /* [3H+H+PH+9BP] each, order W1|b1|W2|p6d|pt, start at zero   */
     int64_t *iter;           /* device scalar: completed iterations (caller initialises)  */
     float *tau;              /* device scalar: temperature of the next iteration          */
-    float *losses;           /* [ring][4]: recon, lambda*flow, total, tau; row iter%ring  */
+    float *losses;           /* [ring][4]: recon, lambda*flow, total, tau; row iter%ring.  recon is the Chamfer sum, or  */
+                             /* the assignment term (use_assign), or Chamfer + assignment term (recon_with_assign)      */
     float *pc_trans;         /* [B,N,3] forward output of the last iteration              */
     int64_t *seg_part;       /* [N] or NULL                                               */
     float *trans_list;       /* [B,P,4,4] or NULL                                         */
@@ -410,6 +420,9 @@ typedef struct reart_relax_buffers {
     /* pc_trans[b][i], or -1 when point i is not among the sampled sources (the caller refreshes it   */
     /* every assign_gap iterations from FPS + linear assignment, run_robot.py:165-178)                */
     const int *assign_map;
+    /* optional [ring]: entry iter%ring = the assignment term (lambda_assign * sum of the squared pair distances) that   */
+    /* recon_with_assign added into losses[..][0]; 0 in every other mode.  NULL: not written                            */
+    float *losses_assign;
 } reart_relax_buffers;
 
 /* Bytes of one instance's workspace; 0 for a configuration the step does not take.  What grows with the sequence: the
@@ -436,7 +449,8 @@ int reart_relax_step(const reart_relax_config *cfg, const reart_relax_buffers *b
  * (/root/reference/README.md:60, run_robot.py: one process per cano_idx) fills the chip: one instance occupies a fraction
  * of the 256 compute units and is a chain of dependent launches.  Box-pruned search paths: Chamfer + flow loss (five
  * launches), Chamfer only, and the assignment loss with or without flow (run_robot.py:164-192: the pairs in each
- * instance's assign_map); every instance in the same mode, 1 <= K <= 6.  Any other search path (use_grid,
+ * instance's assign_map), or both losses together (recon_with_assign); every instance in the same mode -- Chamfer, assignment
+ * loss, or both -- 1 <= K <= 6.  Any other search path (use_grid,
  * search_mode 1, use_boxes 0, tune_cloud): REART_ERR_UNSUPPORTED, for K = 1 as well; instances that differ in shape or
  * mode, or K out of range: REART_ERR_INVALID_ARG. */
 int reart_relax_step_batch(const reart_relax_config *cfgs, const reart_relax_buffers *bufs, void *const *workspaces,

@@ -92,6 +92,10 @@ struct StepBook {
     float *step_next;          // [4]: FinalizeAdam::step of the NEXT step
     int ring, n_iter;
     float lambda_flow, fixed_tau, end_tau, start_tau, beta1, beta2, seg_lr, trans_lr;
+    // recon_with_assign: the assignment partials (each times lambda_assign already) that go on top of frame_loss in row[0];
+    // n_assign_part = 0 in every other mode.  losses_assign: nullable [ring], the assignment term alone (0 in the other modes)
+    const double *assign_part; int n_assign_part;
+    float *losses_assign;
 };
 int reart_base_backward_launch(const BaseBwdArgs *args, const FinalizeAdam *adam, const StepBook *book, void *const *workspaces,
                                size_t workspace_bytes, int K, hipStream_t st, int force_long);     // adam / book: arrays of K, or NULL

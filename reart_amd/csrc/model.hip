@@ -1039,7 +1039,7 @@ __device__ __forceinline__ void base_bwd_finalize_book(const StepBook &bk) {
 #endif
     const long it = (long)bk.iter[0];
     const float tau_cur = bk.tau[0];
-    double recon = 0.0, flow = 0.0, bc = 1.0;
+    double recon = 0.0, flow = 0.0, ass = 0.0, bc = 1.0;
     float tau_next = 0.f;
     if (w == 0) {
         // fixed assignment of terms to lanes + fixed-order tree: deterministic sums
@@ -1047,6 +1047,11 @@ __device__ __forceinline__ void base_bwd_finalize_book(const StepBook &bk) {
         for (int i = l; i < bk.n_flow_part; i += 64) flow += bk.flow_part[i];
         recon = reart_wave_sum_d(recon);
         flow = reart_wave_sum_d(flow) * (double)bk.lambda_flow;
+        if (bk.n_assign_part > 0) {   // recon_with_assign: the assignment term on top of the Chamfer term (wave-uniform branch)
+            for (int b = l; b < bk.n_assign_part; b += 64) ass += bk.assign_part[b];
+            ass = reart_wave_sum_d(ass);
+            recon += ass;
+        }
     } else if (l == 0) {
         // Adam step count of the next iteration: it + 2
         if (w == 1) bc = 1.0 - pow((double)bk.beta1, (double)(it + 2));
@@ -1059,6 +1064,7 @@ __device__ __forceinline__ void base_bwd_finalize_book(const StepBook &bk) {
         float *row = (bk.losses && bk.ring > 0) ? bk.losses + 4 * (size_t)(it % bk.ring) : nullptr;
         if (w == 0) {
             if (row) { row[0] = (float)recon; row[1] = (float)flow; row[2] = (float)(recon + flow); }
+            if (bk.losses_assign && bk.ring > 0) bk.losses_assign[it % bk.ring] = (float)ass;
         } else if (w == 1) {
             bk.step_next[0] = (float)((double)bk.seg_lr / bc);
             bk.step_next[1] = (float)((double)bk.trans_lr / bc);
@@ -1171,6 +1177,7 @@ int reart_base_backward_launch(const BaseBwdArgs *args, const FinalizeAdam *adam
     if (rc != REART_OK) return rc;
     Batched<FinalizeAdam> adb = {};
     Batched<StepBook> bkb = {};
+    static_assert(sizeof(Batched<BaseBwdArgs>) + sizeof(adb) + sizeof(bkb) <= 3584, "kernel-argument segment");
     for (int k = 0; k < K; ++k) {
         if (adam) adb.a[k] = adam[k];
         if (book) bkb.a[k] = book[k];

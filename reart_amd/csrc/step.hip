@@ -23,7 +23,7 @@ struct StepPlan {
     int nchunk, nparams;
     size_t o_ysoa, o_xsoa, o_rsoa, o_rlen, o_qmap;
     size_t o_pd0, o_pi0, o_pd1, o_pi1, o_pd3, o_pi3;
-    size_t o_yT, o_hT, o_hard, o_rt, o_G, o_gpf, o_fx, o_floss, o_fpart, o_grads, o_bwd;
+    size_t o_yT, o_hT, o_hard, o_rt, o_G, o_gpf, o_fx, o_floss, o_apart, o_fpart, o_grads, o_bwd;
     size_t o_bc;              // Adam step sizes (FinalizeAdam::step, float[4]) in two slots: [0..3] of the coming step, read by
                               // the finalize bodies; [4..7] of the step after it, written by the bookkeeping workgroup and
                               // promoted to the first slot by the next backward block launch
@@ -97,6 +97,8 @@ static int step_plan(const reart_relax_config *c, StepPlan *p) {
     p->o_gpf = ws.take_bytes(sizeof(float) * 3 * BN);
     p->o_fx = ws.take_bytes(sizeof(double));
     p->o_floss = ws.take_bytes(sizeof(double) * (size_t)c->B * reart_div_up(c->N, CG_RANGE));
+    // recon_with_assign: the assignment partials of the Chamfer consumer's workgroups, beside their Chamfer partials
+    p->o_apart = ws.take_bytes(c->recon_with_assign ? sizeof(double) * (size_t)c->B * reart_div_up(c->N, CG_RANGE) : 0);
     p->o_fpart = ws.take_bytes(sizeof(double) * (size_t)c->B * reart_div_up(c->N, FLOW_BS));
     p->o_grads = ws.take_bytes(sizeof(float) * p->nparams);
     p->bwd_bytes = reart_base_backward_workspace_bytes(c->N, c->P, c->B, c->H);
@@ -396,6 +398,10 @@ struct CGradArgs {
     float *G;                            // [B,N,3]: d recon / d pc_trans (both directions)
     double *loss_part;                   // [B][gridDim.x]
     int *seed0, *seed1;                  // nullable [B,N]: the neighbour indices, warm start of the next search
+    // AS instantiations only (reart_relax_config.recon_with_assign): the assignment term on top of the Chamfer term
+    const int *map;                      // [B,N] index into Y[b] or -1 (AssignArgs::map)
+    double *assign_part;                 // [B][gridDim.x]: lambda * sum of the squared pair distances
+    float lambda;
 };
 // Workgroup (r, b) owns the targets x_j, j in [r*CG_RANGE, (r+1)*CG_RANGE), of frame b:
 //   1. it walks ALL observed points y_i of the frame (merging their slice partials), and adds the
@@ -431,7 +437,11 @@ __device__ __forceinline__ void merge_slices(const float *__restrict__ pd, const
     j = j < 0 ? 0 : (j >= nmax ? nmax - 1 : j);   // in range whatever the inputs (NaN clouds)
 }
 
-template <int SL>
+// AS: the assignment term of a.map is added to the Chamfer gradient of the own point before its one store, and its loss
+// term goes to a second block sum (recon_with_assign; run_real.py:175-203 of the reference adds both losses).  G is
+// fl(G_chamfer + fl(lambda * fl(2 (x - y_map)))) per component, G_chamfer the very value the !AS form stores; a map entry
+// outside [0, N) is "no pair" as in assign_grad_body.  A template parameter: the !AS forms hold no trace of it.
+template <int SL, bool AS>
 __device__ __forceinline__ void chamfer_grad_body(const CGradArgs &a, const int bx, const int b, const int nbx) {
     __shared__ unsigned long long s_acc[CG_RANGE * 3];
     __shared__ double s_red[CG_BS / REART_WAVE];
@@ -446,12 +456,21 @@ __device__ __forceinline__ void chamfer_grad_body(const CGradArgs &a, const int 
     const int io = r0 + tid, ioc = io < N ? io : N - 1;
     float d0;
     int j0;
+    int am = -1;
+    if (AS) am = a.map[ob + ioc];   // with the partial records, in the first batch of loads
     merge_slices<SL>(a.pd0, a.pi0, a.S0, stride, ob + ioc, N, d0, j0);
     const int sbits = a.fx_bits[0];
     // the gathers of the own target are issued now: they complete under the walk over the observed points
     float yn[3], xo[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) { yn[k] = y[3 * j0 + k]; xo[k] = x[3 * ioc + k]; }
+    const bool paired = AS && am >= 0 && am < N;
+    float ya[3] = {0.f, 0.f, 0.f};
+    if (AS) {   // the assigned point beside the nearest one; without a branch (no pair: point 0, unused)
+        const int amc = paired ? am : 0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) ya[k] = y[3 * amc + k];
+    }
     __syncthreads();
     float d1own = 0.f;
     constexpr int IL = 4;   // observed points in flight per thread
@@ -491,23 +510,38 @@ __device__ __forceinline__ void chamfer_grad_body(const CGradArgs &a, const int 
     }
     if (io < N && a.seed0) a.seed0[ob + io] = j0;
     __syncthreads();
-    double term = 0.0;
+    double term = 0.0, aterm = 0.0;
     if (io < N) {
         term = (double)(d0 + d1own);  // chamfer_forward + chamfer_backward (utils/chamfer.py:119-123)
         const double inv2 = 2.0 * exp2((double)-sbits);
         float *G = a.G + 3 * (ob + io);
+        float sq = 0.f;
 #pragma unroll
-        for (int k = 0; k < 3; ++k)
-            G[k] = 2.0f * (xo[k] - yn[k]) + (float)((double)(long long)s_acc[3 * tid + k] * inv2);
+        for (int k = 0; k < 3; ++k) {
+            const float gc = 2.0f * (xo[k] - yn[k]) + (float)((double)(long long)s_acc[3 * tid + k] * inv2);
+            if (AS && paired) {   // assign_grad_body's term, operation for operation
+                const float d = xo[k] - ya[k];
+                sq += d * d;
+                G[k] = gc + a.lambda * (2.0f * d);
+            } else {
+                G[k] = gc;
+            }
+        }
+        if (AS && paired) aterm = (double)sq;
     }
     term = reart_block_sum_d<CG_BS>(term, s_red);
     if (tid == 0) a.loss_part[(size_t)b * nbx + bx] = term;
+    if (AS) {
+        __syncthreads();   // s_red is read by thread 0 of the first sum
+        aterm = reart_block_sum_d<CG_BS>(aterm, s_red);
+        if (tid == 0) a.assign_part[(size_t)b * nbx + bx] = aterm * (double)a.lambda;
+    }
 }
 
 // the stand-alone consumers; BATCH: K instances in one launch, instance k on the grid's plane z = k
-template <int SL, bool BATCH>
+template <int SL, bool BATCH, bool AS>
 __global__ __launch_bounds__(CG_BS) void chamfer_grad_kernel(Batched<CGradArgs> ab) {
-    chamfer_grad_body<SL>(ab.a[BATCH ? blockIdx.z : 0], blockIdx.x, blockIdx.y, gridDim.x);
+    chamfer_grad_body<SL, AS>(ab.a[BATCH ? blockIdx.z : 0], blockIdx.x, blockIdx.y, gridDim.x);
 }
 template <int SL, bool BATCH>
 __global__ __launch_bounds__(FLOW_BS) void flow_blend_kernel(Batched<FlowArgs> ab) {
@@ -609,7 +643,7 @@ extern "C" int reart_debug_post_clock(unsigned long long *out) {
 #define POST_TS(k) do { } while (0)
 #endif
 // Only the merged (pruned) step launches it, and that step's searches leave ONE record per query: the single-record forms
-template <bool BATCH>
+template <bool BATCH, bool AS>
 __global__ __launch_bounds__(CG_BS) void post_kernel(Batched<PostArgs> ab) {
     const PostArgs &a = ab.a[BATCH ? blockIdx.y : 0];
     const int w = blockIdx.x;
@@ -620,7 +654,7 @@ __global__ __launch_bounds__(CG_BS) void post_kernel(Batched<PostArgs> ab) {
         if (w == 1) POST_TS(1);
     } else if (w < a.nwork) {
         if (w == a.nflow + 1) POST_TS(2);
-        chamfer_grad_body<1>(a.cg, (w - a.nflow) % a.ncx, (w - a.nflow) / a.ncx, a.ncx);
+        chamfer_grad_body<1, AS>(a.cg, (w - a.nflow) % a.ncx, (w - a.nflow) / a.ncx, a.ncx);
         if (w == a.nflow + 1) POST_TS(3);
     } else if (w < a.nwork + a.norder) {
         if (w == a.nwork) POST_TS(4);
@@ -689,6 +723,7 @@ struct StepGeom {
     int fl_sl, cg_sl;          // partial lists per query that consumer's instantiation serves: 1 | 4 (up to four) | 0 (any number)
     int fgx, fgy, ncg, post_blocks, N, B;
     int long_model;              // tune_long: the model's long path also where the pose table fits in LDS
+    int cg_assign;               // recon_with_assign in force: the Chamfer consumer (stand-alone or merged) adds the assignment term
 };
 // One instance's iteration as data: the argument block of every launch and the geometry of the launches.  step_describe
 // fills it, step_launch launches it -- for one instance, or for K of equal geometry at once.
@@ -769,7 +804,10 @@ static int step_describe(const reart_relax_config *cfg, const reart_relax_buffer
         k3.job[1] = kj;
         k3.items0 = B * nqg * p.S3; k3.items = k3.items0;
     }
-    const bool chamfer = !c.use_assign;
+    // recon_with_assign: the assignment term is ADDED to the Chamfer term (by the Chamfer consumer), not put in its place
+    const bool both = c.use_assign && c.recon_with_assign;
+    const bool chamfer = !c.use_assign || both;
+    g.cg_assign = both ? 1 : 0;
     // merged: Chamfer + flow on the pruned path -- ONE search launch, ONE consumer launch
     const bool merged = p.pruned && c.use_flow && chamfer;
     g.merged = merged ? 1 : 0;
@@ -836,7 +874,7 @@ static int step_describe(const reart_relax_config *cfg, const reart_relax_buffer
         g.has_fl = merged ? 0 : 1; g.fl_sl = fl.S == 1 ? 1 : (fl.S <= 4 ? 4 : 0);
     }
     g.ncg = reart_div_up(N, CG_RANGE);
-    if (c.use_assign) {
+    if (!chamfer) {
         // assignment loss instead of the Chamfer loss: no search, the pairs come from the caller's assign_map
         AssignArgs &aa = L.aa;
         aa.X = bufs->pc_trans; aa.Y = bufs->pc_list; aa.map = bufs->assign_map; aa.N = N; aa.B = B;
@@ -851,6 +889,7 @@ static int step_describe(const reart_relax_config *cfg, const reart_relax_buffer
         cg.fx_bits = (const int *)(ws + p.o_fx);
         cg.N = N; cg.B = B; cg.S0 = S0; cg.S1 = p.S1; cg.G = G;
         cg.loss_part = (double *)(ws + p.o_floss);
+        if (both) { cg.map = bufs->assign_map; cg.lambda = c.lambda_assign; cg.assign_part = (double *)(ws + p.o_apart); }
         g.has_cg = merged ? 0 : 1; g.cg_sl = (cg.S0 == 1 && cg.S1 == 1) ? 1 : ((cg.S0 <= 4 && cg.S1 <= 4) ? 4 : 0);
         if (merged) {
             PostArgs &pa = L.pa;
@@ -896,6 +935,8 @@ static int step_describe(const reart_relax_config *cfg, const reart_relax_buffer
     StepBook &bk = L.bk;
     bk.enabled = 1; bk.frame_loss = (const double *)(ws + p.o_floss); bk.n_frame_part = B * g.ncg;
     bk.flow_part = (const double *)(ws + p.o_fpart); bk.n_flow_part = nfp;
+    bk.assign_part = both ? (const double *)(ws + p.o_apart) : nullptr; bk.n_assign_part = both ? B * g.ncg : 0;
+    bk.losses_assign = bufs->losses_assign;
     bk.iter = bufs->iter; bk.tau = bufs->tau; bk.losses = bufs->losses; bk.step_next = (float *)(ws + p.o_bc) + 4;
     bk.ring = c.ring; bk.n_iter = c.n_iter; bk.lambda_flow = c.lambda_flow; bk.fixed_tau = c.fixed_tau;
     bk.end_tau = c.end_tau; bk.start_tau = c.start_tau; bk.beta1 = c.beta1; bk.beta2 = c.beta2;
@@ -971,7 +1012,8 @@ static int step_launch(const StepLaunch *L, int K, hipStream_t st, hipEvent_t *e
     if (forked && hipEventRecord((hipEvent_t)L[0].ev_join, fst) != hipSuccess) return REART_ERR_LAUNCH;
     MARK(3);
     if (g.has_aa) {
-        // 4. assignment loss instead of the Chamfer loss: no search, the pairs come from the caller's assign_map
+        // 4. assignment loss instead of the Chamfer loss: no search, the pairs come from the caller's assign_map (with
+        // recon_with_assign the pairs are the Chamfer consumer's business, below)
         MARK(4);
         const dim3 ag(reart_div_up(g.N, CG_BS), g.B, K);
         const Batched<AssignArgs> ab = gather(L, K, &StepLaunch::aa);
@@ -992,15 +1034,24 @@ static int step_launch(const StepLaunch *L, int K, hipStream_t st, hipEvent_t *e
         // merge + recon loss + direct gradient term + fixed-point scatter; merged: with the flow consumer in one launch
         if (g.merged) {
             const Batched<PostArgs> pb = gather(L, K, &StepLaunch::pa);
-            if (K > 1) hipLaunchKernelGGL((post_kernel<true>), dim3(g.post_blocks, K), dim3(CG_BS), 0, st, pb);
-            else hipLaunchKernelGGL((post_kernel<false>), dim3(g.post_blocks), dim3(CG_BS), 0, st, pb);
+            static_assert(sizeof(Batched<PostArgs>) <= 3584, "kernel-argument segment");
+            if (g.cg_assign) {
+                if (K > 1) hipLaunchKernelGGL((post_kernel<true, true>), dim3(g.post_blocks, K), dim3(CG_BS), 0, st, pb);
+                else hipLaunchKernelGGL((post_kernel<false, true>), dim3(g.post_blocks), dim3(CG_BS), 0, st, pb);
+            } else if (K > 1) hipLaunchKernelGGL((post_kernel<true, false>), dim3(g.post_blocks, K), dim3(CG_BS), 0, st, pb);
+            else hipLaunchKernelGGL((post_kernel<false, false>), dim3(g.post_blocks), dim3(CG_BS), 0, st, pb);
         } else {
             const dim3 cgd(g.ncg, g.B, K);
             const Batched<CGradArgs> cb = gather(L, K, &StepLaunch::cg);
-            if (K > 1) hipLaunchKernelGGL((chamfer_grad_kernel<1, true>), cgd, dim3(CG_BS), 0, st, cb);
-            else if (g.cg_sl == 1) hipLaunchKernelGGL((chamfer_grad_kernel<1, false>), cgd, dim3(CG_BS), 0, st, cb);
-            else if (g.cg_sl) hipLaunchKernelGGL((chamfer_grad_kernel<4, false>), cgd, dim3(CG_BS), 0, st, cb);
-            else hipLaunchKernelGGL((chamfer_grad_kernel<0, false>), cgd, dim3(CG_BS), 0, st, cb);
+            if (g.cg_assign) {
+                if (K > 1) hipLaunchKernelGGL((chamfer_grad_kernel<1, true, true>), cgd, dim3(CG_BS), 0, st, cb);
+                else if (g.cg_sl == 1) hipLaunchKernelGGL((chamfer_grad_kernel<1, false, true>), cgd, dim3(CG_BS), 0, st, cb);
+                else if (g.cg_sl) hipLaunchKernelGGL((chamfer_grad_kernel<4, false, true>), cgd, dim3(CG_BS), 0, st, cb);
+                else hipLaunchKernelGGL((chamfer_grad_kernel<0, false, true>), cgd, dim3(CG_BS), 0, st, cb);
+            } else if (K > 1) hipLaunchKernelGGL((chamfer_grad_kernel<1, true, false>), cgd, dim3(CG_BS), 0, st, cb);
+            else if (g.cg_sl == 1) hipLaunchKernelGGL((chamfer_grad_kernel<1, false, false>), cgd, dim3(CG_BS), 0, st, cb);
+            else if (g.cg_sl) hipLaunchKernelGGL((chamfer_grad_kernel<4, false, false>), cgd, dim3(CG_BS), 0, st, cb);
+            else hipLaunchKernelGGL((chamfer_grad_kernel<0, false, false>), cgd, dim3(CG_BS), 0, st, cb);
         }
     }
     REART_CHECK_LAUNCH();
@@ -1038,7 +1089,7 @@ extern "C" int reart_relax_step(const reart_relax_config *cfg, const reart_relax
 // over canonical frames (README.md:60) fills it this way instead of with K streams that the hardware queues interleave
 // as they please.  Each instance computes exactly what reart_relax_step computes for it.  Box-pruned search paths: the
 // merged Chamfer + flow iteration, Chamfer only, and the assignment loss with or without flow (the second phase of the
-// README recipe, run_robot.py:164-192); K <= 6.  What K instances cannot share is refused for K = 1 as well.
+// README recipe, run_robot.py:164-192), and Chamfer + assignment loss together (recon_with_assign); K <= 6.  What K instances cannot share is refused for K = 1 as well.
 extern "C" int reart_relax_step_batch(const reart_relax_config *cfgs, const reart_relax_buffers *bufs, void *const *workspaces,
                                       size_t workspace_bytes, int K, void *stream) {
     if (!cfgs || !bufs || !workspaces || K < 1 || K > REART_BATCH_MAX) return REART_ERR_INVALID_ARG;

@@ -16,7 +16,8 @@ class RelaxConfig(ctypes.Structure):
     _fields_ = [(n, c_int) for n in ("N", "P", "B", "H", "cano_idx", "use_flow", "robust", "euclidean", "flow_k",
                                      "M_max", "M_total", "n_iter", "ring")] + \
                [(n, c_float) for n in ("lambda_flow", "smooth_weight", "trans_lr", "seg_lr", "beta1", "beta2", "eps",
-                                       "start_tau", "end_tau", "fixed_tau")] + [("seed", ctypes.c_uint64),
+                                       "start_tau", "end_tau", "fixed_tau")] + [("recon_with_assign", c_int),   # in the padding in front of `seed`
+                                                                                 ("seed", ctypes.c_uint64),
                                                                                  ("use_grid", c_int), ("use_boxes", c_int),
                                                                                  ("use_assign", c_int), ("lambda_assign", c_float),
                                                                                  ("weight_decay", c_float)] + \
@@ -57,7 +58,8 @@ def tuning_from_env(env=None):
 class RelaxBuffers(ctypes.Structure):
     _fields_ = [(n, c_void_p) for n in ("cano", "pc_list", "ref_loc", "ref_flow", "ref_off", "gumbel", "W1", "b1", "W2",
                                         "p6d", "pt", "adam_m", "adam_v", "iter", "tau", "losses", "pc_trans",
-                                        "seg_part", "trans_list", "aux_stream", "ev_fork", "ev_join", "assign_map")]
+                                        "seg_part", "trans_list", "aux_stream", "ev_fork", "ev_join", "assign_map",
+                                        "losses_assign")]
 
 
 def morton_order(points):
@@ -146,12 +148,18 @@ class RelaxEngine:
     parameters are optimised IN PLACE; ``pc_ref_list`` / ``flow_ref_list`` are the ragged flow
     references of run_robot.py:81-84 (lists of [M_i,3] tensors) or None for Chamfer only.
     Hyper-parameters carry the reference's flag names and defaults (run_robot.py:362-420).
+
+    ``recon_with_assign=True`` (fixed for the engine's life: the workspace is sized with it): ``set_assignment`` ADDS the
+    assignment loss to the Chamfer loss instead of putting it in its place -- the objective of the reference's
+    run_real.py:175-203 and run_sapien.py:174-203.  Until ``set_assignment`` is called, and after ``clear_assignment``,
+    such an engine is a Chamfer engine like any other.
     """
 
     def __init__(self, cano_pc, pc_list, model, cano_idx, pc_ref_list=None, flow_ref_list=None, n_iter=15000,
                  start_tau=5.0, end_tau=1.0, trans_lr=1e-2, seg_lr=1e-3, lambda_flow=1.0, use_robust_loss=False,
                  smooth_weight=1e-2, fixed_tau=0.0, seed=2, ring=1024, knn_squared=False, start_iter=0, use_grid=False,
-                 overlap_flow=True, spatial_sort=True, weight_decay=0.0, profile=False, tuning=None):
+                 overlap_flow=True, spatial_sort=True, weight_decay=0.0, profile=False, tuning=None,
+                 recon_with_assign=False):
         _lib.require_gpu(cano_pc, pc_list)
         dev = cano_pc.device
         self.device, self.model = dev, model
@@ -189,6 +197,7 @@ class RelaxEngine:
         self.tau = torch.zeros(1, device=dev)
         self.ring = ring
         self.losses = torch.zeros((ring, 4), device=dev)
+        self.losses_assign = torch.zeros((ring,), device=dev)
         self._pc_trans = torch.empty((B, N, 3), device=dev)
         self._assign_map = torch.full((B, N), -1, dtype=torch.int32, device=dev)
         self._seg_part = torch.empty((N,), dtype=torch.int64, device=dev)
@@ -212,7 +221,8 @@ class RelaxEngine:
                                smooth_weight=smooth_weight, trans_lr=trans_lr, seg_lr=seg_lr, beta1=0.9, beta2=0.999,
                                eps=1e-8, start_tau=start_tau, end_tau=end_tau, fixed_tau=fixed_tau, seed=seed,
                                use_grid=int(bool(use_grid)), use_boxes=int(bool(spatial_sort)),
-                               weight_decay=float(weight_decay), profile=int(bool(profile)))
+                               weight_decay=float(weight_decay), profile=int(bool(profile)),
+                               recon_with_assign=int(bool(recon_with_assign)))
         for k, v in (tuning_from_env() if tuning is None else tuning).items():
             setattr(self.cfg, k, int(v))
         L = _lib_fns()
@@ -247,7 +257,7 @@ class RelaxEngine:
                                   aux_stream=None if self._aux is None else self._aux.cuda_stream,
                                   ev_fork=None if self._aux is None else self._ev[0].cuda_event,
                                   ev_join=None if self._aux is None else self._ev[1].cuda_event,
-                                  assign_map=v(self._assign_map))
+                                  assign_map=v(self._assign_map), losses_assign=v(self.losses_assign))
 
     @property
     def pc_trans(self):
@@ -289,7 +299,8 @@ class RelaxEngine:
     def set_assignment(self, src_idx, tgt_idx, lambda_assign):
         """Switch to the assignment loss ``lambda_assign * sum |pc_trans[b, src_idx[r]] - pc_list[b, tgt_idx[b, r]]|^2``.
         src_idx [n] (indices into the canonical cloud), tgt_idx [B,n] (indices into pc_list[b]), both in the
-        caller's point order.  A captured graph is dropped when the mode changes (capture again)."""
+        caller's point order.  A captured graph is dropped when the mode changes (capture again).  On an engine built with
+        ``recon_with_assign`` the term is added to the Chamfer loss instead of replacing it."""
         B, N = self._assign_map.shape
         src = src_idx.to(self.device).long().reshape(-1)
         tgt = tgt_idx.to(self.device).long().reshape(B, -1)
@@ -364,7 +375,10 @@ class RelaxEngine:
                 "workgroup_seconds": float(out[4])}
 
     def loss_log(self):
-        """(iterations done, tensor [min(iter, ring), 4]: recon, lambda*flow, total, tau); syncs."""
+        """(iterations done, tensor [min(iter, ring), 4]: recon, lambda*flow, total, tau); syncs.  ``recon`` is the loss the
+        mode puts beside the flow loss: the Chamfer sum, the assignment term after ``set_assignment``, or -- on a
+        ``recon_with_assign`` engine after ``set_assignment`` -- Chamfer sum + assignment term (the assignment term alone:
+        ``assign_loss_log``), so that ``total`` is the reference's "total Loss" in every mode."""
         it = int(self.iter.item())
         rows = self.losses[: min(it, self.ring)] if it <= self.ring else torch.roll(self.losses, -(it % self.ring), 0)
         return it, rows.clone()
@@ -372,6 +386,19 @@ class RelaxEngine:
     def last_losses(self):
         it = int(self.iter.item())
         return self.losses[(it - 1) % self.ring].clone()
+
+    def assign_loss_log(self):
+        """(iterations done, tensor [min(iter, ring)]): the assignment term that a ``recon_with_assign`` engine added into
+        column 0 of ``loss_log`` (lambda_assign * sum of the squared pair distances), 0 for every iteration of any other
+        mode; syncs."""
+        it = int(self.iter.item())
+        la = self.losses_assign
+        rows = la[: min(it, self.ring)] if it <= self.ring else torch.roll(la, -(it % self.ring), 0)
+        return it, rows.clone()
+
+    def last_assign_loss(self):
+        it = int(self.iter.item())
+        return self.losses_assign[(it - 1) % self.ring].clone()
 
 
 class RelaxBatch:
@@ -381,11 +408,14 @@ class RelaxBatch:
     The engines keep their own state; read results from them as usual."""
 
     MAX = 6
+    MODE_ERROR = "RelaxBatch: the engines must be in the same loss mode (all Chamfer, all assignment loss, or all both)"
 
     def __init__(self, engines):
         engines = list(engines)
         if not 1 <= len(engines) <= self.MAX:
             raise ValueError(f"RelaxBatch takes 1..{self.MAX} engines")
+        if len({e.cfg.recon_with_assign for e in engines}) != 1:
+            raise RuntimeError(self.MODE_ERROR)
         nb = {e.workspace.numel() for e in engines}
         if len(nb) != 1:
             raise ValueError("RelaxBatch: the engines must share one shape")
@@ -405,6 +435,7 @@ class RelaxBatch:
 
     # shape and switch fields of reart_relax_config that every engine of a batch must share
     SAME = ("N", "P", "B", "H", "M_max", "use_flow", "robust", "euclidean", "flow_k", "use_grid", "use_boxes", "use_assign",
+            "recon_with_assign",
             "search_mode", "tune_slices", "tune_slices_flow", "tune_sparse", "tune_fwd_pts", "tune_bwd_pts", "tune_reorder",
             "tune_cloud", "tune_xcd", "tune_share", "tune_long")
 
@@ -418,8 +449,8 @@ class RelaxBatch:
         self._ws = (c_void_p * K)(*[e.workspace.data_ptr() for e in self.engines])
 
     def _enqueue(self):
-        if len({(e.cfg.use_assign, e.cfg.use_flow) for e in self.engines}) != 1:
-            raise RuntimeError("RelaxBatch: the engines must be in the same loss mode (all Chamfer or all assignment loss)")
+        if len({(e.cfg.use_assign, e.cfg.use_flow, e.cfg.recon_with_assign) for e in self.engines}) != 1:
+            raise RuntimeError(self.MODE_ERROR)
         self._refresh()
         rc = _lib_fns().reart_relax_step_batch(self._cfgs, self._bufs, self._ws, self._nbytes, len(self.engines), _lib.stream())
         _lib.check(rc, "reart_relax_step_batch")
@@ -438,7 +469,7 @@ class RelaxBatch:
 
     def _mode(self):
         """What a captured graph has baked in besides the buffers: the loss mode of every engine."""
-        return tuple((e.cfg.use_assign, e.cfg.use_flow, e.cfg.lambda_assign) for e in self.engines)
+        return tuple((e.cfg.use_assign, e.cfg.use_flow, e.cfg.lambda_assign, e.cfg.recon_with_assign) for e in self.engines)
 
     def step(self, n=1):
         """n iterations of every engine (asynchronous)."""

@@ -10,6 +10,8 @@ What is built: the loop itself.
   * ``--model base`` with ``--use_assign_loss`` after ``--assign_iter``: the same engine in its
     assignment-loss mode; every ``--assign_gap`` iterations the host refreshes the pairs (forward of the
     coming iteration, FPS, cost matrices, GPU linear assignment), in between the engine runs alone.
+    With ``--recon_with_assign`` (off by default) the assignment loss is added to the Chamfer loss instead of taking
+    its place, as the reference's ``run_real.py:175-203`` does; ``--model kinematic`` then runs through ``OperatorLoop``.
   * ``--model kinematic``: the reference's own loop structure with
     the HIP operators underneath (``BaseModel`` / ``KinematicModel``, ``ChamferDistance``,
     ``blend_anchor_motion``, ``flow_loss``, FPS) and ``torch.optim.Adam``; the linear assignment of the
@@ -452,6 +454,10 @@ class OperatorLoop:
             ass = args.lambda_assign * ((pc_src - self.matched) ** 2).sum(-1).sum()
             losses["opt assignment loss"] = ass
             loss = loss + ass
+            if getattr(args, "recon_with_assign", False):   # run_real.py:175-203: the Chamfer loss in every iteration
+                rec = recon_loss(pc_trans_list, pc_list, self.chamfer_dist)
+                losses["recon Loss"] = rec
+                loss = loss + rec
         else:
             rec = recon_loss(pc_trans_list, pc_list, self.chamfer_dist)
             losses["recon Loss"] = rec
@@ -488,7 +494,9 @@ def make_projection_loop(args, model, cano_pc, pc_list, pc_ref_list=None, flow_r
     ``assign_iter``, runs without ``--use_assign_loss``), mixed joint types and root motion (the SAPIEN / real-scan variant of
     the model, networks/model.py:113-166); the base model outside the fused engine goes through ``OperatorLoop`` (PyTorch
     autograd + torch.optim.Adam over the same operators), which also remains the engine's reference in the tests."""
-    if args.model == "kinematic":
+    # --recon_with_assign: KinematicEngine has no mode that adds the Chamfer loss to the assignment loss yet (its Chamfer
+    # branch is a composition of operators of its own): the operator loop computes that objective until it has
+    if args.model == "kinematic" and not getattr(args, "recon_with_assign", False):
         from reart_amd.kinematic_engine import KinematicEngine
 
         return KinematicEngine(model, cano_pc, pc_list, args.cano_idx, pc_ref_list if args.use_flow_loss else None,
@@ -710,7 +718,8 @@ def main(args):
         eng = RelaxEngine(cano_pc, pc_list, model, args.cano_idx, pc_ref_list, flow_ref_list, n_iter=args.n_iter,
                           start_tau=args.start_tau, end_tau=args.end_tau, trans_lr=args.trans_lr, seg_lr=args.seg_lr,
                           lambda_flow=args.lambda_flow, use_robust_loss=args.use_robust_loss, fixed_tau=fixed_tau,
-                          seed=args.manual_seed, weight_decay=args.weight_decay)
+                          seed=args.manual_seed, weight_decay=args.weight_decay,
+                          recon_with_assign=bool(getattr(args, "recon_with_assign", False)))
         if fused_until > 0:
             i += eng.capture()
         while i < fused_until:
@@ -725,6 +734,10 @@ def main(args):
 
             def on_snapshot(k):
                 row = eng.last_losses().cpu().numpy()
+                if eng.cfg.recon_with_assign:     # row[0] holds both terms (RelaxEngine.loss_log)
+                    ass = float(eng.last_assign_loss().cpu())
+                    snapshot(k - 1, {"recon Loss": row[0] - ass, "opt assignment loss": ass, "flow Loss": row[1], "total Loss": row[2]})
+                    return
                 snapshot(k - 1, {"opt assignment loss": row[0], "flow Loss": row[1], "total Loss": row[2]})
 
             i = phase.run(i, n_iter, args.snapshot_gap, on_snapshot)
@@ -869,6 +882,11 @@ def build_parser():
     p.add_argument("--fused_ik", action="store_true",
                    help="retarget error of a kinematic model: fit all novel poses in one launch (kinematic_utils.ik_batch) instead of "
                         "one Adam loop per pose; same optimum, not bit-equal to the default")
+    p.add_argument("--recon_with_assign", action="store_true",
+                   help="with --use_assign_loss: from --assign_iter on the assignment loss is ADDED to the Chamfer loss instead of "
+                        "taking its place, as the reference's run_real.py:175 and run_sapien.py:174 do (recon Loss in every "
+                        "iteration); the fused engine runs both in its Chamfer consumer, --model kinematic goes through the "
+                        "operator loop")
     p.add_argument("--fused_losses", action="store_true",
                    help="operator loop (the base model outside the fused engine): the Chamfer term as one warm-started call with a "
                         "fused backward, the T-1 flow blends as one call; same losses up to the summation order of the Chamfer sum")

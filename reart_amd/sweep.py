@@ -636,6 +636,9 @@ def build_cli():
                    help="(default) assignment refreshes settle tied optima canonically (run_robot.py --deterministic): a sweep repeats run to run")
     p.add_argument("--no_deterministic", dest="deterministic", action="store_false")
     p.add_argument("--fused_ik", action="store_true", help="--project: run_robot.py --fused_ik, the retarget error in one launch")
+    p.add_argument("--recon_with_assign", action="store_true",
+                   help="run_robot.py --recon_with_assign: from --assign_iter on the assignment loss is added to the Chamfer loss "
+                        "(the reference's run_real.py:175), in the engines and in the projections")
     return p
 
 
@@ -672,7 +675,8 @@ def _engine_factory(args, device, samples):
         samples[spec["id"]] = sample
         return RelaxEngine(cano, pcs, model, spec["cano_idx"], refs, flows, n_iter=args.n_iter, start_tau=args.start_tau,
                            end_tau=args.end_tau, trans_lr=args.trans_lr, seg_lr=args.seg_lr, lambda_flow=args.lambda_flow,
-                           use_robust_loss=args.use_robust_loss, seed=args.manual_seed, weight_decay=args.weight_decay)
+                           use_robust_loss=args.use_robust_loss, seed=args.manual_seed, weight_decay=args.weight_decay,
+                           recon_with_assign=bool(getattr(args, "recon_with_assign", False)))
 
     return make_engine
 
@@ -726,6 +730,7 @@ def projection_args(args, spec):
     kin.assign_iter, kin.assign_gap, kin.downsample = 0, int(args.project_assign_gap), int(args.project_downsample)
     kin.save_root = args.save_root
     kin.fused_ik = bool(getattr(args, "fused_ik", False))
+    kin.recon_with_assign = bool(getattr(args, "recon_with_assign", False))
     kin.synthetic = spec.get("synthetic") is not None
     if kin.synthetic:
         kin.synthetic_frames = int(spec["frames"])
