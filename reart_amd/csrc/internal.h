@@ -145,25 +145,30 @@ struct SoaArgs {
     SoaJob job[2];
 };
 
+// The members a search wave of prune.hip needs come first and are contiguous (q ... tlen, 88 bytes: SearchHot in prune.hip mirrors
+// them): the search kernel picks its job at run time and fetches that run in one batch of wide scalar loads at its entry, instead of
+// member by member where each is first used.
 struct KnnJob {
     const float *q;        // [N,P1,3] AoS queries
-    const float *tsoa;     // [N,3,Ppad] SoA targets
-    const int64_t *lenq;   // nullable, rows >= lenq[n] produce zeros
-    const int64_t *lent;   // nullable, number of valid targets
     const float *q_alt;    // fused step: query cloud used where qmap[b] < 0
-    const int *qmap;       // nullable per-batch query frame index into q
-    const int *tlen;       // nullable per-batch target count (ragged SoA rows, stride Ppad)
+    const float *tsoa;     // [N,3,Ppad] SoA targets
     const float *boxes;    // nullable [N][Ppad/NN_BOX][8]: AABB (lo xyz, hi xyz, pad) of every NN_BOX targets
     const int *seed;       // pruned search only: [N][P1][KK] candidate neighbour indices (warm start); K = 1: may alias pi
-    const int *border;     // pruned search only, nullable: [N * nqg] (batch, query group) pair = b * nqg + g handled at
-                           // launch position k.  Position k runs on XCD k / ceil(G/8); inside an XCD's chunk heavy pairs
-                           // come first (the items of a launch are dealt in order, late heavy items make a long tail)
-    unsigned int *cost;    // pruned search only, nullable: [N * nqg] work done for the pair at each launch position
-                           // (boxes tested and scanned, all waves), input of the next launch's order
-    int P1, P2, Ppad, L;   // Ppad = S*L, L % NN_UB == 0
-    int nqg;               // ceil(P1/64)
     float *pd;             // partial dists [S][N][P1][KK]   (S > 1)
     int *pi;               // partial idx   [S][N][P1][KK]
+    unsigned int *cost;    // pruned search only, nullable: [N * nqg] work done for the pair at each launch position
+                           // (boxes tested and scanned, all waves), input of the next launch's order
+    int P1, Ppad;          // Ppad = S*L, L % NN_UB == 0
+    int nqg;               // ceil(P1/64)
+    int P2;
+    const int *tlen;       // nullable per-batch target count (ragged SoA rows, stride Ppad)
+    // ---- not read by a search wave whose launch has item words (SearchArgs::item)
+    const int *qmap;       // nullable per-batch query frame index into q
+    int L;
+    const int64_t *lenq;   // nullable, rows >= lenq[n] produce zeros
+    const int64_t *lent;   // nullable, number of valid targets
+    const int *border;     // pruned search only, nullable: [N * nqg] (batch, query group) pair = b * nqg + g handled at
+                           // launch position k (launches without item words; with them the word holds the pair)
     float *dists;          // final [N,P1,K]
     int64_t *idx;          // final [N,P1,K]
 };
@@ -192,25 +197,46 @@ int reart_knn_anyd_run(const T *q, const T *t, const int64_t *lenq, const int64_
 #define NN_BOX 16   // targets per bounding box of the block-skip test (16, 32 or 64; measured 4545 / 4438 / 4321 it/s)
 #endif
 int reart_boxes_launch(const float *soa, int N, int Ppad, float *boxes, hipStream_t st);
+// One launch position of a search job as ONE word, written by whoever lays the order down (relax_init_kernel; the counting
+// sort of post_kernel moves the words as they are): the (batch, query group) pair that runs there in the low bits and the
+// batch's query frame -- qmap[b], or b where the job has no map -- above them, plus one so that -1 (q_alt) is 0.  A search
+// workgroup then has its query cloud after one load instead of border[pos] followed by qmap[b].  (A 16-byte record that
+// also held the batch's target count was the first design; the step's workspace has 4 bytes per position and its size is
+// part of the library's contract, and the count is a scalar load of tlen[b] that travels beside the query and the seeds.)
+#define SEARCH_ITEM_PAIR_BITS 21
+#define SEARCH_ITEM_PAIR_MASK ((1u << SEARCH_ITEM_PAIR_BITS) - 1u)
+#if defined(__HIPCC__)
+#define REART_HD __host__ __device__
+#else
+#define REART_HD
+#endif
+REART_HD static inline bool reart_search_items_fit(long pairs, int frames) {   // else: border / qmap (KnnJob), as the stand-alone operators
+    return pairs <= (long)SEARCH_ITEM_PAIR_MASK && frames + 1 < (1 << (32 - SEARCH_ITEM_PAIR_BITS));
+}
+REART_HD static inline unsigned int reart_search_item(int pair, int qb) { return (unsigned int)pair | ((unsigned int)(qb + 1) << SEARCH_ITEM_PAIR_BITS); }
 // exact search with box pruning + warm start (prune.hip): ONE launch for up to two K = 1 jobs (the Chamfer
-// directions) and one K = 3 job (the flow search); one workgroup per (job, batch, query group), S waves each
+// directions) and one K = 3 job (the flow search); one workgroup per (job, batch, query group), S waves each.
+// The words that pick a workgroup's item and its record come first (one scalar load), the jobs behind them.
 struct SearchArgs {
-    KnnJob k1[2]; int n1;          // K = 1 jobs (0, 1 or 2); results pd / pi [B][P1] (pi int32: also the next seed)
-    KnnJob k3;    int n3;          // K = 3 job (0 or 1); results pd / pi [B][P1][3]: the three best 8-target BLOCKS
-                                   // (block minimum, first index), rescanned with the exact key by the consumer
+    int n1, n3;                    // K = 1 jobs k1[0 .. n1) (0, 1 or 2: the Chamfer directions) and K = 3 job k3 (0 or 1: the flow search)
     int G;                         // (batch, query group) pairs per job = B * nqg (the same for every job)
     int per;                       // pairs per XCD chunk = ceil(G / 8) (set by the launcher)
     int S1, S3;                    // waves per workgroup of a K = 1 / K = 3 item (1..4)
-    int sparse;                    // boxes needed by <= sparse queries of a wave go through the (query, box) queue (0: dense only)
-    int share;                     // 1: every lane's bound also takes the seeds of the 15 other lanes of its row (neighbour seeds)
     int interleave;                // 0: XCD x runs the positions [x*per, (x+1)*per) (a run of frames per L2); 1: positions
                                    // x, x+8, ... (every XCD sees every frame: balanced whatever the frames cost)
+    int sparse;                    // boxes needed by <= sparse queries of a wave go through the (query, box) queue (0: dense only)
+    const unsigned int *item;      // nullable: [3][G] item words (reart_search_item) by launch position, row j for k1[j], row 2 for
+                                   // k3.  NULL: the item comes from the job's border / qmap (the stand-alone warm operators)
+    unsigned long long *prof;      // nullable: [grid][2] wall-clock stamps of every workgroup (start, end)
+    unsigned int *prof_pairs;      //           [grid] distance evaluations executed by the workgroup
+    int share;                     // 1: every lane's bound also takes the seeds of the 15 other lanes of its row (neighbour seeds)
     int cloud_resident;            // 1: when the target clouds fit in LDS, one workgroup of 16 waves per (job, batch, 16
                                    // query groups) with the cloud copied into LDS (knn_cloud_kernel); S1 / S3 then unused
     int cloud_slices;              // cloud-resident form: box slices per query group, 1 | 2 | 4 | 8 (0: the default, 4)
     int k_nqg;                     // query groups per batch (set by the launcher)
-    unsigned long long *prof;      // nullable: [grid][2] wall-clock stamps of every workgroup (start, end)
-    unsigned int *prof_pairs;      //           [grid] distance evaluations executed by the workgroup
+    KnnJob k1[2];                  // K = 1 jobs; results pd / pi [B][P1] (pi int32: also the next seed)
+    KnnJob k3;                     // K = 3 job; results pd / pi [B][P1][3]: the three best 8-target BLOCKS
+                                   // (block minimum, first index), rescanned with the exact key by the consumer
 };
 int reart_search_launch(const SearchArgs &a, hipStream_t st);
 int reart_search_launch_batch(const SearchArgs *a, int K, hipStream_t st);          // group form only, same shapes

@@ -39,6 +39,20 @@
 // XCD -- `interleave = 0`, tune_xcd -- was measured slower: frames differ 10x in work), heaviest pairs first (counting
 // sort of last iteration's work counts, step.hip).
 //
+//   * The head of a search workgroup (knn_group_kernel; read off the emitted gfx950 code, hipcc -S).  Entry: the words that
+//     pick the item (n1 ... sparse, the item pointer, prof, share) in ONE batch of scalar loads and one wait; scalar
+//     arithmetic on blockIdx gives (job, launch position).  Then, still in front of the opening barrier, everything else is
+//     requested: the position's item word (a scalar load -- the previous launch wrote it, the longest wait of the head; it
+//     holds the (batch, query group) pair AND the batch's query frame, internal.h) and the job's members by value (KnnJob
+//     keeps them contiguous: s_load_dwordx16 + x4 + x2 at the job's offset).  One wait, at the barrier.  Behind it the
+//     batch's target count (scalar load of tlen[b], only the flow job has one), the query (one global_load_dwordx3 through a
+//     uniform base + 32-bit lane offset) and the K seeds are requested together; the count is wanted when the seeds are in.
+//     All 3 K seed targets are gathered through the clamped index before the first LDS store (+inf is chosen at the store).
+//     Global round trips from entry to the neighbour-seed bound: item word -> {query, seeds, count} -> seed targets, for
+//     both kinds of item.  Before: the job's members one scalar load and one wait each where first used (about a dozen), the
+//     order array as a vector load + v_readfirstlane, for the flow job qmap[b] the same way behind it, the count as a
+//     flat_load, and the K = 3 seed targets in three dependent groups (2 + 4 + 3 loads) -- six round trips for a flow item.
+//     Launches without item words (SearchArgs::item == NULL, the stand-alone warm operators) keep border[pos] -> qmap[b].
 //   * Neighbour seeds (round 3).  A lane's own seed is a poor bound exactly when it matters: every iteration a fifth of
 //     the points re-sample their part label and jump (queries of the x -> y search, targets of the y -> x search), their
 //     old neighbour is then far away, and those lanes -- 23 % of them -- used to produce 78 % of all (query, box)
@@ -52,8 +66,29 @@
 #include "internal.h"
 #include <math.h>
 #include <string.h>
+#include <stddef.h>
 
 typedef float f2 __attribute__((ext_vector_type(2)));
+// the members of a job a search wave needs, as KnnJob lays them out (internal.h): copied by value at the kernel's entry
+struct SearchHot {
+    const float *q, *q_alt, *tsoa, *boxes;
+    const int *seed;
+    float *pd;
+    int *pi;
+    unsigned int *cost;
+    int P1, Ppad, nqg, P2;
+    const int *tlen;
+};
+static_assert(sizeof(SearchHot) == 88 && offsetof(KnnJob, tlen) == offsetof(SearchHot, tlen) && offsetof(KnnJob, q) == 0 && offsetof(KnnJob, q_alt) == offsetof(SearchHot, q_alt) &&
+              offsetof(KnnJob, tsoa) == offsetof(SearchHot, tsoa) && offsetof(KnnJob, boxes) == offsetof(SearchHot, boxes) &&
+              offsetof(KnnJob, seed) == offsetof(SearchHot, seed) && offsetof(KnnJob, pd) == offsetof(SearchHot, pd) &&
+              offsetof(KnnJob, pi) == offsetof(SearchHot, pi) && offsetof(KnnJob, cost) == offsetof(SearchHot, cost) &&
+              offsetof(KnnJob, P1) == offsetof(SearchHot, P1) && offsetof(KnnJob, Ppad) == offsetof(SearchHot, Ppad) &&
+              offsetof(KnnJob, nqg) == offsetof(SearchHot, nqg) && offsetof(KnnJob, P2) == offsetof(SearchHot, P2),
+              "SearchHot mirrors the head of KnnJob");
+// a wave-uniform word that no launch writes while this one runs (the previous launch wrote it): a scalar load, whatever the
+// compiler can prove about the pointer -- as a plain load it came out as a vector load, a wait and a v_readfirstlane
+__device__ __forceinline__ int pr_uniform_word(const void *p) { return *(const __attribute__((address_space(4))) int *)p; }
 #define PR_SMAX 4       // most waves (box slices) per search workgroup
 // (a box's targets are fetched when it is scanned: prefetching every coarse survivor eight at a time was measured -- more
 // instructions, loads for the 60 % of the boxes the precise test rejects, no gain; DESIGN_HISTORY.md)
@@ -90,10 +125,36 @@ extern "C" int reart_debug_prune_phase(unsigned long long *out, int reset) {
 #define PH_DECL unsigned long long ph_t = __builtin_amdgcn_s_memtime(), ph_acc[7] = {0, 0, 0, 0, 0, 0, 0}
 #define PH(k) do { const unsigned long long n_ = __builtin_amdgcn_s_memtime(); ph_acc[k] += n_ - ph_t; ph_t = n_; } while (0)
 #define PH_FLUSH(from, to) do { if ((threadIdx.x & 63) == 0) for (int k_ = from; k_ <= to; ++k_) atomicAdd(&g_prune_phase[k_], ph_acc[k_]); } while (0)
+// the head of a search wave, K = 1 items in row 0 and K = 3 items in row 1 (ticks summed over waves): 0 kernel entry -> call of
+// knn_pruned_wave (item decode, arguments, record), then inside the prologue 1 -> query in registers, 2 -> seeds in registers,
+// 3 -> seed targets parked in LDS, 4 the whole prologue (phase 0 above), 5 entry -> end of the wave's search, 6 waves.
+// A stamp makes its values an operand of an empty asm, so the compiler waits for them there: the stamps serialise what
+// they measure and belong to this build only.  Everything is added to the counters at the END of the wave's search: vmcnt
+// counts atomics too, and an atomic in front of a stamp would make the stamp wait for 10 944 waves' contention on one word.
+__device__ unsigned long long g_prune_head[2][8];
+extern "C" int reart_debug_prune_head(unsigned long long *out, int reset) {
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_prune_head), sizeof(g_prune_head)) != hipSuccess) return REART_ERR_LAUNCH;
+    if (reset) { unsigned long long z[16] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_prune_head), z, sizeof(z)); }
+    return REART_OK;
+}
+#define PH_HEAD_DECL unsigned long long hd_t = ph_t, hd_acc[3] = {0, 0, 0}
+#define PH_STAMP(k, ...) do { asm volatile("" :: __VA_ARGS__); const unsigned long long n_ = __builtin_amdgcn_s_memtime(); hd_acc[k] = n_ - hd_t; hd_t = n_; } while (0)
+#define PH_HEAD_FLUSH(row) do { if ((threadIdx.x & 63) == 0) { for (int k_ = 0; k_ < 3; ++k_) atomicAdd(&g_prune_head[row][1 + k_], hd_acc[k_]); \
+                                atomicAdd(&g_prune_head[row][4], ph_acc[0]); atomicAdd(&g_prune_head[row][6], 1ull); } } while (0)
+#define PH_ENTRY const unsigned long long hd_entry = __builtin_amdgcn_s_memtime(); unsigned long long hd_head = 0ull
+#define PH_HEAD_END do { hd_head = __builtin_amdgcn_s_memtime() - hd_entry; } while (0)
+#define PH_ENTRY_FLUSH(row) do { if ((threadIdx.x & 63) == 0) { atomicAdd(&g_prune_head[row][0], hd_head); \
+                                 atomicAdd(&g_prune_head[row][5], __builtin_amdgcn_s_memtime() - hd_entry); } } while (0)
 #else
 #define PH_DECL do { } while (0)
 #define PH(k) do { } while (0)
 #define PH_FLUSH(from, to) do { } while (0)
+#define PH_HEAD_DECL do { } while (0)
+#define PH_STAMP(k, ...) do { } while (0)
+#define PH_HEAD_FLUSH(row) do { } while (0)
+#define PH_ENTRY do { } while (0)
+#define PH_HEAD_END do { } while (0)
+#define PH_ENTRY_FLUSH(row) do { } while (0)
 #endif
 
 #define PR_WORK(w) ((unsigned)(w) << 20)   // the work count lives in bits 20..31 of a wave's statistics counter, the pairs below
@@ -140,8 +201,11 @@ __device__ __forceinline__ float box_lb(float lo0, float lo1, float lo2, float h
 // LDS (knn_cloud_kernel); otherwise at the global images.  QCAP: entries of the wave's queue.
 // share: neighbour seeds (parked in the queue's space, which is free until the first coarse round: s_bb | s_q when BOXL,
 // s_q otherwise; skipped when that space is too small for KK x 3 x 64 floats).
+// The caller has resolved what depends on the batch: `qcloud` the query cloud [P1][3] of batch b (q + qmap[b] * P1 * 3, or
+// q_alt), `seed_p` the job's seeds, `n2` the batch's target count -- nothing here waits for a per-batch word.
 template <int KK, bool LDSV, int QCAP, bool BOXL>
-__device__ __forceinline__ void knn_pruned_wave(const KnnJob &jb, const int S, const int sparse, const int b, const int g,
+__device__ __forceinline__ void knn_pruned_wave(const float *qcloud, const int *seed_p, const int P1, const int n2,
+                                                const int S, const int sparse, const int b, const int g,
                                                 const int s, const float *cloud, const int cstride, const float *boxes_p,
                                                 float *s_tg, float *s_qc, unsigned int *s_q, float *s_bb, const int share, float *s_xthr,
                                                 unsigned long long *s_key, float &qx_o, float &qy_o, float &qz_o,
@@ -149,18 +213,19 @@ __device__ __forceinline__ void knn_pruned_wave(const KnnJob &jb, const int S, c
     struct { int S, sparse; } a = {S, sparse};
     const int lane = threadIdx.x & 63;
     PH_DECL;
+    PH_HEAD_DECL;
 
     const int i = g * NN_BS + lane;
-    const int ic = i < jb.P1 ? i : jb.P1 - 1;
-    const int qb = jb.qmap ? jb.qmap[b] : b;
-    const float *qp = (qb < 0 ? jb.q_alt : jb.q + (size_t)qb * jb.P1 * 3) + (size_t)ic * 3;
+    const int ic = i < P1 ? i : P1 - 1;
+    // (wave-uniform base) + (32-bit lane offset in bytes), as in the drain: no 64-bit lane address to build or keep
+    const float *qp = (const float *)((const char *)qcloud + 12u * (unsigned)ic);
     const float qx = qp[0], qy = qp[1], qz = qp[2];
+    PH_STAMP(0, "v"(qx), "v"(qy), "v"(qz));
     const f2 qx2 = {qx, qx}, qy2 = {qy, qy}, qz2 = {qz, qz};
 
     const float *tx = cloud;
     const float *ty = tx + cstride;
     const float *tz = ty + cstride;
-    const int n2 = jb.tlen ? jb.tlen[b] : jb.P2;
     const int nbox = (n2 + NN_BOX - 1) / NN_BOX;
     const float *bx = boxes_p;
 
@@ -168,7 +233,7 @@ __device__ __forceinline__ void knn_pruned_wave(const KnnJob &jb, const int S, c
     float thr = 0.f;
     unsigned int wp = 0u;             // statistics counter, see PR_WORK below
     {
-        const int *sd = jb.seed + ((size_t)b * jb.P1 + ic) * KK;
+        const int *sd = (const int *)((const char *)(seed_p + (size_t)b * P1 * KK) + 4u * KK * (unsigned)ic);
         int sj[KK];
         bool ok = true;
 #pragma unroll
@@ -178,6 +243,7 @@ __device__ __forceinline__ void knn_pruned_wave(const KnnJob &jb, const int S, c
 #pragma unroll
             for (int k2 = 0; k2 < k; ++k2) ok = ok && sj[k] != sj[k2];
         }
+        PH_STAMP(1, "v"(sj[0]), "v"(sj[KK - 1]), "s"(n2));
         // scratch for the neighbour seeds: the result slots (s_key, 384 floats, initialised after this block) and the queue's
         // space behind them (box bounds | queue) are contiguous and idle until the first coarse round
         constexpr bool SCR_JOINT = BOXL;                         // s_bb | s_q contiguous
@@ -186,14 +252,24 @@ __device__ __forceinline__ void knn_pruned_wave(const KnnJob &jb, const int S, c
             // ---- neighbour seeds: the K seed targets of every lane of this row of 16 (the lane's own among them), two lanes
             // per packed step.  A lane without usable seeds parks +inf (its candidates bound nothing -- but it still takes its
             // neighbours' bound); LDS operations of a wave complete in order, and every lane reads only its own row.
+            // All 3 K gathers are in flight before the first LDS store: the index is clamped, so the loads need no guard, and
+            // the +inf is chosen at the store.  (Guarded loads -- ok ? tx[j] : INFINITY -- were compiled into one exec-mask
+            // block per seed, each waiting for its own loads before its stores: three round trips for a K = 3 item.)
             float *s_scr = (float *)s_key;
+            float sx[KK], sy[KK], sz[KK];
 #pragma unroll
             for (int k = 0; k < KK; ++k) {
                 const int j = ok ? sj[k] : 0;
-                s_scr[(3 * k + 0) * 64 + lane] = ok ? tx[j] : INFINITY;
-                s_scr[(3 * k + 1) * 64 + lane] = ok ? ty[j] : INFINITY;
-                s_scr[(3 * k + 2) * 64 + lane] = ok ? tz[j] : INFINITY;
+                sx[k] = tx[j]; sy[k] = ty[j]; sz[k] = tz[j];
             }
+            if (!LDSV) __builtin_amdgcn_sched_barrier(0);      // the scheduler must not sink a gather below a store
+#pragma unroll
+            for (int k = 0; k < KK; ++k) {
+                s_scr[(3 * k + 0) * 64 + lane] = ok ? sx[k] : INFINITY;
+                s_scr[(3 * k + 1) * 64 + lane] = ok ? sy[k] : INFINITY;
+                s_scr[(3 * k + 2) * 64 + lane] = ok ? sz[k] : INFINITY;
+            }
+            PH_STAMP(2, "v"(lane));
             thr = INFINITY;
             const float *row = s_scr + (lane & 48);
             // s_xthr (the workgroup's exchange array [S][64]): the S waves of the workgroup hold the same 64 queries, so each
@@ -512,6 +588,7 @@ __device__ __forceinline__ void knn_pruned_wave(const KnnJob &jb, const int S, c
     if (qcnt > 0) drain_queue();
     PH(5);
     PH_FLUSH(0, 5);
+    PH_HEAD_FLUSH(KK == 1 ? 0 : 1);
     qx_o = qx; qy_o = qy; qz_o = qz;
     work_o = (int)(wp >> 20); pairs_o = wp & 0xFFFFFu;
 }
@@ -523,7 +600,8 @@ __device__ __forceinline__ void knn_pruned_wave(const KnnJob &jb, const int S, c
 template <bool BATCH>
 __global__ __launch_bounds__(64 * PR_SMAX, PR_WPE) void knn_group_kernel(Batched<SearchArgs> ab) {
     // instance of a batch (gridDim.x is a multiple of 8: blockIdx.x & 7 is still the XCD); a single one reads at a fixed offset
-    const SearchArgs &a = ab.a[BATCH ? blockIdx.y : 0];
+    PH_ENTRY;
+    const SearchArgs &a_ = ab.a[BATCH ? blockIdx.y : 0];
     extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];      // blockDim.x / 64 x PR_LDS_WAVE_BYTES
     // where wave t parks its candidates for the merge: its own result slots (s_key, 3 x 64 x 8 bytes), dead once its search
     // is over -- as static arrays they cost 6 KB per workgroup, i.e. the sixth resident workgroup of a compute unit
@@ -533,11 +611,14 @@ __global__ __launch_bounds__(64 * PR_SMAX, PR_WPE) void knn_group_kernel(Batched
     __shared__ float s_xthr[PR_SMAX][64];   // the waves' partial neighbour-seed bounds (written once, read after one barrier)
     __shared__ unsigned int s_ticket;
     __shared__ unsigned long long s_t0;
-    if (threadIdx.x == 0) { s_ticket = 0u; s_t0 = a.prof ? wall_clock64() : 0ull; }
-    __syncthreads();                        // at the start, where all waves of the workgroup arrive together
+    // ---- which item: scalar arithmetic on blockIdx and the first words of the argument block, fetched in one load
+    struct { int n1, n3, G, per, S1, S3, interleave, sparse; } a = {a_.n1, a_.n3, a_.G, a_.per, a_.S1, a_.S3, a_.interleave, a_.sparse};
+    const unsigned int *const items = a_.item;
+    unsigned long long *const prof = a_.prof;
+    const int share = a_.share;
+    asm volatile("" :: "s"(a.n1), "s"(a.n3), "s"(a.G), "s"(a.per), "s"(a.S1), "s"(a.S3), "s"(a.interleave), "s"(a.sparse), "s"(items), "s"(prof), "s"(share));
     const int L = blockIdx.x, x = L & 7, r = L >> 3;
     const int s = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const unsigned long long t0 = s_t0;
     // XCD-local item r: two K = 1 items alternate with one K = 3 item while both kinds last
     const int items1 = a.n1 * a.per, items3 = a.n3 * a.per;
     const int mixed = (a.n1 == 2 && a.n3) ? 3 * a.per : 0;
@@ -556,15 +637,33 @@ __global__ __launch_bounds__(64 * PR_SMAX, PR_WPE) void knn_group_kernel(Batched
     const int p = kind == 1 ? (a.n1 == 2 ? (idx >> 1) : idx) : idx;
     const int pos = a.interleave ? p * 8 + x : x * a.per + p;   // launch position: XCD x owns a contiguous chunk, or every 8th
     const bool live = p < a.per && pos < a.G && (kind == 1 ? idx < items1 : idx < items3);
+    // ---- everything the workgroup needs to know is requested HERE, in front of the opening barrier: the item word (one
+    // scalar load whose address depends on blockIdx and a.item only; the previous launch wrote it, so it misses the local
+    // L2 and is the longest wait of the head) and the job's members (one batch of wide scalar loads of the argument segment
+    // at the job's offset).  A padding position (!live) reads word 0 of its row.
+    const KnnJob *jp = kind == 1 ? &a_.k1[j] : &a_.k3;
+    int rec = pos;
+    if (items) rec = pr_uniform_word(items + ((size_t)(kind == 1 ? j : 2) * a.G + (live ? pos : 0)));
+    SearchHot h;
+    __builtin_memcpy(&h, jp, sizeof(SearchHot));
+    if (threadIdx.x == 0) { s_ticket = 0u; s_t0 = prof ? wall_clock64() : 0ull; }
+    __syncthreads();                        // at the start, where all waves of the workgroup arrive together
+    // the values are wanted in registers at this point: keeps the compiler from moving a load down to its first use
+    asm volatile("" :: "s"(rec), "s"(h.tlen), "s"(h.q), "s"(h.q_alt), "s"(h.tsoa), "s"(h.boxes), "s"(h.seed), "s"(h.pd),
+                 "s"(h.pi), "s"(h.cost), "s"(h.P1), "s"(h.Ppad), "s"(h.nqg), "s"(h.P2));
+    const unsigned long long t0 = s_t0;
     if (!live) {                                                        // padding of the last chunk (uniform per workgroup)
-        if (a.prof && threadIdx.x == 0) { a.prof[2 * (size_t)L] = t0; a.prof[2 * (size_t)L + 1] = t0; a.prof_pairs[L] = 0u; }
+        if (prof && threadIdx.x == 0) { prof[2 * (size_t)L] = t0; prof[2 * (size_t)L + 1] = t0; a_.prof_pairs[L] = 0u; }
         return;
     }
-    const KnnJob &jb = kind == 1 ? a.k1[j] : a.k3;
     const int S = kind == 1 ? a.S1 : a.S3;
     if (s >= S) return;                                                 // the other kind of item uses more waves
-    const int grp = jb.border ? jb.border[pos] : pos;
-    const int b = grp / jb.nqg, g = grp - b * jb.nqg;
+    // without item words (the stand-alone warm operators): the order array, then the query map
+    const int grp = items ? (int)((unsigned)rec & SEARCH_ITEM_PAIR_MASK) : (jp->border ? jp->border[pos] : pos);
+    const int b = grp / h.nqg, g = grp - b * h.nqg;
+    const int qb = items ? (int)((unsigned)rec >> SEARCH_ITEM_PAIR_BITS) - 1 : (jp->qmap ? jp->qmap[b] : b);
+    const int n2 = h.tlen ? pr_uniform_word(h.tlen + b) : h.P2;       // beside the query and the seeds; wanted when the seeds are in
+    const float *qcloud = qb < 0 ? h.q_alt : h.q + (size_t)qb * h.P1 * 3;
     float qx = 0.f, qy = 0.f, qz = 0.f;
     float bm[3] = {INFINITY, INFINITY, INFINITY};
     int bb[3] = {-1, -1, -1};
@@ -581,17 +680,19 @@ __global__ __launch_bounds__(64 * PR_SMAX, PR_WPE) void knn_group_kernel(Batched
         float *s_bb = (float *)s_q;          // the bounds of a coarse round's 64 boxes take the first 384 entries of the queue's space
         s_q += 384;
         constexpr int QC = PR_QCAP - 384;
-        const float *cloud = jb.tsoa + (size_t)b * 3 * jb.Ppad;
-        const float *boxes_p = jb.boxes + (size_t)b * (jb.Ppad / NN_BOX) * 8;
+        const float *cloud = h.tsoa + (size_t)b * 3 * h.Ppad;
+        const float *boxes_p = h.boxes + (size_t)b * (h.Ppad / NN_BOX) * 8;
+        PH_HEAD_END;
         if (kind == 1) {
             float m1[1]; int b1[1];
-            knn_pruned_wave<1, false, QC, true>(jb, S, a.sparse, b, g, s, cloud, jb.Ppad, boxes_p, s_tg, s_qc, s_q, s_bb, a.share, a.share > 1 ? &s_xthr[0][0] : nullptr, s_key,
+            knn_pruned_wave<1, false, QC, true>(qcloud, h.seed, h.P1, n2, S, a.sparse, b, g, s, cloud, h.Ppad, boxes_p, s_tg, s_qc, s_q, s_bb, share, share > 1 ? &s_xthr[0][0] : nullptr, s_key,
                                                qx, qy, qz, m1, b1, work, pairs);
             bm[0] = m1[0]; bb[0] = b1[0];
         } else {
-            knn_pruned_wave<3, false, QC, true>(jb, S, a.sparse, b, g, s, cloud, jb.Ppad, boxes_p, s_tg, s_qc, s_q, s_bb, a.share, a.share > 1 ? &s_xthr[0][0] : nullptr, s_key,
+            knn_pruned_wave<3, false, QC, true>(qcloud, h.seed, h.P1, n2, S, a.sparse, b, g, s, cloud, h.Ppad, boxes_p, s_tg, s_qc, s_q, s_bb, share, share > 1 ? &s_xthr[0][0] : nullptr, s_key,
                                                qx, qy, qz, bm, bb, work, pairs);
         }
+        PH_ENTRY_FLUSH(kind == 1 ? 0 : 1);
     }
     // ---- the LAST wave to finish merges (no barrier: a wave that is done leaves at once and frees its slot; measured with
     // a barrier here, 17 % of a wave's life was waiting for its slowest sibling).  Every wave parks its candidates, then
@@ -617,7 +718,7 @@ __global__ __launch_bounds__(64 * PR_SMAX, PR_WPE) void knn_group_kernel(Batched
     // ---- merge the slices' candidates by (minimum, first index): distinct slices hold distinct boxes, so the lower block
     // start is the lower index
     const int i = g * NN_BS + lane;
-    const float *tx = jb.tsoa + (size_t)b * 3 * jb.Ppad, *ty = tx + jb.Ppad, *tz = ty + jb.Ppad;
+    const float *tx = h.tsoa + (size_t)b * 3 * h.Ppad, *ty = tx + h.Ppad, *tz = ty + h.Ppad;
     if (kind == 1) {
         float m = bm[0];
         int blk = bb[0];
@@ -637,9 +738,9 @@ __global__ __launch_bounds__(64 * PR_SMAX, PR_WPE) void knn_group_kernel(Batched
             }
         }
         pairs += 64u * (NN_BOX / 2);
-        if (i < jb.P1) {
-            const size_t o = (size_t)b * jb.P1 + i;
-            jb.pd[o] = m; jb.pi[o] = bi;
+        if (i < h.P1) {
+            const size_t o = (size_t)b * h.P1 + i;
+            h.pd[o] = m; h.pi[o] = bi;
         }
     } else {
         float kd[3] = {INFINITY, INFINITY, INFINITY};
@@ -653,17 +754,17 @@ __global__ __launch_bounds__(64 * PR_SMAX, PR_WPE) void knn_group_kernel(Batched
                 reart_top3_insert(kd, ki, PARK_M(t)[k * 64 + lane], bt >= 0 ? bt : 0x7fffffff);
             }
         }
-        if (i < jb.P1) {
-            const size_t o = ((size_t)b * jb.P1 + i) * 3;
+        if (i < h.P1) {
+            const size_t o = ((size_t)b * h.P1 + i) * 3;
 #pragma unroll
-            for (int k = 0; k < 3; ++k) { jb.pd[o + k] = kd[k]; jb.pi[o + k] = kd[k] < INFINITY ? ki[k] : -1; }
+            for (int k = 0; k < 3; ++k) { h.pd[o + k] = kd[k]; h.pi[o + k] = kd[k] < INFINITY ? ki[k] : -1; }
         }
     }
     if (lane == 0) {
-        if (jb.cost) jb.cost[pos] = (unsigned int)work;
-        if (a.prof) {
-            a.prof[2 * (size_t)L] = t0; a.prof[2 * (size_t)L + 1] = wall_clock64();
-            a.prof_pairs[L] = pairs;
+        if (h.cost) h.cost[pos] = (unsigned int)work;
+        if (prof) {
+            prof[2 * (size_t)L] = t0; prof[2 * (size_t)L + 1] = wall_clock64();
+            a_.prof_pairs[L] = pairs;
         }
     }
 }
@@ -721,13 +822,16 @@ __global__ __launch_bounds__(64 * PC_WAVES) void knn_cloud_kernel(SearchArgs a) 
         unsigned char *wl = wbase + (size_t)w * PC_WAVE_BYTES;
         float *s_qc = (float *)wl;
         unsigned int *s_q = (unsigned int *)(wl + 64 * 16 + 3 * 64 * 8);
+        const int qb = jb.qmap ? jb.qmap[b] : b;
+        const float *qcloud = qb < 0 ? jb.q_alt : jb.q + (size_t)qb * jb.P1 * 3;
+        const int n2 = jb.tlen ? jb.tlen[b] : jb.P2;
         if (kind == 1) {
             float m1[1]; int b1[1];
-            knn_pruned_wave<1, true, PC_QCAP, false>(jb, S, a.sparse, b, g, sl, cl, Ppad, bxs, nullptr, s_qc, s_q, nullptr, a.share, nullptr, s_key, qx, qy, qz,
+            knn_pruned_wave<1, true, PC_QCAP, false>(qcloud, jb.seed, jb.P1, n2, S, a.sparse, b, g, sl, cl, Ppad, bxs, nullptr, s_qc, s_q, nullptr, a.share, nullptr, s_key, qx, qy, qz,
                                               m1, b1, work, pairs);
             bm[0] = m1[0]; bb[0] = b1[0];
         } else {
-            knn_pruned_wave<3, true, PC_QCAP, false>(jb, S, a.sparse, b, g, sl, cl, Ppad, bxs, nullptr, s_qc, s_q, nullptr, a.share, nullptr, s_key, qx, qy, qz,
+            knn_pruned_wave<3, true, PC_QCAP, false>(qcloud, jb.seed, jb.P1, n2, S, a.sparse, b, g, sl, cl, Ppad, bxs, nullptr, s_qc, s_q, nullptr, a.share, nullptr, s_key, qx, qy, qz,
                                               bm, bb, work, pairs);
         }
         if (S > 1 && sl > 0) {

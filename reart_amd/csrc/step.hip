@@ -34,7 +34,7 @@ struct StepPlan {
     int W1, W3;               // pruned: waves (box slices) per search workgroup, K = 1 / K = 3
     int sparse;               // pruned: sparse-scan limit
     size_t o_seed3;           // last iteration's flow neighbour indices [B,N,3] (the Chamfer seeds are the K = 1 records themselves)
-    size_t o_border;          // [3][B * nqg] launch order of the (frame, query group) pairs of the three search jobs
+    size_t o_item;            // [3][B * nqg] item words (reart_search_item) of the three search jobs by launch position: the launch order
     size_t o_cost;            // [3][B * nqg] work counts of the last search launch, by launch position
     size_t o_prof, o_prof_pairs, o_prof_acc;   // cfg.profile: per-workgroup stamps of the search launch and their accumulators
     size_t o_gridY, o_gridR;  // exact-search grids over pc_list and the flow reference sets
@@ -110,7 +110,7 @@ static int step_plan(const reart_relax_config *c, StepPlan *p) {
     p->o_boxR = ws.take_bytes(sizeof(float) * 8 * (size_t)c->B * (p->Mpad / NN_BOX + 1));
     p->o_seed3 = ws.take_bytes((p->pruned && c->use_flow) ? sizeof(int) * BN * 3 : 0);
     const size_t G = (size_t)c->B * reart_div_up(c->N, NN_BS);
-    p->o_border = ws.take_bytes(sizeof(int) * 3 * G);
+    p->o_item = ws.take_bytes(sizeof(unsigned int) * 3 * G);
     p->o_cost = ws.take_bytes(sizeof(unsigned int) * 3 * G);
     const size_t nprof = (c->profile && p->pruned) ? (size_t)reart_search_grid(2, 1, (int)G) : 0;
     p->o_prof = ws.take_bytes(sizeof(unsigned long long) * 2 * nprof);
@@ -135,7 +135,7 @@ __global__ void relax_init_kernel(reart_relax_config c, const int *__restrict__ 
                                   int *__restrict__ rlen, int *__restrict__ qmap,
                                   int64_t *__restrict__ iter, float *__restrict__ tau,
                                   const float *__restrict__ pc_list, int *__restrict__ fx_bits,
-                                  float *__restrict__ adam_step, int *__restrict__ seed3, int *__restrict__ border) {
+                                  float *__restrict__ adam_step, int *__restrict__ seed3, unsigned int *__restrict__ item) {
     __shared__ float s_max[1024];
     const int t = threadIdx.x;
     // warm start of the first k=3 search: any 3 distinct valid indices
@@ -161,18 +161,23 @@ __global__ void relax_init_kernel(reart_relax_config c, const int *__restrict__ 
         fx_bits[0] = bits > 39 ? 39 : (bits < 0 ? 0 : bits);
     }
     if (t < c.B) {
-        // Launch order of the search items: position k = pair k (frame-major), so that every XCD's eighth of the
-        // positions is a run of consecutive frames; the consumer launch re-sorts every eighth by measured work.
-        {
-            const int nqg = (c.N + NN_BS - 1) / NN_BS, ng = c.B * nqg;
-            for (int g = 0; g < nqg; ++g)
-                for (int j = 0; j < 3; ++j) border[j * ng + t * nqg + g] = t * nqg + g;
-        }
         // flow pair f (complete frames f -> f+1) queries complete frame f (run_robot.py:196):
         // complete frame f is pc_trans[f] before the canonical index, the canonical cloud at it,
         // pc_trans[f-1] after it.
-        qmap[t] = (t < c.cano_idx) ? t : (t == c.cano_idx ? -1 : t - 1);
+        const int qm = (t < c.cano_idx) ? t : (t == c.cano_idx ? -1 : t - 1);
+        qmap[t] = qm;
         if (c.use_flow) rlen[t] = ref_off[t + 1] - ref_off[t];
+        // Launch order of the search items: position k = pair k (frame-major), so that every XCD's eighth of the
+        // positions is a run of consecutive frames; the consumer launch re-sorts every eighth by measured work.  A position
+        // holds the item word: the pair and the frame's query cloud as the job sees it (the Chamfer jobs query frame t, the
+        // flow job qmap[t]).  Shapes whose pairs or frames do not fit the word keep plain pairs (KnnJob::border).
+        {
+            const int nqg = (c.N + NN_BS - 1) / NN_BS, ng = c.B * nqg;
+            const bool words = reart_search_items_fit((long)ng, c.B);
+            for (int g = 0; g < nqg; ++g)
+                for (int j = 0; j < 3; ++j)
+                    item[j * ng + t * nqg + g] = words ? reart_search_item(t * nqg + g, j < 2 ? t : qm) : (unsigned int)(t * nqg + g);
+        }
     }
     if (t == 0) {
         // `iter` is caller state: it is NOT reset here, so a resumed run continues its schedule
@@ -229,7 +234,7 @@ extern "C" int reart_relax_prepare(const reart_relax_config *cfg, const reart_re
     hipLaunchKernelGGL(relax_init_kernel, dim3(1), dim3(1024), 0, st, *cfg, bufs->ref_off,
                        (int *)(ws + p.o_rlen), (int *)(ws + p.o_qmap), bufs->iter, bufs->tau, bufs->pc_list,
                        (int *)(ws + p.o_fx), (float *)(ws + p.o_bc),
-                       (p.pruned && cfg->use_flow) ? (int *)(ws + p.o_seed3) : nullptr, (int *)(ws + p.o_border));
+                       (p.pruned && cfg->use_flow) ? (int *)(ws + p.o_seed3) : nullptr, (unsigned int *)(ws + p.o_item));
     if (hipMemsetAsync(ws + p.o_ticket, 0, 4 * sizeof(unsigned int), st) != hipSuccess) return REART_ERR_LAUNCH;
     if (hipMemsetAsync(ws + p.o_prof_acc, 0, 4 * sizeof(unsigned long long), st) != hipSuccess) return REART_ERR_LAUNCH;
     if (p.pruned) {  // warm start of the first Chamfer search: index 0 (any valid index); the K = 1 records are the seeds
@@ -555,7 +560,7 @@ __global__ __launch_bounds__(FLOW_BS) void flow_blend_kernel(Batched<FlowArgs> a
 // heaviest first.
 struct OrderArgs {
     const unsigned int *cost[3];   // per job: x -> y, y -> x, flow; [groups] work counts by launch position (CURRENT order)
-    int *border[3];                // per job: launch position -> (frame, query group) pair (read, then rewritten)
+    unsigned int *item[3];         // per job: launch position -> item word of a (frame, query group) pair (read, then rewritten)
     int groups;                    // B * nqg pairs per job
     int per;                       // positions per XCD chunk = ceil(groups / 8): chunk x = positions [x*per, (x+1)*per);
                                    // per >= groups: one chunk (interleaved launch order: a global sort)
@@ -571,14 +576,15 @@ __device__ __forceinline__ void order_body(const OrderArgs &o, const int j) {
     if (!o.cost[j] || o.groups > ORD_MAX * CG_BS) return;
     for (int e = tid; e < 8 * 256; e += CG_BS) s_hist[e] = 0u;
     __syncthreads();
-    int old[ORD_MAX], bucket[ORD_MAX];
+    unsigned int old[ORD_MAX];     // the whole word moves: what it says about the pair's frame stays true
+    int bucket[ORD_MAX];
 #pragma unroll
     for (int u = 0; u < ORD_MAX; ++u) {
         const int k = tid + u * CG_BS;
-        old[u] = 0; bucket[u] = -1;
+        old[u] = 0u; bucket[u] = -1;
         if (k < o.groups) {
             const unsigned int c = o.cost[j][k] >> 5;
-            old[u] = o.border[j][k];
+            old[u] = o.item[j][k];
             bucket[u] = (k / o.per) * 256 + 255 - (int)(c < 255u ? c : 255u);   // heaviest pairs in the chunk's first buckets
             atomicAdd(&s_hist[bucket[u]], 1u);
         }
@@ -604,7 +610,7 @@ __device__ __forceinline__ void order_body(const OrderArgs &o, const int j) {
     __syncthreads();
 #pragma unroll
     for (int u = 0; u < ORD_MAX; ++u)
-        if (bucket[u] >= 0) o.border[j][atomicAdd(&s_hist[bucket[u]], 1u)] = old[u];
+        if (bucket[u] >= 0) o.item[j][atomicAdd(&s_hist[bucket[u]], 1u)] = old[u];
 }
 // cfg.profile: duration of the search launch that just ran = last workgroup end - first workgroup start (constant-rate
 // wall clock), and the distance evaluations it executed; accumulated on the device, read by reart_relax_profile
@@ -774,6 +780,7 @@ static int step_describe(const reart_relax_config *cfg, const reart_relax_buffer
 
     const int nqg = reart_div_up(N, NN_BS);
     const int *qmap = (const int *)(ws + p.o_qmap);
+    const bool item_words = reart_search_items_fit((long)B * nqg, B);       // as relax_init_kernel decides
     // job descriptions: K = 1 x -> y (0), y -> x (1); K = 3 flow
     KnnArgs &ka = L.ka, &k3 = L.k3;
     ka.N = B; ka.S = p.S1; ka.K = 1; ka.euclidean = 0;
@@ -786,7 +793,7 @@ static int step_describe(const reart_relax_config *cfg, const reart_relax_buffer
         kj.pi = (int *)(ws + (j == 0 ? p.o_pi0 : p.o_pi1));
         kj.boxes = c.use_boxes ? (const float *)(ws + (j == 0 ? p.o_boxY : p.o_boxX)) : nullptr;
         kj.seed = p.pruned ? kj.pi : nullptr;            // last iteration's record is this iteration's seed (in place)
-        kj.border = (const int *)(ws + p.o_border) + (size_t)j * B * nqg;
+        kj.border = item_words ? nullptr : (const int *)(ws + p.o_item) + (size_t)j * B * nqg;
         kj.cost = p.pruned ? (unsigned int *)(ws + p.o_cost) + (size_t)j * B * nqg : nullptr;
     }
     ka.items0 = B * nqg * p.S1; ka.items = 2 * ka.items0;
@@ -799,7 +806,7 @@ static int step_describe(const reart_relax_config *cfg, const reart_relax_buffer
         kj.P1 = N; kj.P2 = c.M_max; kj.Ppad = p.Mpad; kj.L = p.Mpad / p.S3; kj.nqg = nqg;
         kj.pd = (float *)(ws + p.o_pd3); kj.pi = (int *)(ws + p.o_pi3);
         kj.seed = p.pruned ? (const int *)(ws + p.o_seed3) : nullptr;
-        kj.border = (const int *)(ws + p.o_border) + 2 * (size_t)B * nqg;
+        kj.border = item_words ? nullptr : (const int *)(ws + p.o_item) + 2 * (size_t)B * nqg;
         kj.cost = p.pruned ? (unsigned int *)(ws + p.o_cost) + 2 * (size_t)B * nqg : nullptr;
         k3.job[1] = kj;
         k3.items0 = B * nqg * p.S3; k3.items = k3.items0;
@@ -817,6 +824,7 @@ static int step_describe(const reart_relax_config *cfg, const reart_relax_buffer
     int search_wgs = 0, S3 = p.S3, S0 = p.S1;
     if (p.pruned) {
         SearchArgs &sa = L.sa;
+        sa.item = item_words ? (const unsigned int *)(ws + p.o_item) : nullptr;
         sa.G = B * nqg; sa.S1 = p.W1; sa.S3 = p.W3; sa.sparse = p.sparse; sa.share = c.tune_share < 0 ? 0 : (c.tune_share == 1 ? 1 : 2); sa.interleave = c.tune_xcd > 0 ? 0 : 1;
         sa.cloud_resident = c.tune_cloud > 0 ? 1 : 0; sa.cloud_slices = c.tune_cloud > 0 ? c.tune_cloud : 0;
         if (chamfer) { sa.k1[0] = ka.job[0]; sa.k1[1] = ka.job[1]; sa.n1 = 2; }
@@ -899,7 +907,7 @@ static int step_describe(const reart_relax_config *cfg, const reart_relax_buffer
             for (int j = 0; j < 3; ++j) {
                 const KnnJob &kj = j < 2 ? ka.job[j] : k3.job[0];
                 pa.od.cost[j] = reorder ? kj.cost : nullptr;
-                pa.od.border[j] = (int *)(ws + p.o_border) + (size_t)j * B * nqg;
+                pa.od.item[j] = (unsigned int *)(ws + p.o_item) + (size_t)j * B * nqg;
             }
             pa.od.groups = B * nqg; pa.od.per = c.tune_xcd > 0 ? reart_div_up(B * nqg, 8) : B * nqg;
             pa.norder = reorder ? 3 : 0;
