@@ -173,6 +173,27 @@ int reart_kin_post(const float *pc_trans, const float *cano, int B, int N, int c
                    float smooth_weight, float *G, float *matched, float *losses, void *workspace, size_t workspace_bytes,
                    void *stream);
 
+/* reart_kin_post with the Chamfer term of the same iteration as an input (run_real.py:175-203 / run_sapien.py:174-203 of the
+ * reference add recon_loss in every iteration and ass_loss on top of it from --assign_iter on; KinematicEngine's
+ * recon_with_assign mode).  The arguments of reart_kin_post, plus
+ *   g_recon [B,N,3]  d Chamfer loss / d predicted cloud (reart_chamfer_loss's grad_x), its rows in the order in which the caller
+ *                    stored that cloud for the search;
+ *   inv_x [N] i32    the stored row of canonical point p; NULL: identity.  An entry outside [0, N) is range-checked: that point
+ *                    takes no Chamfer gradient and nothing is read for it;
+ *   loss_recon       device scalar, the Chamfer loss;
+ *   losses [4]       lambda_assign x assignment loss (0 when n = 0) | lambda_flow x flow loss | *loss_recon |
+ *                    fl(fl(losses[0] + losses[2]) + losses[1]) -- the order in which the operator loop adds them.
+ * G[b][p][c] is built in this order, every sum rounded once to float32 (the fused relaxation step's rule for the same sum):
+ * g = g_recon[b][inv_x[p]][c]; at a sampled point g = g + two_lambda x d_c; with the flow branch g = g + t_c -- two_lambda, d_c
+ * and t_c exactly the values reart_kin_post forms.  n = 0 is the Chamfer-only form, with or without flow (the iterations before
+ * --assign_iter).  NULL g_recon or loss_recon: REART_ERR_INVALID_ARG; every other refusal, the workspace
+ * (reart_kin_post_workspace_bytes) and the number of launches are reart_kin_post's; no host synchronisation, no atomics. */
+int reart_kin_post_recon(const float *pc_trans, const float *cano, int B, int N, int cano_idx, const float *pc_src, const float *tgt,
+                         const int32_t *cols, const int32_t *slot_of_point, int n, float lambda_assign, const float *ref,
+                         const float *ref_flow, const int64_t *ref_len, int nr_max, int k, int euclidean, float lambda_flow, int robust,
+                         float smooth_weight, const float *g_recon, const int32_t *inv_x, const float *loss_recon, float *G,
+                         float *matched, float *losses, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Replaces flow_loss(gt_flow_list, pred_flow_list, flow_mask_list, robust, smooth_weight)
  * (networks/loss.py:10-21): gt, pred [B,N,3]; mask [B,N] uint8 or NULL (= all ones);
  * loss: device float scalar; grad_pred [B,N,3] or NULL = d loss / d pred. */

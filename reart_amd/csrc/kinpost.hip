@@ -32,6 +32,10 @@ struct KinPostArgs {
     float *matched;          // [B][n][3] out (nullable): the matched target of every sampled point
     double *partial;         // [blocks] the assignment loss's partial sums
     float *losses;           // [3] out: lambda_assign x assignment loss | lambda_flow x flow loss | total
+    // Chamfer input (reart_kin_post_recon only): losses is [4] then -- the two terms above | Chamfer loss | total
+    const float *g_recon;    // [B][N][3] d Chamfer loss / d pc_trans, rows in the order the caller stored the cloud for its search
+    const int *inv_x;        // [N] stored row of canonical point p (null: identity)
+    const float *loss_recon; // device scalar
 };
 
 __global__ __launch_bounds__(256) void kin_comp_kernel(KinPostArgs a) {
@@ -46,20 +50,29 @@ __global__ __launch_bounds__(256) void kin_comp_kernel(KinPostArgs a) {
 }
 
 #define KP_BS 256
-__global__ __launch_bounds__(KP_BS) void kin_grad_kernel(KinPostArgs a) {
-    __shared__ double s_red[KP_BS / 64];
+// RECON: G starts from the Chamfer gradient of the point's stored row, the pairs' term and the flow term are added to it in this
+// order, each sum rounded once (the fused relaxation step's rule for the same sum); without it the body is reart_kin_post's
+template <bool RECON> __device__ __forceinline__ void kin_grad_body(const KinPostArgs &a, double *s_red) {
     const int fi = blockIdx.y, p = blockIdx.x * KP_BS + threadIdx.x;
     double acc = 0.0;
     if (p < a.N) {
         const size_t per = (size_t)a.N * 3, o = (size_t)fi * per + 3 * (size_t)p;
         float g0 = 0.f, g1 = 0.f, g2 = 0.f;
+        if (RECON) {
+            const int r = a.inv_x ? a.inv_x[p] : p;
+            if (r >= 0 && r < a.N) {      // a row outside the cloud contributes nothing and is never read
+                const float *q = a.g_recon + (size_t)fi * per + 3 * (size_t)r;
+                g0 = q[0]; g1 = q[1]; g2 = q[2];
+            }
+        }
         const int sl = a.slot ? a.slot[p] : -1;
         if (sl >= 0) {
             const size_t so = ((size_t)fi * a.n + sl) * 3;
             const int cj = a.cols[(size_t)fi * a.n + sl];
             const float *t = a.tgt + ((size_t)fi * a.n + cj) * 3;
             const float d0 = a.pc_src[so] - t[0], d1 = a.pc_src[so + 1] - t[1], d2 = a.pc_src[so + 2] - t[2];
-            g0 = a.two_lambda * d0; g1 = a.two_lambda * d1; g2 = a.two_lambda * d2;
+            if (RECON) { g0 = g0 + a.two_lambda * d0; g1 = g1 + a.two_lambda * d1; g2 = g2 + a.two_lambda * d2; }
+            else { g0 = a.two_lambda * d0; g1 = a.two_lambda * d1; g2 = a.two_lambda * d2; }
             acc = (double)(d0 * d0) + (double)(d1 * d1) + (double)(d2 * d2);
             if (a.matched) { a.matched[so] = t[0]; a.matched[so + 1] = t[1]; a.matched[so + 2] = t[2]; }
         }
@@ -79,19 +92,34 @@ __global__ __launch_bounds__(KP_BS) void kin_grad_kernel(KinPostArgs a) {
     acc = reart_block_sum_d<KP_BS>(acc, s_red);
     if (threadIdx.x == 0) a.partial[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = acc;
 }
+__global__ __launch_bounds__(KP_BS) void kin_grad_kernel(KinPostArgs a) {
+    __shared__ double s_red[KP_BS / 64];
+    kin_grad_body<false>(a, s_red);
+}
+__global__ __launch_bounds__(KP_BS) void kin_grad_recon_kernel(KinPostArgs a) {
+    __shared__ double s_red[KP_BS / 64];
+    kin_grad_body<true>(a, s_red);
+}
 
 // The partials come from the launch before this one: plain loads (reart_partials_sum_d's agent-scope loads are for partials
 // written inside the same launch and would change the scope of these)
-__global__ __launch_bounds__(64) void kin_loss_kernel(KinPostArgs a, int blocks) {
+template <bool RECON> __device__ __forceinline__ void kin_loss_body(const KinPostArgs &a, int blocks) {
     double t = 0.0;
     for (int e = threadIdx.x; e < blocks; e += 64) t += a.partial[e];
     t = reart_wave_sum_d(t);
     if (threadIdx.x == 0) {
         const float ass = a.lambda_assign * (float)t;
         const float fl = a.gp ? *a.loss_flow * a.lambda_flow : 0.f;
-        a.losses[0] = ass; a.losses[1] = fl; a.losses[2] = ass + fl;
+        if (RECON) {      // the order in which the operator loop adds them: assignment, Chamfer, flow
+            const float rec = *a.loss_recon;
+            a.losses[0] = ass; a.losses[1] = fl; a.losses[2] = rec; a.losses[3] = (ass + rec) + fl;
+        } else {
+            a.losses[0] = ass; a.losses[1] = fl; a.losses[2] = ass + fl;
+        }
     }
 }
+__global__ __launch_bounds__(64) void kin_loss_kernel(KinPostArgs a, int blocks) { kin_loss_body<false>(a, blocks); }
+__global__ __launch_bounds__(64) void kin_loss_recon_kernel(KinPostArgs a, int blocks) { kin_loss_body<true>(a, blocks); }
 
 // the flow loss's and the batched blend's own workspaces come last, each at the size its operator reports (flow only)
 struct KinPostWs { float *comp, *pred, *gt, *gp, *loss_flow; uint8_t *mask; double *partial; char *fl, *blend; size_t blend_bytes; };
@@ -114,11 +142,12 @@ extern "C" size_t reart_kin_post_workspace_bytes(int B, int N, int nr_max, int k
     return kp_layout(B, N, nr_max > 0 ? nr_max : 1, k > 0 ? k : 1, nr_max > 0, nullptr, &w);
 }
 
-extern "C" int reart_kin_post(const float *pc_trans, const float *cano, int B, int N, int cano_idx, const float *pc_src, const float *tgt,
-                              const int32_t *cols, const int32_t *slot_of_point, int n, float lambda_assign, const float *ref,
-                              const float *ref_flow, const int64_t *ref_len, int nr_max, int k, int euclidean, float lambda_flow, int robust,
-                              float smooth_weight, float *G, float *matched, float *losses, void *workspace, size_t workspace_bytes,
-                              void *stream) {
+// both entries: `recon` selects the kernels that start G from the Chamfer gradient and write four losses
+static int kp_run(const float *pc_trans, const float *cano, int B, int N, int cano_idx, const float *pc_src, const float *tgt,
+                  const int32_t *cols, const int32_t *slot_of_point, int n, float lambda_assign, const float *ref,
+                  const float *ref_flow, const int64_t *ref_len, int nr_max, int k, int euclidean, float lambda_flow, int robust,
+                  float smooth_weight, float *G, float *matched, float *losses, void *workspace, size_t workspace_bytes,
+                  void *stream, bool recon, const float *g_recon, const int32_t *inv_x, const float *loss_recon) {
     if (B < 1 || N < 1 || n < 0 || cano_idx < 0 || cano_idx > B) return REART_ERR_INVALID_ARG;
     if (!pc_trans || !cano || !G || !losses || !workspace) return REART_ERR_INVALID_ARG;
     if (n > 0 && (!pc_src || !tgt || !cols || !slot_of_point)) return REART_ERR_INVALID_ARG;
@@ -134,6 +163,7 @@ extern "C" int reart_kin_post(const float *pc_trans, const float *cano, int B, i
     a.two_lambda = (float)(2.0 * (double)lambda_assign); a.lambda_assign = lambda_assign;
     a.gp = flow ? w.gp : nullptr; a.loss_flow = w.loss_flow; a.lambda_flow = lambda_flow;
     a.G = G; a.matched = matched; a.partial = w.partial; a.losses = losses;
+    a.g_recon = g_recon; a.inv_x = inv_x; a.loss_recon = loss_recon;
     if (flow) {
         const size_t total = (size_t)(B + 1) * N * 3;
         hipLaunchKernelGGL(kin_comp_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a);
@@ -146,9 +176,35 @@ extern "C" int reart_kin_post(const float *pc_trans, const float *cano, int B, i
         if (rc != REART_OK) return rc;
     }
     const int gx = reart_div_up(N, KP_BS);
-    hipLaunchKernelGGL(kin_grad_kernel, dim3(gx, B), dim3(KP_BS), 0, st, a);
+    if (recon) hipLaunchKernelGGL(kin_grad_recon_kernel, dim3(gx, B), dim3(KP_BS), 0, st, a);
+    else hipLaunchKernelGGL(kin_grad_kernel, dim3(gx, B), dim3(KP_BS), 0, st, a);
     REART_CHECK_LAUNCH();
-    hipLaunchKernelGGL(kin_loss_kernel, dim3(1), dim3(64), 0, st, a, gx * B);
+    if (recon) hipLaunchKernelGGL(kin_loss_recon_kernel, dim3(1), dim3(64), 0, st, a, gx * B);
+    else hipLaunchKernelGGL(kin_loss_kernel, dim3(1), dim3(64), 0, st, a, gx * B);
     REART_CHECK_LAUNCH();
     return REART_OK;
+}
+
+extern "C" int reart_kin_post(const float *pc_trans, const float *cano, int B, int N, int cano_idx, const float *pc_src, const float *tgt,
+                              const int32_t *cols, const int32_t *slot_of_point, int n, float lambda_assign, const float *ref,
+                              const float *ref_flow, const int64_t *ref_len, int nr_max, int k, int euclidean, float lambda_flow, int robust,
+                              float smooth_weight, float *G, float *matched, float *losses, void *workspace, size_t workspace_bytes,
+                              void *stream) {
+    return kp_run(pc_trans, cano, B, N, cano_idx, pc_src, tgt, cols, slot_of_point, n, lambda_assign, ref, ref_flow, ref_len, nr_max, k,
+                  euclidean, lambda_flow, robust, smooth_weight, G, matched, losses, workspace, workspace_bytes, stream, false, nullptr,
+                  nullptr, nullptr);
+}
+
+// reart_kin_post with the Chamfer term's gradient and value as inputs (the engine's recon_with_assign mode): the same launches,
+// G = Chamfer gradient (through inv_x) + pairs' term + flow term, losses [4].  n = 0: the Chamfer-only form (with or without flow)
+extern "C" int reart_kin_post_recon(const float *pc_trans, const float *cano, int B, int N, int cano_idx, const float *pc_src,
+                                    const float *tgt, const int32_t *cols, const int32_t *slot_of_point, int n, float lambda_assign,
+                                    const float *ref, const float *ref_flow, const int64_t *ref_len, int nr_max, int k, int euclidean,
+                                    float lambda_flow, int robust, float smooth_weight, const float *g_recon, const int32_t *inv_x,
+                                    const float *loss_recon, float *G, float *matched, float *losses, void *workspace,
+                                    size_t workspace_bytes, void *stream) {
+    if (!g_recon || !loss_recon) return REART_ERR_INVALID_ARG;
+    return kp_run(pc_trans, cano, B, N, cano_idx, pc_src, tgt, cols, slot_of_point, n, lambda_assign, ref, ref_flow, ref_len, nr_max, k,
+                  euclidean, lambda_flow, robust, smooth_weight, G, matched, losses, workspace, workspace_bytes, stream, true, g_recon,
+                  inv_x, loss_recon);
 }

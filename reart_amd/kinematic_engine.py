@@ -27,13 +27,37 @@ class KinematicEngine:
     ``use_assign_loss`` / ``assign_iter`` / ``assign_gap`` / ``downsample`` / ``lambda_assign``, ``lambda_flow``,
     ``use_robust_loss``.  Before ``assign_iter`` (or with ``use_assign_loss=False``) the iteration takes the Chamfer branch
     (run_robot.py:187-190): two exact K = 1 searches and ``knn_points_backward`` for dL/d pc_trans, no autograd there either.
+
+    ``recon_with_assign=True`` (off by default: nothing new is allocated, the attributes below are None, every launch is the
+    default mode's): the objective of the reference's real-scan and SAPIEN recipes (run_real.py:175-203, run_sapien.py:174-203) --
+    the Chamfer loss in EVERY iteration, the assignment loss added to it from ``assign_iter`` on, as ``OperatorLoop`` computes it
+    under ``--recon_with_assign``.  The Chamfer term is the warm exact search with its gradient as one call
+    (``reart_chamfer_loss``) on clouds stored in k-d order -- one order of the canonical cloud for every predicted frame, each
+    observed frame in its own --, in front of the re-solve (queued eagerly between the two captured graphs); ``reart_kin_post_recon`` adds
+    its gradient, the pairs' term and the flow term in one write.  Neighbours and distances are bit for bit ``knn_points``'s; a
+    tie between distinct equidistant targets goes to the one stored first in the k-d order (``ChamferLoss``'s rule).  The loss
+    dictionary has ``OperatorLoop``'s keys in its order: [opt assignment loss,] recon Loss, [flow Loss,] total Loss.
+    ``recon_grad()``: the latest Chamfer gradient in the caller's numbering; ``last_fx_bits``: its fixed-point bits.  One
+    lambda_assign, no weight on the Chamfer term, K = 1.  The Chamfer gradient is discontinuous where a point has two nearest
+    neighbours, so this mode keeps to the bits of an autograd loop over the model: the root motion is applied with the model's
+    own expression (product, then addition) and the step is ``reart_amd.optim.Adam`` (torch.optim.Adam's bits, one launch; the
+    parameters' ``.grad`` are then the engine's gradient buffers).  Shapes beyond the warm call (frames x (points + 512) >= 2^30) raise
+    ``NotImplementedError`` from the constructor.
     """
 
     def __init__(self, model, cano_pc, pc_list, cano_idx, pc_ref_list=None, flow_ref_list=None, trans_lr=1e-2,
                  weight_decay=0.0, assign_iter=0, assign_gap=5, downsample=4, lambda_assign=3e-1, lambda_flow=1.0,
                  use_robust_loss=False, smooth_weight=1e-2, knn_squared=False, use_assign_loss=True, src_idx=None, tgt_idx=None,
-                 warm_flow=False):
+                 warm_flow=False, recon_with_assign=False):
         _lib.require_gpu(cano_pc, pc_list)
+        self.recon_with_assign = bool(recon_with_assign)
+        self._cham_bytes = 0
+        if self.recon_with_assign:      # a shape the warm Chamfer call does not take: refused before anything is launched
+            B_, N_ = int(pc_list.shape[0]), int(pc_list.shape[1])
+            self._cham_bytes = int(_lib.lib().reart_chamfer_loss_workspace_bytes(B_, N_, N_))
+            if self._cham_bytes == 0:
+                raise NotImplementedError(f"KinematicEngine(recon_with_assign=True): {B_} frames of {N_} points are beyond "
+                                          "reart_chamfer_loss (frames <= 65535, frames x (points + 512) < 2^30)")
         self.root = hasattr(model, "root_6d") and hasattr(model, "root_t")      # networks/model.py:153-158
         self._pris = None
         if model.joint_type_list is not None:
@@ -132,6 +156,30 @@ class KinematicEngine:
         self._loss3 = torch.zeros((3,), dtype=torch.float32, device=self.dev)
         self._post_ws = torch.empty((max(int(_lib.lib().reart_kin_post_workspace_bytes(self.B, self.N, self._nr_max, 3)), 256),),
                                     dtype=torch.uint8, device=self.dev)
+        # recon_with_assign: the state of the warm Chamfer term (reart_chamfer_loss), built once.  One storage order serves the
+        # predicted cloud of every frame -- the parts move rigidly, the canonical cloud's locality carries over --, every observed
+        # frame is stored in its own; the buffers are owned here (a captured graph keeps their addresses)
+        self._order_x = self._inv_x = self._ys = self._seed_xy = self._seed_yx = self._fx_bits = self._cham_ws = None
+        self._xs = self._g_recon = self._loss_recon = self._loss4 = self._loss_tmp = None
+        self._cham_calls = 0
+        self._opt = None        # recon_with_assign: reart_amd.optim.Adam over self.params (created at the first step)
+        if self.recon_with_assign:
+            from .relax import kd_order
+
+            order = kd_order(self.cano).to(torch.int64)
+            inv = torch.empty_like(order)
+            inv[order] = torch.arange(self.N, dtype=torch.int64, device=self.dev)
+            self._order_x, self._inv_x = order.int().contiguous(), inv.int().contiguous()
+            self._ys = torch.stack([self.pc_list[b][kd_order(self.pc_list[b]).long()] for b in range(self.B)]).contiguous()
+            self._seed_xy = torch.full((self.B, self.N), -1, dtype=torch.int32, device=self.dev)
+            self._seed_yx = torch.full((self.B, self.N), -1, dtype=torch.int32, device=self.dev)
+            self._fx_bits = torch.zeros((self.B,), dtype=torch.int32, device=self.dev)
+            self._cham_ws = torch.empty((self._cham_bytes,), dtype=torch.uint8, device=self.dev)
+            self._xs = torch.empty((self.B, self.N, 3), dtype=torch.float32, device=self.dev)
+            self._g_recon = torch.zeros((self.B, self.N, 3), dtype=torch.float32, device=self.dev)
+            self._loss_recon = torch.zeros((), dtype=torch.float32, device=self.dev)
+            self._loss4 = torch.zeros((4,), dtype=torch.float32, device=self.dev)
+            self._loss_tmp = torch.zeros((), dtype=torch.float32, device=self.dev)
 
     # ---- pieces -----------------------------------------------------------------------------------------------------
     def _joint_values(self):
@@ -158,6 +206,13 @@ class KinematicEngine:
         _lib.check(rc, "reart_compute_pc_transform")
         if self.root:                                     # networks/model.py:153-158: x R^T + t per frame
             R = self._root_rotation()[0]
+            if self.recon_with_assign:
+                # the model's own expression, product then addition (KinematicModel.forward): the Chamfer term is discontinuous
+                # where a point has two nearest neighbours, so this mode computes the cloud bit for bit as the model does and a
+                # last-bit difference cannot send the engine and an autograd loop over the model down different branches
+                torch.matmul(self.pc_fk, R.transpose(1, 2), out=self.pc_trans)
+                self.pc_trans.add_(m.root_t.detach()[:, None, :])
+                return self.pc_trans
             torch.baddbmm(m.root_t.detach()[:, None, :], self.pc_fk, R.transpose(1, 2), out=self.pc_trans)
         return self.pc_trans
 
@@ -226,6 +281,20 @@ class KinematicEngine:
 
         L = _lib.lib()
         self.step_count += 1
+        if self.recon_with_assign:
+            # torch.optim.Adam's step in torch's own bits (reart_amd.optim.Adam: one launch, no synchronisation; its weight decay
+            # is torch's L2 form).  reart_adam_step_multi rounds a step differently in the last bit, and with the Chamfer term in
+            # every iteration one last bit can switch a point's nearest neighbour, where the gradient is discontinuous: this mode
+            # stays on the trajectory of an autograd loop with torch.optim.Adam.  The parameters' .grad are the engine's buffers.
+            if self._opt is None:
+                from .optim import Adam
+
+                self._opt = Adam(self.params, lr=self.lr, weight_decay=self.wd)
+            for p in self.params:
+                if p.grad is not self.grads[id(p)]:
+                    p.grad = self.grads[id(p)]
+            self._opt.step()
+            return
         grads = []
         for p in self.params:
             g = self.grads[id(p)]
@@ -341,12 +410,73 @@ class KinematicEngine:
                                             _lib.ptr(self._pc_src), _lib.stream())                 # pc_trans[:, src_idx], one launch
         _lib.check(rc, "reart_gather_points")
 
+    def _recon_term(self):
+        """recon_with_assign: recon_loss(pc_trans, pc_list) (networks/loss.py:24-29) and its gradient w.r.t. pc_trans as the warm
+        exact search's one call, on the stored clouds: self._loss_recon, self._g_recon (rows in the stored order), self._fx_bits.
+        Neighbours and distances are bit for bit ``knn_points``'s; a tie between distinct equidistant targets goes to the one stored
+        first in the k-d order (``ChamferLoss``'s rule).  The seeds are in/out and never change a result."""
+        L = _lib.lib()
+        B, N = self.B, self.N
+        rc = L.reart_gather_points(_lib.ptr(self.pc_trans), _lib.ptr(self._order_x), B, N, N, _lib.ptr(self._xs), _lib.stream())
+        _lib.check(rc, "reart_gather_points")
+        # y_unchanged: 0 on the first call with this workspace, 1 afterwards
+        rc = L.reart_chamfer_loss(_lib.ptr(self._xs), _lib.ptr(self._ys), B, N, N, _lib.ptr(self._seed_xy), _lib.ptr(self._seed_yx),
+                                  int(self._cham_calls > 0), None, None, None, None, _lib.ptr(self._loss_recon), _lib.ptr(self._g_recon),
+                                  None, _lib.ptr(self._fx_bits), _lib.ptr(self._cham_ws), self._cham_ws.numel(), _lib.stream())
+        _lib.check(rc, "reart_chamfer_loss")
+        self._cham_calls += 1
+
+    def recon_grad(self):
+        """recon_with_assign: the latest Chamfer gradient d recon_loss / d pc_trans [T-1,N,3] in the caller's point numbering."""
+        return self._g_recon.index_select(1, self._inv_x.long())
+
+    @property
+    def last_fx_bits(self):
+        """recon_with_assign: the fractional bits [T-1] of the latest Chamfer gradient's fixed-point sums (reart_chamfer_loss)."""
+        return self._fx_bits
+
     FUSED_POST = True   # reart_kin_post (nine launches); False: the same values as tensor expressions (_post_expressions)
 
-    def _post(self):
-        """Everything between the solve and Adam: matched targets, assignment (+ flow) loss, dL/d pc_trans, the FK backward."""
-        if not self.FUSED_POST or self.lap_state["cols"].dtype != torch.int32 or (self.refs is not None and min(int(r.shape[0]) for r, _ in self.refs) < 3):
-            return self._post_expressions()
+    def _post_recon(self, assign):
+        """_post of a recon_with_assign engine (reart_kin_post_recon: the launches of reart_kin_post): G = Chamfer gradient + the
+        pairs' term + the flow term, four losses.  ``assign`` False: the Chamfer-only form (n = 0) of the iterations before
+        assign_iter."""
+        L = _lib.lib()
+        n = int(self.src_idx.numel()) if assign else 0
+        warm = self._flow_term is not None
+        rc = L.reart_kin_post_recon(_lib.ptr(self.pc_trans), _lib.ptr(self.cano), self.B, self.N, self.cano_idx,
+                                    _lib.ptr(self._pc_src) if assign else None, _lib.ptr(self.tgt_pts) if assign else None,
+                                    _lib.ptr(self.lap_state["cols"]) if assign else None, _lib.ptr(self._slot) if assign else None, n,
+                                    self.lambda_assign, None if warm else _lib.ptr(self._ref_pad), None if warm else _lib.ptr(self._flow_pad),
+                                    None if warm else _lib.ptr(self._ref_len), self._nr_max, 3, self.euclid, self.lambda_flow,
+                                    int(self.robust), self.smooth, _lib.ptr(self._g_recon), _lib.ptr(self._inv_x), _lib.ptr(self._loss_recon),
+                                    _lib.ptr(self.G), _lib.ptr(self._matched_buf) if assign else None, _lib.ptr(self._loss4),
+                                    _lib.ptr(self._post_ws), self._post_ws.numel(), _lib.stream())
+        _lib.check(rc, "reart_kin_post_recon")
+        l4 = self._loss4
+        if warm:        # flow gradient onto G, its value into losses[1], the total redone in the order of losses[3]
+            self._flow_term.add_gradient(self.pc_trans, self.cano, self.G, l4[1])
+            torch.add(l4[0], l4[2], out=self._loss_tmp)
+            torch.add(self._loss_tmp, l4[1], out=l4[3])
+        losses = {}
+        if assign:
+            self.matched = self._matched_buf
+            losses["opt assignment loss"] = l4[0]
+        losses["recon Loss"] = l4[2]
+        if self.refs is not None:
+            losses["flow Loss"] = l4[1]
+        losses["total Loss"] = l4[3]
+        self._backward()
+        self.losses = losses
+
+    def _post(self, assign=True):
+        """Everything between the solve and Adam: matched targets, assignment (+ flow) loss, dL/d pc_trans, the FK backward.
+        ``assign`` False (recon_with_assign engines only): no pairs, the Chamfer-only form."""
+        if (not self.FUSED_POST or (assign and self.lap_state["cols"].dtype != torch.int32)
+                or (self.refs is not None and min(int(r.shape[0]) for r, _ in self.refs) < 3)):
+            return self._post_expressions(assign)
+        if self.recon_with_assign:
+            return self._post_recon(assign)
         L = _lib.lib()
         n = int(self.src_idx.numel())
         warm = self._flow_term is not None     # then reart_kin_post runs without references: its assignment branch overwrites G
@@ -370,9 +500,11 @@ class KinematicEngine:
         self._backward()
         self.losses = losses
 
-    def _post_expressions(self):
+    def _post_expressions(self, assign=True):
         """_post as the reference's tensor expressions (run_robot.py:177-209) over the per-frame operators: the form reart_kin_post
         replaced, kept as its check (tests/test_kinematic_engine_gpu.py)."""
+        if self.recon_with_assign:
+            return self._post_recon_expressions(assign)
         cols = self.lap_state["cols"].long()
         self.matched = self.tgt_pts.gather(1, cols[..., None].expand(-1, -1, 3))
         diff = self._pc_src - self.matched
@@ -389,10 +521,35 @@ class KinematicEngine:
         self._backward()
         self.losses = losses
 
+    def _post_recon_expressions(self, assign):
+        """_post_recon as tensor expressions that round as reart_kin_post_recon does (its check, and the path when FUSED_POST is
+        off or the columns are not int32): G = the Chamfer gradient in the caller's numbering, the pairs' term added at the
+        sampled points, then the flow term; total = (assignment + Chamfer) + flow, OperatorLoop's order."""
+        self.G.copy_(self._g_recon.index_select(1, self._inv_x.long()))
+        losses = {}
+        total = self._loss_recon
+        if assign:
+            cols = self.lap_state["cols"].long()
+            self.matched = self.tgt_pts.gather(1, cols[..., None].expand(-1, -1, 3))
+            diff = self._pc_src - self.matched
+            ass = self.lambda_assign * (diff * diff).sum()
+            self.G[:, self.src_idx] = self.G[:, self.src_idx] + (2.0 * self.lambda_assign) * diff
+            losses["opt assignment loss"] = ass
+            total = ass + total
+        losses["recon Loss"] = self._loss_recon
+        if self.refs is not None:
+            fl = self._flow_terms()
+            losses["flow Loss"] = fl
+            total = total + fl
+        losses["total Loss"] = total
+        self._backward()
+        self.losses = losses
+
     def _post_chamfer(self):
         """The Chamfer branch (run_robot.py:187-190: recon_loss = sum of the bidirectional per-point Chamfer distance,
         networks/loss.py:24-29) without autograd: both searches, then the gradient of each direction's distances w.r.t. the
-        predicted cloud (utils/chamfer.py:195-209 with grad_dists = 1), flow terms, FK backward."""
+        predicted cloud (utils/chamfer.py:195-209 with grad_dists = 1), flow terms, FK backward.  (The default mode's branch; a
+        recon_with_assign engine never runs it.)"""
         from . import chamferdist_C as _C
 
         X, Y = self.pc_trans, self.pc_list
@@ -430,7 +587,11 @@ class KinematicEngine:
         and Adam, whose step count is a host value, stay eager): same launches, same results, a tenth of the host work."""
         if not self.use_assign or i < self.assign_iter:                   # run_robot.py:187-190
             self.forward()
-            self._post_chamfer()
+            if self.recon_with_assign:      # the warm Chamfer term and the consumer's Chamfer-only form; eager, as this branch is
+                self._recon_term()
+                self._post(assign=False)
+            else:
+                self._post_chamfer()
             self._adam()
             return self.losses
         if self._pc_src is None:
@@ -441,6 +602,13 @@ class KinematicEngine:
             self._pre()
             if self.GRAPHS and self.lap_solves >= 2:
                 self._g_pre = self._graph(self._pre)                      # (the warm-up inside recomputes the same forward)
+        if self.recon_with_assign:
+            # The Chamfer term does not depend on the optimum: in front of the re-solve.  Queued eagerly (five launches and the
+            # 4-byte memset of its reduction's counter), not captured with _pre: replayed from the captured graph beside an
+            # autograd loop in the same process, the call stopped writing its loss from the sixth iteration on (the gradient
+            # stayed right) -- measured on the MI355X, deterministic, cause not found; tests/test_kinematic_both_gpu.py
+            # (test_the_recon_loss_is_current_in_every_iteration) holds the eager form
+            self._recon_term()
         posted = False
         if self.lap_state.get("cols") is None or i % self.assign_gap == 0:                       # run_robot.py:165-178
             if self.lap_events is not None:

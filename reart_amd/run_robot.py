@@ -493,18 +493,26 @@ def make_projection_loop(args, model, cano_pc, pc_list, pc_ref_list=None, flow_r
     as the reference's README runs it (``--use_assign_loss --assign_iter 0``), its Chamfer branch (iterations before
     ``assign_iter``, runs without ``--use_assign_loss``), mixed joint types and root motion (the SAPIEN / real-scan variant of
     the model, networks/model.py:113-166); the base model outside the fused engine goes through ``OperatorLoop`` (PyTorch
-    autograd + torch.optim.Adam over the same operators), which also remains the engine's reference in the tests."""
-    # --recon_with_assign: KinematicEngine has no mode that adds the Chamfer loss to the assignment loss yet (its Chamfer
-    # branch is a composition of operators of its own): the operator loop computes that objective until it has
-    if args.model == "kinematic" and not getattr(args, "recon_with_assign", False):
+    autograd + torch.optim.Adam over the same operators), which also remains the engine's reference in the tests.
+    ``--recon_with_assign`` (Chamfer and assignment loss together) goes through ``OperatorLoop`` too, unless ``--fused_recon``
+    asks for the engine's ``recon_with_assign`` mode."""
+    # --recon_with_assign alone: the operator loop computes that objective (the routing tests/test_relax_both_gpu.py pins);
+    # with --fused_recon the engine does, in its recon_with_assign mode (the warm Chamfer term + reart_kin_post_recon)
+    both = bool(getattr(args, "recon_with_assign", False))
+    fused_recon = bool(getattr(args, "fused_recon", False))
+    if fused_recon and not (both and args.model == "kinematic"):
+        raise ValueError("--fused_recon is the kinematic engine's form of --recon_with_assign: it needs --model kinematic "
+                         "--recon_with_assign")
+    if args.model == "kinematic" and (not both or fused_recon):
         from reart_amd.kinematic_engine import KinematicEngine
 
+        mode = {"recon_with_assign": True} if fused_recon else {}
         return KinematicEngine(model, cano_pc, pc_list, args.cano_idx, pc_ref_list if args.use_flow_loss else None,
                                flow_ref_list if args.use_flow_loss else None, trans_lr=args.trans_lr,
                                weight_decay=args.weight_decay, assign_iter=args.assign_iter, assign_gap=args.assign_gap,
                                downsample=args.downsample, lambda_assign=args.lambda_assign, lambda_flow=args.lambda_flow,
                                use_robust_loss=args.use_robust_loss, use_assign_loss=args.use_assign_loss,
-                               warm_flow=bool(getattr(args, "fused_flow", False)))
+                               warm_flow=bool(getattr(args, "fused_flow", False)), **mode)
     return OperatorLoop(args, model, cano_pc, pc_list, pc_ref_list, flow_ref_list, tau_func)
 
 
@@ -886,7 +894,12 @@ def build_parser():
                    help="with --use_assign_loss: from --assign_iter on the assignment loss is ADDED to the Chamfer loss instead of "
                         "taking its place, as the reference's run_real.py:175 and run_sapien.py:174 do (recon Loss in every "
                         "iteration); the fused engine runs both in its Chamfer consumer, --model kinematic goes through the "
-                        "operator loop")
+                        "operator loop unless --fused_recon is given")
+    p.add_argument("--fused_recon", action="store_true",
+                   help="with --model kinematic --recon_with_assign: the autograd-free kinematic engine computes that objective "
+                        "(KinematicEngine(recon_with_assign=True): the Chamfer term as one warm-started call in front of the re-solve, "
+                        "its gradient, the pairs' term and the flow term added in one launch) instead of the operator loop; "
+                        "anything else with this flag is an error")
     p.add_argument("--fused_losses", action="store_true",
                    help="operator loop (the base model outside the fused engine): the Chamfer term as one warm-started call with a "
                         "fused backward, the T-1 flow blends as one call; same losses up to the summation order of the Chamfer sum")

@@ -639,6 +639,9 @@ def build_cli():
     p.add_argument("--recon_with_assign", action="store_true",
                    help="run_robot.py --recon_with_assign: from --assign_iter on the assignment loss is added to the Chamfer loss "
                         "(the reference's run_real.py:175), in the engines and in the projections")
+    p.add_argument("--fused_recon", action="store_true",
+                   help="--project --recon_with_assign: run_robot.py --fused_recon, the projections in the kinematic engine's "
+                        "recon_with_assign mode instead of the operator loop")
     return p
 
 
@@ -731,6 +734,7 @@ def projection_args(args, spec):
     kin.save_root = args.save_root
     kin.fused_ik = bool(getattr(args, "fused_ik", False))
     kin.recon_with_assign = bool(getattr(args, "recon_with_assign", False))
+    kin.fused_recon = bool(getattr(args, "fused_recon", False))
     kin.synthetic = spec.get("synthetic") is not None
     if kin.synthetic:
         kin.synthetic_frames = int(spec["frames"])
