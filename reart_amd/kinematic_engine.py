@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .networks.pointnet2_utils import farthest_point_sample, index_points
+from .utils import lap
 from .utils.flow_utils import blend_anchor_motion
 from .utils.kinematic_utils import _effective_joint_values
 
@@ -98,17 +98,10 @@ class KinematicEngine:
         # (``src_idx`` [n] / ``tgt_idx`` [T-1,n]: samples handed in instead -- the reference's CPU sampler starts from a random point,
         # networks/pointnet2_utils.py:90, so a trajectory the reference produced on a CPU comes with its samples:
         # tests/golden/kinematic_loop.npz)
-        num_fps = self.N // int(downsample)
-        zero = torch.zeros(1, dtype=torch.long, device=self.dev)
-        self.src_idx = (farthest_point_sample(self.cano[None], num_fps, start=zero, cuda_mode=True)[0] if src_idx is None
-                        else torch.as_tensor(src_idx, dtype=torch.long, device=self.dev).reshape(-1))          # [n]
-        tgt_idx = (farthest_point_sample(self.pc_list, num_fps, start=zero.expand(self.B), cuda_mode=True) if tgt_idx is None
-                   else torch.as_tensor(tgt_idx, dtype=torch.long, device=self.dev).reshape(self.B, -1))
         # the sampled targets are the COLUMNS of every re-solve of the run: numbered along a Z-order curve (lap.spatial_order)
-        from .utils.lap import spatial_order
-        self.tgt_order = spatial_order(index_points(self.pc_list, tgt_idx))                                     # [B,n] into the FPS order
-        self.tgt_idx = tgt_idx.gather(1, self.tgt_order)
-        self.tgt_pts = index_points(self.pc_list, self.tgt_idx).contiguous()                                    # [B,n,3]
+        sample = lap.AssignmentSample(self.cano, self.pc_list, downsample, src_idx, tgt_idx)
+        self.src_idx, self.tgt_order = sample.src_idx, sample.tgt_order                 # [n]; [B,n] into the FPS order
+        self.tgt_idx, self.tgt_pts = sample.tgt_idx, sample.tgt_pts                     # [B,n]; [B,n,3]
         self.matched = None
         self.lap_state = {}
         self.lap_solves = self.lap_fallbacks = 0
@@ -127,9 +120,7 @@ class KinematicEngine:
         self._side = None
         # reart_kin_post's inputs that never change: the sample slot of every canonical point, the frames' flow references padded
         # to one length; its buffers (owned here: a captured graph keeps their addresses)
-        n = int(self.src_idx.numel())
-        self._slot = torch.full((self.N,), -1, dtype=torch.int32, device=self.dev)
-        self._slot[self.src_idx] = torch.arange(n, dtype=torch.int32, device=self.dev)
+        n, self._slot = sample.n, sample.slot
         self._ref_pad = self._flow_pad = self._ref_len = None
         self._nr_max = 0
         if self.refs is not None:
@@ -357,22 +348,20 @@ class KinematicEngine:
     GRAPHS = True       # replay the launches around the solve from two captured graphs (False: every launch eagerly)
     SIDE_STREAMS = 6    # streams the per-frame flow blends of an iteration are dealt to
 
-    def _solve(self, pc_src, behind=None):
+    def _solve(self, pc_src, timer, behind=None):
         """The assignment refresh (run_robot.py:165-178) -> the solver's [B,4] statistics; the optimum is in lap_state["cols"].
+        ``timer``: the started ``lap.EventPair`` of this solve; its end is recorded behind the solve's launches, before the host waits.
         ``behind``: launches that only READ the optimum (the replay of the post graph), queued behind the re-solve BEFORE the host
         waits for its flags -- the GPU goes straight on while the host wakes up and reads them (75-85 us of every iteration
         otherwise: tools/solve_gaps.py) -- and queued once more in the rare case that the host then changed the columns (a tied
         or an uncertified problem).  Returns True when ``behind`` ran."""
-        from .utils import lap
-
         B, n = pc_src.shape[:2]
         ran = False
         if lap.InPlaceResolve.usable(self.lap_state, B, n):
             if self._inplace is None:
                 self._inplace = lap.InPlaceResolve(B, n, self.dev)
             self._inplace.begin(pc_src, self.tgt_pts, self.lap_state, stats=True)
-            if self.lap_events is not None:
-                self.lap_events[-1][1].record()
+            timer.end()
             if behind is not None:
                 behind()
                 ran = True
@@ -383,8 +372,7 @@ class KinematicEngine:
         else:       # the first solve (cold), sizes outside the chain forms: the general entry (its columns are a new tensor)
             _, fb, st = lap.linear_sum_assignment_points(pc_src.contiguous(), self.tgt_pts, self.lap_state, return_stats="full", device_cols=True)
             self._g_post = None                     # a graph that reads the columns must see the new tensor
-            if self.lap_events is not None:
-                self.lap_events[-1][1].record()
+            timer.end()
         self.lap_solves += 1
         self.lap_fallbacks += fb
         self.lap_stats = st
@@ -611,11 +599,8 @@ class KinematicEngine:
             self._recon_term()
         posted = False
         if self.lap_state.get("cols") is None or i % self.assign_gap == 0:                       # run_robot.py:165-178
-            if self.lap_events is not None:
-                ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                ev[0].record()
-                self.lap_events.append(ev)              # (the end is recorded right behind the re-solve's launches)
-            posted = self._solve(self._pc_src, behind=self._g_post.replay if self._g_post is not None else None)
+            timer = lap.EventPair(self.lap_events).start()      # (_solve records the end right behind the re-solve's launches)
+            posted = self._solve(self._pc_src, timer, behind=self._g_post.replay if self._g_post is not None else None)
         if posted:
             pass                                        # (the post graph went in behind the re-solve)
         elif self._g_post is not None:

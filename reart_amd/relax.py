@@ -168,7 +168,7 @@ class RelaxEngine:
         # in the caller's order; the optimisation problem is invariant to point order).
         order = {"kd": kd_order, "morton": morton_order}[os.environ.get("REART_ORDER", "kd")]
         self._perm = order(cano_pc) if spatial_sort else None
-        self._perm_frames = None
+        self._perm_frames = self._inv_frames = None
         if spatial_sort:
             cano_pc = cano_pc[self._perm]
             self._perm_frames = torch.stack([order(f) for f in pc_list])
@@ -275,10 +275,26 @@ class RelaxEngine:
         tail and of the linear assignment -- must see these, not ``self.cano`` / ``self.pc_list``."""
         if self._perm is None:
             return self.cano, self.pc_list
-        B, N = self._perm_frames.shape
-        inv_f = torch.empty_like(self._perm_frames)
-        inv_f.scatter_(1, self._perm_frames, torch.arange(N, device=self.device).expand(B, N))
-        return self.cano[self._inv], torch.gather(self.pc_list, 1, inv_f[..., None].expand(-1, -1, 3))
+        return self.cano[self._inv], torch.gather(self.pc_list, 1, self._inverse_frames()[..., None].expand(-1, -1, 3))
+
+    def _inverse_frames(self):
+        """[T-1,N]: the stored position of every point of every frame, by its index in the caller's order (the inverse of
+        ``_perm_frames``; fixed for the engine's life: built on first use)."""
+        if self._inv_frames is None:
+            B, N = self._perm_frames.shape
+            self._inv_frames = torch.empty_like(self._perm_frames)
+            self._inv_frames.scatter_(1, self._perm_frames, torch.arange(N, device=self.device).expand(B, N))
+        return self._inv_frames
+
+    def stored_indices(self, src_idx, tgt_idx):
+        """src_idx [n] (indices into the canonical cloud), tgt_idx [T-1,n] (indices into pc_list[b]) in the caller's point order
+        -> (src_stored [n], tgt_stored [T-1,n]), long: where the engine STORES those points -- the rows of the buffers its kernels
+        read and write (``_pc_trans``, ``_assign_map``)."""
+        src = src_idx.to(self.device).long().reshape(-1)
+        tgt = tgt_idx.to(self.device).long().reshape(self._assign_map.shape[0], -1)
+        if self._perm is not None:
+            src, tgt = self._inv[src], self._inverse_frames().gather(1, tgt)
+        return src, tgt
 
     def set_gumbel(self, noise):
         """Inject the Gumbel noise [N,P] used by every following step (tests); None = in-kernel Philox."""
@@ -301,16 +317,7 @@ class RelaxEngine:
         src_idx [n] (indices into the canonical cloud), tgt_idx [B,n] (indices into pc_list[b]), both in the
         caller's point order.  A captured graph is dropped when the mode changes (capture again).  On an engine built with
         ``recon_with_assign`` the term is added to the Chamfer loss instead of replacing it."""
-        B, N = self._assign_map.shape
-        src = src_idx.to(self.device).long().reshape(-1)
-        tgt = tgt_idx.to(self.device).long().reshape(B, -1)
-        if self._perm is not None:   # caller order -> internal storage order
-            src = self._inv[src]
-            if getattr(self, "_inv_frames", None) is None:      # fixed for the engine's life: built on first use
-                inv_f = torch.empty_like(self._perm_frames)
-                inv_f.scatter_(1, self._perm_frames, torch.arange(N, device=self.device).expand(B, N))
-                self._inv_frames = inv_f
-            tgt = self._inv_frames.gather(1, tgt)
+        src, tgt = self.stored_indices(src_idx, tgt_idx)
         self._assign_map.fill_(-1)
         self._assign_map[:, src] = tgt.to(torch.int32)
         lam32 = ctypes.c_float(lambda_assign).value       # the config holds fp32: compare what it would hold (0.3 != fp32(0.3))

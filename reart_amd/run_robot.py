@@ -42,7 +42,7 @@ import torch
 from reart_amd.knn_cuda import KNN
 from reart_amd.networks.loss import flow_loss, recon_loss
 from reart_amd.networks.model import BaseModel, KinematicModel
-from reart_amd.networks.pointnet2_utils import farthest_point_sample, index_points
+from reart_amd.networks.pointnet2_utils import index_points
 from reart_amd.relax import RelaxEngine
 from reart_amd.utils.chamfer import ChamferDistance, ChamferLoss
 from reart_amd.utils.flow_utils import FlowTerm, blend_anchor_motion, blend_anchor_motion_batch, pad_reference_sets
@@ -87,31 +87,50 @@ def flow_references(args, sample, device, seq_path=None):
             [complete[i + 1][t] - complete[i][s] for i, (s, t) in enumerate(zip(src_list, tgt_list))])
 
 
+def _cat(parts):
+    """torch.cat along dim 0; a single part is returned as it is (no copy, no launch)."""
+    return parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
+
+
 class AssignmentPhase:
     """The base model's assignment-loss phase (run_robot.py:164-187) on the fused ``RelaxEngine``.  Every ``assign_gap``
     iterations: forward of the coming iteration (``peek_forward``: the temperature and noise the step will use) -> the sampled
     source points (FPS of the canonical cloud, run_robot.py:167) -> optimal assignment to the sampled target points
     (``cdist`` + ``linear_sum_assignment`` in the reference, :170-176) -> the pairs go to the engine, which then runs the
     iterations up to the next refresh from a captured graph without touching the host.
-    Both FPS calls of the reference sample fixed clouds from a fixed start (its CUDA FPS starts at index 0): computed once.
+    Both FPS calls of the reference sample fixed clouds from a fixed start (its CUDA FPS starts at index 0): computed once
+    (``lap.AssignmentSample``, one per engine in ``parts``).
     The first refresh is a cold solve (raced auction + exact certificate); every later one re-solves from the previous
     optimum and potentials (``linear_sum_assignment_points``: shortest augmenting paths, the row reduction one chain per
-    wave, costs recomputed from the points, same certificate).  ``fallbacks`` counts matrices that went to the host solver."""
+    wave, costs recomputed from the points, same certificate).  ``fallbacks`` counts matrices that went to the host solver.
+
+    The phase drives 1..K engines of one shape through a *stepper*, the object whose ``step(n)`` and
+    ``capture(steps_per_graph)`` advance them: this constructor takes one engine, which is its own stepper;
+    ``AssignmentPhaseBatch`` takes the K engines of a ``RelaxBatch``.  With K engines every refresh gathers the sampled source
+    points of all of them and solves their K x (T-1) problems in ONE call -- one set of launches, every problem its own
+    workgroup(s) --, then hands each engine its pairs: rows k (T-1) ... of ``tgt_idx`` / ``tgt_order`` / ``tgt_pts`` /
+    ``lap_state["cols"]`` and row k of ``src_idx`` belong to engine k.  Each engine ends exactly as it would alone (the optimal
+    assignment does not depend on who else is in the call)."""
+
+    NATIVE = os.environ.get("REART_ASSIGN_NATIVE", "1") != "0"      # "0": every refresh through the host path's tensor operations
 
     def __init__(self, eng, cano_pc, pc_list, downsample, assign_gap, lambda_assign):
-        self.eng, self.gap, self.lam = eng, int(assign_gap), float(lambda_assign)
-        device = cano_pc.device
-        self.B, N = pc_list.shape[0], pc_list.shape[1]
-        self.n = N // downsample
-        zero = torch.zeros(1, dtype=torch.long, device=device)
-        self.src_idx = farthest_point_sample(cano_pc[None], self.n, start=zero, cuda_mode=True)                      # [1, n]
-        tgt_fps = farthest_point_sample(pc_list, self.n, start=zero.expand(self.B), cuda_mode=True)                  # [B, n]
+        self._setup(eng, [eng], [(cano_pc, pc_list)], downsample, assign_gap, lambda_assign)
+
+    def _setup(self, stepper, engines, clouds, downsample, assign_gap, lambda_assign):
+        """clouds: [(cano_pc, pc_list)] per engine, in the caller's point order."""
+        from reart_amd.utils.lap import AssignmentSample
+
+        self.stepper, self.engines = stepper, list(engines)
+        self.gap, self.lam = int(assign_gap), float(lambda_assign)
         # the sampled targets are the COLUMNS of every refresh: numbered along a Z-order curve (lap.spatial_order: the searches'
         # waves then hold neighbouring columns); the pairs a refresh returns are the same whatever the numbering
-        from reart_amd.utils.lap import spatial_order
-        self.tgt_order = spatial_order(index_points(pc_list, tgt_fps))                                               # [B, n] into the FPS order
-        self.tgt_idx = tgt_fps.gather(1, self.tgt_order)
-        self.tgt_pts = index_points(pc_list, self.tgt_idx).contiguous()
+        self.parts = [AssignmentSample(c, p, downsample) for c, p in clouds]
+        if len({tuple(s.tgt_idx.shape) for s in self.parts}) != 1:
+            raise ValueError("AssignmentPhase: the engines must share one shape")
+        self.B, self.n = self.parts[0].tgt_idx.shape
+        self.src_idx = _cat([s.src_idx[None] for s in self.parts])                                                   # [K, n]
+        self.tgt_order, self.tgt_idx, self.tgt_pts = (_cat([getattr(s, a) for s in self.parts]) for a in ("tgt_order", "tgt_idx", "tgt_pts"))
         self.lap_state = {}
         self.refreshes = self.fallbacks = 0
         self.events = None          # set to [] to collect a (start, end) torch.cuda.Event pair around every solve
@@ -120,54 +139,53 @@ class AssignmentPhase:
                                     # steps, mean row-reduction steps, most search steps, mean backward rounds)
         self.stats_raw = []         # per device-side refresh: the solver's [B,4] statistics words as written (tools/exp_tail.py)
         self.capture_guard = None   # a context-manager factory entered around the graph capture (the sweep's _CaptureGate)
-        self._have, self._inplace = False, None
+        self.work_guard = None      # a context-manager factory entered around every refresh (the sweep's gate, reader side)
+        self._have = False
+        # the device path's tables (_native_tables)
+        self._src_stored = self._slot = self._tgt_stored = self._src_pts = self._inplace = None
 
     def _native_tables(self):
-        """Index tables of the device-side refresh, in the engine's STORAGE order (built once): the stored position of every
-        sampled canonical point, the sample slot of every stored point (-1: not sampled), the stored position of every
-        sampled target point."""
-        eng, dev = self.eng, self.eng.device
-        N = eng._assign_map.shape[1]
-        src = self.src_idx[0].long()
-        tgt = self.tgt_idx.long()
-        if eng._perm is not None:
-            src = eng._inv[src]
-            if getattr(eng, "_inv_frames", None) is None:
-                inv_f = torch.empty_like(eng._perm_frames)
-                inv_f.scatter_(1, eng._perm_frames, torch.arange(N, device=dev).expand(self.B, N))
-                eng._inv_frames = inv_f
-            tgt = eng._inv_frames.gather(1, tgt)
-        slot = torch.full((N,), -1, dtype=torch.int32, device=dev)
-        slot[src] = torch.arange(self.n, dtype=torch.int32, device=dev)
-        self._src_stored, self._slot, self._tgt_stored = src.int().contiguous(), slot, tgt.int().contiguous()
-        self._src_pts = torch.empty((self.B, self.n, 3), device=dev)
+        """What the device-side refresh needs, built once.  Per engine, in the engine's STORAGE order: the stored position of
+        every sampled canonical point, the sample slot of every stored point (-1: not sampled), the stored position of every
+        sampled target point.  For all: the solver's source points and the re-solve itself."""
+        from reart_amd.utils import lap
+
+        dev, N = self.engines[0].device, self.parts[0].N
+        stored = [e.stored_indices(s.src_idx, s.tgt_idx) for e, s in zip(self.engines, self.parts)]
+        self._src_stored = [src.int().contiguous() for src, _ in stored]
+        self._slot = [lap.slot_table(src, N) for src, _ in stored]
+        self._tgt_stored = [tgt.int().contiguous() for _, tgt in stored]
+        self._src_pts = torch.empty((len(self.engines) * self.B, self.n, 3), device=dev)
+        self._inplace = lap.InPlaceResolve(len(self.engines) * self.B, self.n, dev)
 
     def _refresh_on_device(self):
-        """A refresh after the first, without a host-side tensor operation: gather (reart_gather_points) -> re-solve from the
-        previous optimum in place (lap.InPlaceResolve) -> pair map (reart_assign_pairs), all queued behind the forward; the
-        host waits for the B certificate flags only (an uncertified problem goes to scipy, as everywhere)."""
+        """A refresh after the first, without a host-side tensor operation: a gather per engine into one source batch
+        (reart_gather_points) -> ONE re-solve of all problems from the previous optimum in place (lap.InPlaceResolve) -> a pair
+        map per engine (reart_assign_pairs), all queued behind the forward; the host waits for the certificate flags only (an
+        uncertified problem goes to scipy, as everywhere)."""
         from reart_amd import _lib
         from reart_amd.utils import lap
 
-        eng, st, L = self.eng, self.lap_state, _lib.lib()
-        B, n, N = self.B, self.n, eng._assign_map.shape[1]
-        if self._inplace is None:
-            self._inplace = lap.InPlaceResolve(B, n, eng.device)
+        st, L, B, n, N = self.lap_state, _lib.lib(), self.B, self.n, self.parts[0].N
         self._inplace.launches.guard = self.capture_guard
         cols = st["cols"]
 
         def gather():
-            _lib.check(L.reart_gather_points(_lib.ptr(eng._pc_trans), _lib.ptr(self._src_stored), B, N, n, _lib.ptr(self._src_pts), _lib.stream()),
-                       "reart_gather_points")
+            for k, e in enumerate(self.engines):
+                _lib.check(L.reart_gather_points(_lib.ptr(e._pc_trans), _lib.ptr(self._src_stored[k]), B, N, n,
+                                                 _lib.ptr(self._src_pts[k * B:]), _lib.stream()), "reart_gather_points")
 
         def pairs():
-            _lib.check(L.reart_assign_pairs(_lib.ptr(cols), _lib.ptr(self._slot), _lib.ptr(self._tgt_stored), B, N, n,
-                                            _lib.ptr(eng._assign_map), _lib.stream()), "reart_assign_pairs")
+            for k, e in enumerate(self.engines):
+                _lib.check(L.reart_assign_pairs(_lib.ptr(cols[k * B:]), _lib.ptr(self._slot[k]), _lib.ptr(self._tgt_stored[k]), B, N, n,
+                                                _lib.ptr(e._assign_map), _lib.stream()), "reart_assign_pairs")
 
-        self._inplace.begin(self._src_pts, self.tgt_pts, st, stats=bool(self.collect_stats), before=gather, after=pairs,
-                            key=(eng._pc_trans.data_ptr(), eng._assign_map.data_ptr()))
-        fb, raw, changed = self._inplace.finish()
-        if changed:                                                       # the host rewrote columns (a tie, a host solve): the map again
+        key = tuple(e._pc_trans.data_ptr() for e in self.engines) + tuple(e._assign_map.data_ptr() for e in self.engines)
+        self._inplace.begin(self._src_pts, self.tgt_pts, st, stats=bool(self.collect_stats), before=gather, after=pairs, key=key)
+        # the refresh's own graph (lap.ReplayedLaunches) is captured here -- or, under a work_guard, by refresh() once the guard
+        # is left: a capture is the gate's writer
+        fb, raw, changed = self._inplace.finish(capture=self.work_guard is None)
+        if changed:                                                       # the host rewrote columns (a tie, a host solve): the maps again
             pairs()
         if raw is not None:
             self.stats_raw.append(raw)
@@ -184,68 +202,66 @@ class AssignmentPhase:
     def _device_path(self):
         from reart_amd.utils import lap
 
-        return (self.NATIVE and self.eng.cfg.use_assign and self.eng.cfg.lambda_assign == ctypes.c_float(self.lam).value
-                and lap.InPlaceResolve.usable(self.lap_state, self.B, self.n))
-
-    NATIVE = os.environ.get("REART_ASSIGN_NATIVE", "1") != "0"
+        lam32 = ctypes.c_float(self.lam).value
+        return (self.NATIVE and all(e.cfg.use_assign and e.cfg.lambda_assign == lam32 for e in self.engines)
+                and lap.InPlaceResolve.usable(self.lap_state, len(self.engines) * self.B, self.n))
 
     def refresh(self):
-        from reart_amd.utils.lap import linear_sum_assignment_points
+        """New pairs for every engine -> True when that changed the engines' loss mode (their graphs were dropped)."""
+        if self.work_guard is None:
+            return self._refresh()
+        with self.work_guard():
+            first = self._refresh()
+        if self._inplace is not None:           # the capture a finish(capture=False) left due: OUTSIDE the guard's reader section
+            self._inplace.capture()
+        return first
 
-        eng = self.eng
-        eng.peek_forward()
+    def _refresh(self):
+        from reart_amd.utils import lap
+
+        B, n = self.B, self.n
+        for e in self.engines:
+            e.peek_forward()
         if self._device_path():
-            if getattr(self, "_slot", None) is None:
+            if self._slot is None:
                 self._native_tables()
-            if self.events is not None:
-                ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                ev[0].record()
-            fb = self._refresh_on_device()
-            if self.events is not None:
-                ev[1].record()
-                self.events.append(ev)
-            self.fallbacks += fb
-            self.refreshes += 1
-            return False
-        src_pts = index_points(eng.pc_trans, self.src_idx.expand(self.B, self.n)).contiguous()
-        if self.events is not None:
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record()
-        if self.collect_stats:
-            cols, fb, st = linear_sum_assignment_points(src_pts, self.tgt_pts, self.lap_state, device_cols=True, return_stats="full")
-            self._log_stats(st)
+            with lap.EventPair(self.events):
+                fb = self._refresh_on_device()
+            first = False
         else:
-            cols, fb = linear_sum_assignment_points(src_pts, self.tgt_pts, self.lap_state, device_cols=True)
-        if self.events is not None:
-            ev[1].record()
-            self.events.append(ev)
+            src_pts = _cat([index_points(e.pc_trans, s.src_idx.expand(B, n)) for e, s in zip(self.engines, self.parts)]).contiguous()
+            with lap.EventPair(self.events):
+                if self.collect_stats:
+                    cols, fb, st = lap.linear_sum_assignment_points(src_pts, self.tgt_pts, self.lap_state, device_cols=True, return_stats="full")
+                    self._log_stats(st)
+                else:
+                    cols, fb = lap.linear_sum_assignment_points(src_pts, self.tgt_pts, self.lap_state, device_cols=True)
+            first = not self.engines[0].cfg.use_assign
+            for k, (e, s) in enumerate(zip(self.engines, self.parts)):
+                e.set_assignment(s.src_idx, s.tgt_idx.gather(1, cols[k * B:(k + 1) * B]), self.lam)
+            self._have = True
         self.fallbacks += fb
         self.refreshes += 1
-        first = not eng.cfg.use_assign
-        eng.set_assignment(self.src_idx[0], self.tgt_idx.gather(1, cols), self.lam)
-        self._have = True
         return first
 
     def run(self, i, n_iter, snapshot_gap=0, on_snapshot=None):
         """Iterations i .. n_iter-1 -> n_iter.  ``on_snapshot(k)`` after iteration k-1 whenever k % snapshot_gap == 0 or k == n_iter."""
-        eng = self.eng
         while i < n_iter:
             if not self._have or i % self.gap == 0:
-                if self.refresh() and n_iter - i > 1:
-                    # the engine's mode changed (its graph was dropped): one eager iteration, then a graph of the iterations
+                if self.refresh() and n_iter - i > 1 and self.gap > 1:
+                    # the engines' mode changed (their graph was dropped): one eager iteration, then a graph of the iterations
                     # between two refreshes
-                    if self.gap > 1:
-                        with (self.capture_guard() if self.capture_guard else contextlib.nullcontext()):
-                            i += eng.capture(steps_per_graph=self.gap - 1)
-                        # the capture's eager iteration has moved i: a refresh or a snapshot may be due right here
-                        # (assign_iter % assign_gap == assign_gap - 1: run_robot.py:165 refreshes at every i % gap == 0)
-                        if on_snapshot is not None and (i == n_iter or (snapshot_gap and i % snapshot_gap == 0)):
-                            on_snapshot(i)
-                        continue
+                    with (self.capture_guard() if self.capture_guard else contextlib.nullcontext()):
+                        i += self.stepper.capture(steps_per_graph=self.gap - 1)
+                    # the capture's eager iteration has moved i: a refresh or a snapshot may be due right here
+                    # (assign_iter % assign_gap == assign_gap - 1: run_robot.py:165 refreshes at every i % gap == 0)
+                    if on_snapshot is not None and (i == n_iter or (snapshot_gap and i % snapshot_gap == 0)):
+                        on_snapshot(i)
+                    continue
             nxt = (i // self.gap + 1) * self.gap                                       # next refresh
             snap = (i // snapshot_gap + 1) * snapshot_gap if snapshot_gap else n_iter
             chunk = max(1, min(nxt, snap, n_iter) - i)
-            eng.step(chunk)
+            self.stepper.step(chunk)
             i += chunk
             if on_snapshot is not None and (i == n_iter or (snapshot_gap and i % snapshot_gap == 0)):
                 on_snapshot(i)
@@ -260,111 +276,14 @@ class AssignmentPhase:
         return out
 
 
-class AssignmentPhaseBatch:
-    """The assignment phase of K instances of one shape that step in shared launches (``RelaxBatch``; the sweep over canonical
-    frames): every refresh gathers the sampled source points of all instances and solves their K x (T-1) assignment problems
-    in ONE call -- one set of launches, every problem its own workgroup(s) --, then hands each instance its pairs; the
-    iterations between refreshes replay one graph for all instances.  Each instance ends exactly as its own
-    ``AssignmentPhase`` would (the optimal assignment does not depend on who else is in the call)."""
+class AssignmentPhaseBatch(AssignmentPhase):
+    """``AssignmentPhase`` for the K instances of one shape that step in shared launches (``RelaxBatch``; the sweep over
+    canonical frames): the batch is the stepper, the iterations between refreshes replay one graph for all instances.
+    Nothing but the constructor differs."""
 
     def __init__(self, batch, clouds, downsample, assign_gap, lambda_assign):
         """clouds: [(cano_pc, pc_list)] per engine of ``batch``, in the caller's point order."""
-        self.batch, self.gap, self.lam = batch, int(assign_gap), float(lambda_assign)
-        self.parts = [AssignmentPhase(e, c, p, downsample, assign_gap, lambda_assign) for e, (c, p) in zip(batch.engines, clouds)]
-        if len({(ph.B, ph.n) for ph in self.parts}) != 1:
-            raise ValueError("AssignmentPhaseBatch: the instances must share one shape")
-        self.B, self.n = self.parts[0].B, self.parts[0].n
-        self.tgt_all = torch.cat([ph.tgt_pts for ph in self.parts], dim=0).contiguous()
-        self.lap_state = {}
-        self.refreshes = self.fallbacks = 0
-        self.capture_guard = None
-        self.work_guard = None      # a context-manager factory entered around every refresh (the sweep's gate, reader side)
-        self._have, self._inplace = False, None
-
-    def refresh(self):
-        if self.work_guard is None:
-            first = self._refresh()
-        else:
-            with self.work_guard():
-                first = self._refresh()
-        if self._inplace is not None:           # the refresh's own graph (lap.ReplayedLaunches): captured OUTSIDE the reader section
-            self._inplace.capture()             # of the gate -- a capture is its writer
-        return first
-
-    def _refresh(self):
-        from reart_amd.utils.lap import linear_sum_assignment_points
-
-        for ph in self.parts:
-            ph.eng.peek_forward()
-        if self._device_path():
-            self.fallbacks += self._refresh_on_device()
-            self.refreshes += 1
-            return False
-        src_all = torch.cat([index_points(ph.eng.pc_trans, ph.src_idx.expand(self.B, self.n)) for ph in self.parts], dim=0).contiguous()
-        cols, fb = linear_sum_assignment_points(src_all, self.tgt_all, self.lap_state, device_cols=True)
-        self.fallbacks += fb
-        self.refreshes += 1
-        first = not self.parts[0].eng.cfg.use_assign
-        for k, ph in enumerate(self.parts):
-            ph.eng.set_assignment(ph.src_idx[0], ph.tgt_idx.gather(1, cols[k * self.B:(k + 1) * self.B]), self.lam)
-        self._have = True
-        return first
-
-    def _device_path(self):
-        from reart_amd.utils import lap
-
-        return (AssignmentPhase.NATIVE and all(ph.eng.cfg.use_assign and ph.eng.cfg.lambda_assign == ctypes.c_float(self.lam).value for ph in self.parts)
-                and lap.InPlaceResolve.usable(self.lap_state, len(self.parts) * self.B, self.n))
-
-    def _refresh_on_device(self):
-        """AssignmentPhase._refresh_on_device for the K instances of a shared launch: K gathers into one source batch, ONE
-        re-solve of the K x (T-1) problems, K pair maps; the host waits for the certificate flags only."""
-        from reart_amd import _lib
-        from reart_amd.utils import lap
-
-        st, L, K, B, n = self.lap_state, _lib.lib(), len(self.parts), self.B, self.n
-        if self._inplace is None:
-            for ph in self.parts:
-                ph._native_tables()
-            self._src_all = torch.empty((K * B, n, 3), device=self.parts[0].eng.device)
-            self._inplace = lap.InPlaceResolve(K * B, n, self._src_all.device)
-        self._inplace.launches.guard = self.capture_guard
-        cols = st["cols"]
-
-        def gather():
-            for k, ph in enumerate(self.parts):
-                N = ph.eng._assign_map.shape[1]
-                _lib.check(L.reart_gather_points(_lib.ptr(ph.eng._pc_trans), _lib.ptr(ph._src_stored), B, N, n,
-                                                 _lib.ptr(self._src_all[k * B:]), _lib.stream()), "reart_gather_points")
-
-        def pairs():
-            for k, ph in enumerate(self.parts):
-                N = ph.eng._assign_map.shape[1]
-                _lib.check(L.reart_assign_pairs(_lib.ptr(cols[k * B:]), _lib.ptr(ph._slot), _lib.ptr(ph._tgt_stored), B, N, n,
-                                                _lib.ptr(ph.eng._assign_map), _lib.stream()), "reart_assign_pairs")
-
-        key = tuple(ph.eng._pc_trans.data_ptr() for ph in self.parts) + tuple(ph.eng._assign_map.data_ptr() for ph in self.parts)
-        self._inplace.begin(self._src_all, self.tgt_all, st, before=gather, after=pairs, key=key)
-        fb, _, changed = self._inplace.finish(capture=False)              # (refresh() captures, outside the gate's reader section)
-        if changed:
-            pairs()
-        return fb
-
-    def run(self, i, n_iter):
-        while i < n_iter:
-            if not self._have or i % self.gap == 0:
-                if self.refresh() and n_iter - i > 1 and self.gap > 1:
-                    with (self.capture_guard() if self.capture_guard else contextlib.nullcontext()):
-                        i += self.batch.capture(steps_per_graph=self.gap - 1)     # one eager iteration, then the graph between refreshes
-                    continue                                                       # (a refresh may be due at the new i)
-            nxt = (i // self.gap + 1) * self.gap
-            chunk = max(1, min(nxt, n_iter) - i)
-            self.batch.step(chunk)
-            i += chunk
-        return i
-
-    def report(self):
-        return {"assign_refreshes": self.refreshes, "lap_fallbacks": self.fallbacks}
+        self._setup(batch, batch.engines, clouds, downsample, assign_gap, lambda_assign)
 
 
 class OperatorLoop:
@@ -376,7 +295,6 @@ class OperatorLoop:
     def __init__(self, args, model, cano_pc, pc_list, pc_ref_list=None, flow_ref_list=None, tau_func=None):
         self.args, self.model, self.cano_pc, self.pc_list = args, model, cano_pc, pc_list
         self.pc_ref_list, self.flow_ref_list, self.tau_func = pc_ref_list, flow_ref_list, tau_func
-        device = cano_pc.device
         # --fused_adam: the same optimiser with its step as one launch (reart_amd.optim.Adam; same groups, options and state)
         Adam = torch.optim.Adam
         if getattr(args, "fused_adam", False):
@@ -409,15 +327,16 @@ class OperatorLoop:
         self.lap_solves = self.lap_fallbacks = 0
         self.lap_events = None      # set to [] to collect a (start, end) torch.cuda.Event pair around every re-solve
         if args.use_assign_loss:
-            # run_robot.py:167-169: both FPS calls sample fixed clouds (start 0 on the reference's CUDA path): once
-            num_fps = pc_list.shape[1] // args.downsample
-            zero = torch.zeros(1, dtype=torch.long, device=device)
-            self.src_idx = farthest_point_sample(cano_pc[None], num_fps, start=zero, cuda_mode=True).expand(pc_list.shape[0], num_fps)
-            self.tgt_pts = index_points(pc_list, farthest_point_sample(pc_list, num_fps, start=zero.expand(pc_list.shape[0]),
-                                                                       cuda_mode=True))
+            # run_robot.py:167-169: both FPS calls sample fixed clouds (start 0 on the reference's CUDA path): once.  The columns
+            # stay in FPS order: this loop only gathers the matched points, and its potentials and ties are pinned to that order
+            from reart_amd.utils.lap import AssignmentSample
+
+            sample = AssignmentSample(cano_pc, pc_list, args.downsample, z_order=False)
+            self.src_idx = sample.src_idx.expand(pc_list.shape[0], sample.n)
+            self.tgt_idx, self.tgt_order, self.tgt_pts = sample.tgt_idx, sample.tgt_order, sample.tgt_pts
 
     def iteration(self, i):
-        from reart_amd.utils.lap import cdist, linear_sum_assignment_batch, linear_sum_assignment_points
+        from reart_amd.utils.lap import EventPair, cdist, linear_sum_assignment_batch, linear_sum_assignment_points
 
         args, model, cano_pc, pc_list = self.args, self.model, self.cano_pc, self.pc_list
         kwargs = {"tau": self.tau_func(cur_iter=i + 1)} if args.model == "base" else {}
@@ -428,9 +347,7 @@ class OperatorLoop:
             if self.matched is None or i % args.assign_gap == 0:  # run_robot.py:165-178
                 # certified optimum on the GPU; an uncertified matrix falls back to scipy on the host, so this is
                 # always the assignment the reference's linear_sum_assignment / parallel_lap returns
-                if self.lap_events is not None:
-                    ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                    ev[0].record()
+                timer = EventPair(self.lap_events).start()
                 if self.lap_state is not None:      # slowly moving problems: re-solve from the previous optimum
                     cols, fb, self.lap_stats = linear_sum_assignment_points(pc_src.detach(), self.tgt_pts, self.lap_state,
                                                                             return_stats="full", device_cols=True)
@@ -443,9 +360,7 @@ class OperatorLoop:
                     if st_ is not None and lap_.canonicalize(pc_src.detach().contiguous(), self.tgt_pts.contiguous(), st_):
                         rows_ = np.arange(pc_src.shape[1], dtype=np.int64)
                         assign = [(rows_, c_) for c_ in st_["cols"].cpu().numpy().astype(np.int64)]
-                if self.lap_events is not None:
-                    ev[1].record()
-                    self.lap_events.append(ev)
+                timer.end()
                 self.lap_solves += 1
                 self.lap_fallbacks += fb
                 if self.lap_state is None:

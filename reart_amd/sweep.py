@@ -210,8 +210,9 @@ def run_sweep_engines(instances, make_engine, n_iter, device, per_gpu=3, chunk=1
     does not implement) falls back to the streams path for that group; it never aborts the sweep.
     ``assign = dict(assign_iter, assign_gap, downsample, lambda_assign)``: the README recipe's second phase
     (run_robot.py:164-187, ``--use_assign_loss``) -- after ``assign_iter`` iterations the Chamfer loss gives way to the
-    assignment loss, its pairs refreshed every ``assign_gap`` iterations; a batch group solves the problems of all its
-    instances in one call per refresh (``run_robot.AssignmentPhaseBatch``) and keeps stepping in shared launches.
+    assignment loss, its pairs refreshed every ``assign_gap`` iterations (``run_robot.AssignmentPhase``); a batch group hands
+    the phase its ``RelaxBatch``: the problems of all its instances are solved in one call per refresh, and it keeps stepping in
+    shared launches.
     ``on_finish(inst, spec, engine, energy dict or None)`` is called once per finished instance (the command line writes
     the instance's result files there).  ``groups_in_flight``: how many groups of the recipe sweep run concurrently (each
     with its engines, graphs, a stream and a host thread); the rest are built when a slot frees up.
@@ -306,21 +307,31 @@ def run_sweep_engines(instances, make_engine, n_iter, device, per_gpu=3, chunk=1
     first_phase = n_iter if assign is None else min(int(assign["assign_iter"]), n_iter)
     lap_counts = {"assign_refreshes": 0, "lap_fallbacks": 0}
 
+    def assignment_phase(entries, batch=None):
+        """The assignment phase of ``entries`` -- host-driven (a refresh reads its certificates) -- up to n_iter: in the shared
+        launches of ``batch``, or (one entry) on the entry's own engine."""
+        from .run_robot import AssignmentPhase, AssignmentPhaseBatch
+
+        recipe = (assign["downsample"], assign["assign_gap"], assign["lambda_assign"])
+        guarded = batch is not None and concurrent
+        with (gate.tail() if guarded else contextlib.nullcontext()):          # (allocates: not while another group captures)
+            if batch is not None:
+                ph = AssignmentPhaseBatch(batch, [e[2].caller_clouds() for e in entries], *recipe)
+            else:
+                ph = AssignmentPhase(entries[0][2], *entries[0][2].caller_clouds(), *recipe)
+        ph.capture_guard = gate.capture
+        ph.work_guard = gate.tail if guarded else None
+        done = ph.run(first_phase, n_iter)
+        lap_counts["assign_refreshes"] += ph.refreshes
+        lap_counts["lap_fallbacks"] += ph.fallbacks
+        return done
+
     def enqueue(live, plan):
         batched = set()
         for batch, part, used in plan:
             batch.step(first_phase - used)
-            if first_phase < n_iter:          # the assignment phase: host-driven (a refresh reads its certificates), shared launches
-                from .run_robot import AssignmentPhaseBatch
-
-                with (gate.tail() if concurrent else contextlib.nullcontext()):      # (allocates: not while another group captures)
-                    ph = AssignmentPhaseBatch(batch, [e[2].caller_clouds() for e in part], assign["downsample"], assign["assign_gap"],
-                                              assign["lambda_assign"])
-                ph.capture_guard = gate.capture
-                ph.work_guard = gate.tail if concurrent else None
-                ph.run(first_phase, n_iter)
-                lap_counts["assign_refreshes"] += ph.refreshes
-                lap_counts["lap_fallbacks"] += ph.fallbacks
+            if first_phase < n_iter:
+                assignment_phase(part, batch)
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream(device))
             for e in part:
@@ -335,15 +346,9 @@ def run_sweep_engines(instances, make_engine, n_iter, device, per_gpu=3, chunk=1
                         e[2].step(n)
                     e[4] += n
         if first_phase < n_iter:                          # streams: the assignment phase, one instance after the other
-            from .run_robot import AssignmentPhase
-
             for e in rest:
                 with torch.cuda.stream(e[3]):
-                    ph = AssignmentPhase(e[2], *e[2].caller_clouds(), assign["downsample"], assign["assign_gap"], assign["lambda_assign"])
-                    ph.capture_guard = gate.capture
-                    e[4] = ph.run(first_phase, n_iter)
-                lap_counts["assign_refreshes"] += ph.refreshes
-                lap_counts["lap_fallbacks"] += ph.fallbacks
+                    e[4] = assignment_phase([e])
         for e in rest:
             e[5] = torch.cuda.Event()
             e[5].record(e[3])

@@ -4,6 +4,7 @@ on the GPU (``reart_lap_auction``: epsilon-scaling auction + exact dual certific
 ``reart_lap_resolve_large`` for 4096 < n <= 8192).  A matrix whose certificate does not close is solved with scipy on the host, so the result is always
 an optimal assignment."""
 import contextlib
+import functools
 import os
 
 import numpy as np
@@ -646,6 +647,66 @@ def spatial_order(pts):
     return torch.argsort(code, dim=1, stable=True)
 
 
+def slot_table(idx, N):
+    """idx [n] (distinct point indices) -> [N] int32: the position in ``idx`` of every point, -1 for a point not in it."""
+    slot = torch.full((N,), -1, dtype=torch.int32, device=idx.device)
+    slot[idx] = torch.arange(idx.numel(), dtype=torch.int32, device=idx.device)
+    return slot
+
+
+class AssignmentSample:
+    """The sampled assignment problem of a run (run_robot.py:167-169): n = N // downsample points of the canonical cloud (the
+    rows) against n points of every frame (the columns), both by FPS from start 0 -- the reference samples fixed clouds from a
+    fixed start on its CUDA path, so once per run.  ``src_idx`` [n] / ``tgt_idx`` [B,n] handed in take the place of the FPS calls
+    (the reference's CPU sampler starts from a random point, networks/pointnet2_utils.py:90: a trajectory it produced on a CPU
+    comes with its samples).  ``z_order``: the columns are numbered along a Z-order curve (``spatial_order``) --
+    ``tgt_order`` [B,n] into the FPS order, ``tgt_idx`` the FPS sample in that numbering; the pairs a solve returns are the same
+    whatever the numbering, potentials and the choice among tied optima are not, so a loop pinned to the FPS order turns it off
+    (``tgt_order`` None).  ``tgt_pts`` [B,n,3]: the columns' points; ``slot`` [N] int32: the sample slot of every canonical
+    point, -1 if not sampled (built on first use)."""
+
+    def __init__(self, cano_pc, pc_list, downsample, src_idx=None, tgt_idx=None, z_order=True):
+        from ..networks.pointnet2_utils import farthest_point_sample, index_points
+
+        dev, (B, self.N) = cano_pc.device, pc_list.shape[:2]
+        n = self.N // int(downsample)
+        zero = torch.zeros(1, dtype=torch.long, device=dev)
+        self.src_idx = (farthest_point_sample(cano_pc[None], n, start=zero, cuda_mode=True)[0] if src_idx is None
+                        else torch.as_tensor(src_idx, dtype=torch.long, device=dev).reshape(-1))
+        tgt_idx = (farthest_point_sample(pc_list, n, start=zero.expand(B), cuda_mode=True) if tgt_idx is None
+                   else torch.as_tensor(tgt_idx, dtype=torch.long, device=dev).reshape(B, -1))
+        self.tgt_order = spatial_order(index_points(pc_list, tgt_idx)) if z_order else None
+        self.tgt_idx = tgt_idx.gather(1, self.tgt_order) if z_order else tgt_idx
+        self.tgt_pts = index_points(pc_list, self.tgt_idx).contiguous()
+        self.n = int(self.src_idx.numel())
+
+    @functools.cached_property
+    def slot(self):
+        return slot_table(self.src_idx, self.N)
+
+
+class EventPair:
+    """A (start, end) pair of timing events around a solve, kept in ``log`` -- the list a loop collects them in, or None: then
+    nothing is recorded.  ``with EventPair(log): ...`` brackets a block; ``start()`` / ``end()`` where the end belongs in the
+    middle of one (right behind the launches, before the host waits for them)."""
+
+    def __init__(self, log):
+        self.log, self.pair = log, None
+
+    def start(self):
+        if self.log is not None:
+            self.pair = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+            self.pair[0].record()
+            self.log.append(self.pair)
+        return self
+
+    def end(self, *exc):
+        if self.pair is not None:
+            self.pair[1].record()
+
+    __enter__, __exit__ = start, end
+
+
 class ReplayedLaunches:
     """The launches of one refresh, queued eagerly until the same ``key`` (every address and launch parameter the closure
     uses) has come ``after`` times in a row, then captured ONCE into a graph and replayed.  A refresh is ~18 launches (passes,
@@ -688,8 +749,8 @@ class InPlaceResolve:
     see the new optimum at the same addresses.  The host waits for the B certificate flags (and, on request, the B x 4
     statistics words) and nothing else; an uncertified problem goes to scipy like everywhere.  ``usable(state, B, n)`` says
     whether the state qualifies (a first call has to go through ``linear_sum_assignment_points``).  The ONE device-side refresh:
-    the kinematic engine and the assignment phases (run_robot.AssignmentPhase[Batch]) differ in the launches they let ride with
-    the solve (``begin``) and in when the graph is captured (``finish`` / ``capture``)."""
+    the kinematic engine and the assignment phase (run_robot.AssignmentPhase, for one engine or the K of a shared launch) differ
+    in the launches they let ride with the solve (``begin``) and in when the graph is captured (``finish`` / ``capture``)."""
 
     def __init__(self, B, n, device):
         self.B, self.n, self.device = B, n, device
