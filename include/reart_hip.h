@@ -703,6 +703,43 @@ int reart_three_interpolate(const float *xyz1, const float *xyz2, const float *p
                             int N, int S2, int D, float *out, int ldo, int col0,
                             void *workspace, size_t workspace_bytes, void *stream);
 
+/* First-order backward of reart_mlp_layer (csrc/pointnet_grad.hip).  The layer is A = relu?(X Wt + b), Y = the max over groups
+ * of pool_k rows of A, or A itself.  The operand description (X / ldx, or gather_idx / K / S / Npts / F / D / Q / C / xyz_first),
+ * Wt, rows, Cin, Cout, relu and pool_k are the forward's; A [rows, Cout] is what reart_mlp_layer writes with pool_k = 0 (for an
+ * un-pooled layer: its output); dY [rows (/pool_k), lddy] is read at columns dycol0 .. dycol0 + Cout.
+ *   dZ[r,c] = dY[group(r),c] where row r is selected and (with relu) A[r,c] > 0, else exactly 0.  Without pooling every row is
+ *   selected; with pooling the LOWEST row of the group whose A equals the group's maximum (with relu a group whose maximum is 0
+ *   selects nothing).
+ * Outputs, each NULL = not wanted and not computed:
+ *   dWt [Cin, Cout] = X^T dZ and dbias [Cout] = column sums of dZ, on v_mfma_f32_32x32x2_f32: the rows are cut into chunks of
+ *     REART_MLP_GRAD_ROW_CHUNK, each chunk's tile goes to the workspace, the tiles are added in ascending chunk order (no
+ *     floating-point atomics: two runs agree in every bit).  A gathered X is formed element by element as the forward forms it
+ *     (the same float32 Q - C) and never materialised; a gather index outside [0, Npts) contributes a zero row;
+ *   dX [rows, lddx] (plain input only) = dZ Wt^T, computed by reart_mlp_layer on dZ with the transposed weight;
+ *   dF [B*Npts, D] (gathered input only; B = rows / (S*K)): the feature columns of dX summed over the rows that name the point,
+ *     in ascending row order (inverse lists by a stable counting sort); a point no row names gets exactly 0, an index outside
+ *     [0, Npts) is skipped, the xyz columns are dropped (coordinates get no gradient).
+ * Limits and error codes are reart_mlp_layer's; dX with a gathered input or dF with a plain one: REART_ERR_INVALID_ARG.
+ * Non-finite input gives meaningless values, never an out-of-range access.
+ * workspace: reart_mlp_layer_backward_scratch_bytes(rows, Cin, Cout, B, Npts, D) with B = Npts = D = 0 for a plain input. */
+#define REART_MLP_GRAD_ROW_CHUNK 256
+size_t reart_mlp_layer_backward_scratch_bytes(int rows, int Cin, int Cout, int B, int Npts, int D);
+int reart_mlp_layer_backward(const float *X, int ldx, const int64_t *gather_idx, int K, int S, int Npts,
+                             const float *F, int D, const float *Q, const float *C, int xyz_first,
+                             const float *Wt, int rows, int Cin, int Cout, int relu, int pool_k,
+                             const float *A, const float *dY, int lddy, int dycol0,
+                             float *dWt, float *dbias, float *dX, int lddx, float *dF,
+                             void *workspace, size_t workspace_bytes, void *stream);
+
+/* Backward of reart_three_interpolate with respect to points2: dpoints2[b,s,:] = sum of w[b,n,j] * dOut[b*N + n, col0 .. col0 + D)
+ * over the pairs (n, j) with idx3[b,n,j] = s, in ascending (n, j) (the same inverse lists as above); idx3 and w are the forward's
+ * (reart_three_nn, w_j = (1 / (d_j + 1e-8)) / ((w_0 + w_1) + w_2)).  A coarse point no fine point selects gets exactly 0.
+ * dOut [B*N, ldo]; dpoints2 [B,S2,D]; weights: NULL, or [B,N,3] to receive w.  Limits as reart_three_interpolate. */
+size_t reart_three_interpolate_backward_scratch_bytes(int B, int N, int S2);
+int reart_three_interpolate_backward(const float *xyz1, const float *xyz2, const float *dOut, int ldo, int col0,
+                                     int B, int N, int S2, int D, float *dpoints2, float *weights,
+                                     void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------ */
 /* Exact K-NN against static target sets (uniform grid)                      */
 /* ------------------------------------------------------------------------ */

@@ -31,6 +31,7 @@ STRUCT_MAX_P = 64        # parts of reart_structure_term / reart_rel_trans_backw
 STRUCT_MAX_E = 4096      # their edges: a part's incidence list is held in LDS
 CONN_MAX_N = 65536       # REART_CONN_MAX_N: points of reart_connection_select / reart_connection_term (two indices in 32 bits of a key)
 CONN_MAX_K = 64          # REART_CONN_MAX_K: pairs per edge, one wave's list
+MLP_GRAD_ROW_CHUNK = 256  # REART_MLP_GRAD_ROW_CHUNK: rows per partial tile of reart_mlp_layer_backward's dWt / dbias
 ADAM_MAX_TENSORS = 32   # REART_ADAM_MAX_TENSORS: records of one reart_adam_groups call, passed by value to its kernel
 
 # name -> (restype, argtypes); mirrors include/reart_hip.h one to one
@@ -105,6 +106,11 @@ PROTOTYPES = {
     "reart_three_nn": (c_int, [P, P, c_int, c_int, c_int, P, P, P]),
     "reart_three_interpolate_workspace_bytes": (c_size_t, [c_int] * 3),
     "reart_three_interpolate": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P, c_int, c_int, P, c_size_t, P]),
+    "reart_mlp_layer_backward_scratch_bytes": (c_size_t, [c_int] * 6),
+    "reart_mlp_layer_backward": (c_int, [P, c_int, P, c_int, c_int, c_int, P, c_int, P, P, c_int, P, c_int, c_int, c_int, c_int, c_int,
+                                         P, P, c_int, c_int, P, P, P, c_int, P, P, c_size_t, P]),
+    "reart_three_interpolate_backward_scratch_bytes": (c_size_t, [c_int] * 3),
+    "reart_three_interpolate_backward": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, c_size_t, P]),
     "reart_grid_knn_workspace_bytes": (c_size_t, [c_int] * 2),
     "reart_grid_knn": (c_int, [P, P, c_int, c_int, P, c_int, c_int, P, P, P, c_size_t, P]),
     "reart_knn_points_warm_workspace_bytes": (c_size_t, [c_int] * 4),

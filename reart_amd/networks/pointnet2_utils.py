@@ -13,11 +13,20 @@ true whenever a GPU is present) -- mirrored here as ``CUDA = True``, because thi
 
 The layer classes (``PointNetSetAbstraction``, ``PointNetSetAbstractionMsg``, ``PointNetFeaturePropagation``) carry the
 reference's constructor arguments, channel-first ``forward`` shapes and parameter names (``mlp_convs`` / ``mlp_bns``,
-``conv_blocks`` / ``bn_blocks``: its checkpoints load with ``strict=True``).  They are inference-only (``forward`` in
-training mode raises): BatchNorm uses its running statistics, folded into the 1x1 conv, and the grouped tensor is never
-built -- the gather, the conv stack and the max over a group run in ``reart_mlp_layer`` / the fused chain kernels.
-``forward`` takes two keyword-only extras, ``fps_start`` ([B] first index of the farthest point sampling) and ``cuda_mode``
-(the sampling rules, None: the module switch ``CUDA``), with the meaning they have in ``PointNet2Msg2.forward``.
+``conv_blocks`` / ``bn_blocks``: its checkpoints load with ``strict=True``).  They run in ``eval()`` only (``forward`` in
+training mode raises: batch statistics are not built): BatchNorm uses its running statistics, folded into the 1x1 conv, and
+the grouped tensor is never built -- the gather, the conv stack and the max over a group run in ``reart_mlp_layer`` / the
+fused chain kernels.
+``forward`` takes keyword-only extras: ``fps_start`` ([B] first index of the farthest point sampling) and ``cuda_mode``
+(the sampling rules, None: the module switch ``CUDA``), with the meaning they have in ``PointNet2Msg2.forward``, and ``grad``.
+
+``grad=False`` (the default) is inference: nothing returned requires grad.  ``grad=True`` (``forward``, ``run``, ``pool_all``;
+``eval()`` only, autograd enabled, float32 contiguous operands) returns the same bits with a FIRST-ORDER graph from the feature
+output to the incoming features (``points`` / ``points1`` / ``points2``) and to ``conv.weight``, ``conv.bias``, ``bn.weight``,
+``bn.bias`` of the stacks, whichever require grad (``reart_mlp_layer_backward`` / ``reart_three_interpolate_backward``).
+Coordinates get NO gradient and ``xyz.requires_grad`` is ignored: not the ``xyz - centre`` columns, not the centres
+(``new_xyz`` carries no graph), not the interpolation weights.  The stacks run layer by layer on the current stream; two runs
+agree in every bit; nothing synchronises with the host.
 """
 import torch
 import torch.nn as nn
@@ -131,7 +140,7 @@ def sample_and_group_all(xyz, points):
 
 
 class _InferenceLayer(nn.Module):
-    """What the three layer classes share: inference only, cached BatchNorm folds dropped when the parameters move."""
+    """What the three layer classes share: eval() only, cached BatchNorm folds dropped when the parameters move."""
 
     def invalidate_fold(self):
         for m in self.modules():
@@ -155,6 +164,21 @@ class _InferenceLayer(nn.Module):
         if self.training:
             raise RuntimeError(f"{type(self).__name__} is inference-only here (call .eval())")
         _lib.require_gpu(*tensors)
+
+    def _call(self, grad, fn):
+        """``fn(grad)`` under torch.no_grad() (inference), or -- grad=True -- with autograd, which must be enabled."""
+        if not grad:
+            with torch.no_grad():
+                return fn(False)
+        from .feature_extractor import require_grad_mode
+
+        require_grad_mode(type(self).__name__)
+        return fn(True)
+
+
+def _coords(t):
+    """Coordinates take no part in the graph."""
+    return None if t is None else t.detach()
 
 
 def _last(t):
@@ -193,12 +217,21 @@ class PointNetSetAbstractionMsg(_InferenceLayer):
         return new_xyz, [query_ball_point(radius, K, xyz, new_xyz, cuda_mode=cuda_mode)
                          for radius, K in zip(self.radius_list, self.nsample_list)]
 
-    def run(self, xyz, feats, start=None, cuda_mode=None, sampled=None):
+    def run(self, xyz, feats, start=None, cuda_mode=None, sampled=None, grad=False):
         """xyz [B,N,3], feats [B,N,D] (channel-last) or None -> new_xyz [B,S,3], new_feats [B,S,sum C]."""
         from .feature_extractor import grouped_mlp
 
         B, N, _ = xyz.shape
         S = self.npoint
+        if grad:
+            self._check(xyz, feats)
+            xyz = _coords(xyz)
+            with torch.no_grad():
+                new_xyz, idx_list = sampled if sampled is not None else self.sample(xyz, start=start, cuda_mode=cuda_mode)
+            Q, F, C = xyz.reshape(B * N, 3), _flat(feats), new_xyz.reshape(B * S, 3)
+            outs = [grouped_mlp(self.conv_blocks[i], self.bn_blocks[i], dict(idx=idx, F=F, Q=Q, C=C, Npts=N, xyz_first=0), None, 0,
+                                grad=True) for i, idx in enumerate(idx_list)]
+            return new_xyz, torch.cat(outs, dim=1).reshape(B, S, self.out_channels)
         new_xyz, idx_list = sampled if sampled is not None else self.sample(xyz, start=start, cuda_mode=cuda_mode)
         out = torch.empty((B * S, self.out_channels), dtype=torch.float32, device=xyz.device)
         col = 0
@@ -209,12 +242,14 @@ class PointNetSetAbstractionMsg(_InferenceLayer):
             col += self.conv_blocks[i][-1].weight.shape[0]
         return new_xyz, out.reshape(B, S, self.out_channels)
 
-    @torch.no_grad()
-    def forward(self, xyz, points, *, fps_start=None, cuda_mode=None):
+    def forward(self, xyz, points, *, fps_start=None, cuda_mode=None, grad=False):
         """xyz [B,3,N], points [B,D,N] or None -> new_xyz [B,3,S], new_points [B,sum C,S]."""
         self._check(xyz, points)
-        new_xyz, out = self.run(_last(xyz), _last(points), start=fps_start, cuda_mode=cuda_mode)
-        return new_xyz.permute(0, 2, 1), out.permute(0, 2, 1)
+
+        def fn(g):
+            new_xyz, out = self.run(_last(_coords(xyz) if g else xyz), _last(points), start=fps_start, cuda_mode=cuda_mode, grad=g)
+            return new_xyz.permute(0, 2, 1), out.permute(0, 2, 1)
+        return self._call(grad, fn)
 
 
 class PointNetSetAbstraction(_InferenceLayer):
@@ -231,25 +266,39 @@ class PointNetSetAbstraction(_InferenceLayer):
             self.mlp_bns.append(nn.BatchNorm2d(out))
             last = out
 
-    def pool_all(self, xyz, feats):
+    def pool_all(self, xyz, feats, grad=False):
         """group_all on channel-last input: xyz [B,N,3], feats [B,N,D] or None -> [B,C] (any N)."""
         from .feature_extractor import grouped_mlp
 
         B, N, _ = xyz.shape
         idx = torch.arange(N, device=xyz.device, dtype=torch.int64).expand(B, 1, N).contiguous()
+        if grad:
+            self._check(xyz, feats)
+            return grouped_mlp(self.mlp_convs, self.mlp_bns, dict(idx=idx, F=_flat(feats), Q=_coords(xyz).reshape(B * N, 3), C=None,
+                                                                  Npts=N, xyz_first=1), None, 0, grad=True)
         out = torch.empty((B, self.mlp_convs[-1].weight.shape[0]), dtype=torch.float32, device=xyz.device)
         # [xyz | features], xyz first, nothing subtracted (sample_and_group_all :186-188)
         return grouped_mlp(self.mlp_convs, self.mlp_bns, dict(idx=idx, F=_flat(feats), Q=xyz.reshape(B * N, 3), C=None, Npts=N,
                                                               xyz_first=1), out, 0)
 
-    def run(self, xyz, feats, start=None, cuda_mode=None):
+    def run(self, xyz, feats, start=None, cuda_mode=None, grad=False):
         """xyz [B,N,3], feats [B,N,D] (channel-last) or None -> new_xyz [B,S,3], new_feats [B,S,C]."""
         from .feature_extractor import grouped_mlp
 
         B, N, _ = xyz.shape
         if self.group_all:
-            return torch.zeros((B, 1, 3), dtype=torch.float32, device=xyz.device), self.pool_all(xyz, feats)[:, None, :]
+            return torch.zeros((B, 1, 3), dtype=torch.float32, device=xyz.device), self.pool_all(xyz, feats, grad=grad)[:, None, :]
         S = self.npoint
+        if grad:
+            self._check(xyz, feats)
+            xyz = _coords(xyz)
+            with torch.no_grad():
+                fps = farthest_point_sample(xyz, S, start=start, cuda_mode=cuda_mode)
+                new_xyz = index_points(xyz, fps).contiguous()
+                idx = query_ball_point(self.radius, self.nsample, xyz, new_xyz, cuda_mode=cuda_mode)
+            out = grouped_mlp(self.mlp_convs, self.mlp_bns, dict(idx=idx, F=_flat(feats), Q=xyz.reshape(B * N, 3),
+                                                                 C=new_xyz.reshape(B * S, 3), Npts=N, xyz_first=1), None, 0, grad=True)
+            return new_xyz, out.reshape(B, S, -1)
         fps = farthest_point_sample(xyz, S, start=start, cuda_mode=cuda_mode)
         new_xyz = index_points(xyz, fps).contiguous()
         idx = query_ball_point(self.radius, self.nsample, xyz, new_xyz, cuda_mode=cuda_mode)
@@ -259,12 +308,14 @@ class PointNetSetAbstraction(_InferenceLayer):
                                                        Npts=N, xyz_first=1), out, 0)
         return new_xyz, out.reshape(B, S, -1)
 
-    @torch.no_grad()
-    def forward(self, xyz, points, *, fps_start=None, cuda_mode=None):
+    def forward(self, xyz, points, *, fps_start=None, cuda_mode=None, grad=False):
         """xyz [B,3,N], points [B,D,N] or None -> new_xyz [B,3,S], new_points [B,C,S] (group_all: S = 1, new_xyz zeros)."""
         self._check(xyz, points)
-        new_xyz, out = self.run(_last(xyz), _last(points), start=fps_start, cuda_mode=cuda_mode)
-        return new_xyz.permute(0, 2, 1), out.permute(0, 2, 1)
+
+        def fn(g):
+            new_xyz, out = self.run(_last(_coords(xyz) if g else xyz), _last(points), start=fps_start, cuda_mode=cuda_mode, grad=g)
+            return new_xyz.permute(0, 2, 1), out.permute(0, 2, 1)
+        return self._call(grad, fn)
 
 
 class PointNetFeaturePropagation(_InferenceLayer):
@@ -281,13 +332,27 @@ class PointNetFeaturePropagation(_InferenceLayer):
             self.mlp_bns.append(nn.BatchNorm1d(out))
             last = out
 
-    def run(self, xyz1, xyz2, points1, points2):
+    def run(self, xyz1, xyz2, points1, points2, grad=False):
         """xyz1 [B,N,3], xyz2 [B,S,3], points1 [B,N,D1] or None, points2 [B,S,D2] -> [B,N,C]."""
-        from .feature_extractor import _fold, mlp_layer, three_interpolate
+        from .feature_extractor import _fold, _fold_grad, mlp_layer, three_interpolate
 
         B, N, _ = xyz1.shape
         S, D2 = points2.shape[1], points2.shape[2]
         D1 = 0 if points1 is None else points1.shape[2]
+        if grad:
+            self._check(xyz1, xyz2, points1, points2)
+            # the copy of points1 and the S = 1 repeat are tensor expressions; the interpolation is its own operator
+            if S == 1:
+                h = points2.expand(B, N, D2).reshape(B * N, D2)
+            else:
+                h = three_interpolate(_coords(xyz1).contiguous(), _coords(xyz2).contiguous(), points2.contiguous(), None, 0, grad=True)
+            if D1:
+                h = torch.cat([points1.reshape(B * N, D1), h], dim=1)
+            h = h.contiguous()
+            for conv, bn in zip(self.mlp_convs, self.mlp_bns):
+                Wt, b = _fold_grad(conv, bn)
+                h = mlp_layer(h, Wt, b, grad=True)
+            return h.reshape(B, N, -1)
         X = torch.empty((B * N, D1 + D2), dtype=torch.float32, device=xyz1.device)
         if D1:
             X[:, :D1] = points1.reshape(B * N, D1)
@@ -301,9 +366,8 @@ class PointNetFeaturePropagation(_InferenceLayer):
             h = mlp_layer(h, Wt, b)
         return h.reshape(B, N, -1)
 
-    @torch.no_grad()
-    def forward(self, xyz1, xyz2, points1, points2, *, fps_start=None, cuda_mode=None):
+    def forward(self, xyz1, xyz2, points1, points2, *, fps_start=None, cuda_mode=None, grad=False):
         """xyz1 [B,3,N], xyz2 [B,3,S], points1 [B,D1,N] or None, points2 [B,D2,S] -> [B,C,N].  (Nothing is sampled here:
         ``fps_start`` and ``cuda_mode`` are accepted for a uniform signature and have no effect.)"""
         self._check(xyz1, xyz2, points1, points2)
-        return self.run(_last(xyz1), _last(xyz2), _last(points1), _last(points2)).permute(0, 2, 1)
+        return self._call(grad, lambda g: self.run(_last(xyz1), _last(xyz2), _last(points1), _last(points2), grad=g).permute(0, 2, 1))
