@@ -1241,6 +1241,35 @@ int reart_part_pair_cost(const float *cano_fps, const float *frame_fps, int T, i
 int reart_group_temporal_err(const float *pcs, int T, int N, const int64_t *seg, const int64_t *labels, int Ps,
                              float *per_part, float *worst, void *stream);
 
+/* The contrastive descriptor loss (PointInfoNCE) on two descriptor sets, streaming: the N1 x N2 logits are formed tile by tile
+ * on the fp32 matrix cores and never stored (csrc/infonce.hip).
+ *   f1 [B,N1,C], f2 [B,N2,C] f32 contiguous; pos [B,N1] i64: the column of f2 that is the positive of row i, an entry outside
+ *   [0, N2) (the conventional -1) = row not used; col_mask [B,N2] u8 or NULL: 0 = the column takes part in no row's sum, and a
+ *   row whose positive is masked out is not used; tau > 0.  s_ij = <f1_i, f2_j> / tau.
+ * reart_infonce_forward -> for the used rows lse = log sum_j exp(s_ij) over the live columns, row_loss = lse - s_i,pos(i),
+ *   top = the lowest live column attaining the row maximum (unused rows: 0, 0, -1); count [1] i64 = used rows of the batch;
+ *   loss [1] = the sum of row_loss in double, a fixed order, divided by count and rounded once (count = 0: exactly 0).
+ *   All of loss, row_loss, lse [B,N1] f32, top [B,N1] i64 and count are required.  Three launches.
+ * reart_infonce_backward: from the forward's operands, its lse and count, and an upstream scalar g [1] on the device (NULL = 1):
+ *   with p'_ij = exp(s_ij - lse_i) - [j = pos(i)] on live columns of used rows, 0 elsewhere,
+ *   dF1_i = g / (count tau) sum_j p'_ij f2_j [B,N1,C], dF2_j = g / (count tau) sum_i p'_ij f1_i [B,N2,C]; either may be NULL (not
+ *   computed).  Every row of a computed output is written, unused rows and masked columns with zeros.  One or two launches each.
+ * Nothing is kept between calls but what the caller holds.  No floating-point atomics, a fixed summation order for every
+ * output entry (the same bits on every run), no host synchronisation, the given stream only.  Non-finite descriptors give
+ * meaningless values, never an out-of-range access; pos is range-checked on the device.
+ * Limits: 1 <= C <= REART_MAX_D, N1 and N2 <= REART_NCE_MAX_N, B <= REART_NCE_MAX_B; beyond them the workspace query returns 0
+ * and the calls REART_ERR_UNSUPPORTED.  tau <= 0, C < 1, a negative size, a NULL required pointer, a NULL or short workspace:
+ * REART_ERR_INVALID_ARG.  B = 0 or N1 = 0: REART_OK, loss 0, count 0.  One workspace size serves both calls. */
+#define REART_NCE_MAX_N 65536
+#define REART_NCE_MAX_B 1024
+size_t reart_infonce_scratch_bytes(int B, int N1, int N2, int C);
+int reart_infonce_forward(const float *f1, const float *f2, const int64_t *pos, const uint8_t *col_mask, int B, int N1, int N2,
+                          int C, float tau, float *loss, float *row_loss, float *lse, int64_t *top, int64_t *count,
+                          void *workspace, size_t workspace_bytes, void *stream);
+int reart_infonce_backward(const float *f1, const float *f2, const int64_t *pos, const uint8_t *col_mask, const float *lse,
+                           const int64_t *count, const float *g, int B, int N1, int N2, int C, float tau, float *dF1, float *dF2,
+                           void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

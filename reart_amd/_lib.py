@@ -31,6 +31,8 @@ STRUCT_MAX_P = 64        # parts of reart_structure_term / reart_rel_trans_backw
 STRUCT_MAX_E = 4096      # their edges: a part's incidence list is held in LDS
 CONN_MAX_N = 65536       # REART_CONN_MAX_N: points of reart_connection_select / reart_connection_term (two indices in 32 bits of a key)
 CONN_MAX_K = 64          # REART_CONN_MAX_K: pairs per edge, one wave's list
+NCE_MAX_N = 65536        # REART_NCE_MAX_N: rows / columns of reart_infonce_forward / _backward
+NCE_MAX_B = 1024         # REART_NCE_MAX_B: their batch
 MLP_GRAD_ROW_CHUNK = 256  # REART_MLP_GRAD_ROW_CHUNK: rows per partial tile of reart_mlp_layer_backward's dWt / dbias
 ADAM_MAX_TENSORS = 32   # REART_ADAM_MAX_TENSORS: records of one reart_adam_groups call, passed by value to its kernel
 
@@ -164,6 +166,9 @@ PROTOTYPES = {
     "reart_connection_select": (c_int, [P, P, c_int, c_int, P, c_int, c_int, P, P, P, P, P, c_size_t, P]),
     "reart_connection_term_workspace_bytes": (c_size_t, [c_int] * 4),
     "reart_connection_term": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_float, P, P, P, P, c_size_t, P]),
+    "reart_infonce_scratch_bytes": (c_size_t, [c_int] * 4),
+    "reart_infonce_forward": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_float, P, P, P, P, P, P, c_size_t, P]),
+    "reart_infonce_backward": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, P, P, P, c_size_t, P]),
     "reart_part_fps": (c_int, [P, P, c_int, P, c_int, c_int, c_int, P, P, P]),
     "reart_part_pair_cost": (c_int, [P, P, c_int, c_int, c_int, P, P, P, P]),
     "reart_group_temporal_err": (c_int, [P, c_int, c_int, P, P, c_int, P, P, P]),

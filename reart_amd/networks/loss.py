@@ -353,3 +353,162 @@ class ConnectionTerm(torch.nn.Module):
             _lib.require_gpu(cano, seg, pc)
             src, tgt, valid = self._select(cano, seg)
         return _ConnectionTermFn.apply(pc, src, tgt, valid, self.k, self.weight, self)
+
+
+# ------------------------------------------------------------------------------------------- descriptor InfoNCE
+def _infonce_forward_call(f1, f2, pos, mask, tau):
+    """One ``reart_infonce_forward`` call on contiguous device tensors -> (loss, row_loss [B,N1], lse [B,N1], top [B,N1], count)."""
+    (B, N1, C), N2, dev = f1.shape, f2.shape[1], f1.device
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    row_loss = torch.empty((B, N1), dtype=torch.float32, device=dev)
+    lse = torch.empty((B, N1), dtype=torch.float32, device=dev)
+    top = torch.empty((B, N1), dtype=torch.int64, device=dev)
+    count = torch.empty((), dtype=torch.int64, device=dev)
+    L = _lib.lib()
+    ws = _lib.workspace(L.reart_infonce_scratch_bytes(B, N1, N2, C), dev)
+    rc = L.reart_infonce_forward(_lib.ptr(f1), _lib.ptr(f2), _lib.ptr(pos), _lib.ptr(mask), B, N1, N2, C, float(tau), _lib.ptr(loss),
+                                 _lib.ptr(row_loss), _lib.ptr(lse), _lib.ptr(top), _lib.ptr(count), _lib.ptr(ws), ws.numel(), _lib.stream())
+    _lib.check(rc, "reart_infonce_forward")
+    return loss, row_loss, lse, top, count
+
+
+def _infonce_backward_call(f1, f2, pos, mask, lse, count, g, tau, want1, want2):
+    """One ``reart_infonce_backward`` call -> (dF1 or None, dF2 or None); ``g`` a float32 device scalar or None (= 1)."""
+    (B, N1, C), N2, dev = f1.shape, f2.shape[1], f1.device
+    d1 = torch.empty_like(f1) if want1 else None
+    d2 = torch.empty_like(f2) if want2 else None
+    if (want1 and d1.numel()) or (want2 and d2.numel()):
+        L = _lib.lib()
+        ws = _lib.workspace(L.reart_infonce_scratch_bytes(B, N1, N2, C), dev)
+        rc = L.reart_infonce_backward(_lib.ptr(f1), _lib.ptr(f2), _lib.ptr(pos), _lib.ptr(mask), _lib.ptr(lse), _lib.ptr(count), _lib.ptr(g),
+                                      B, N1, N2, C, float(tau), _lib.ptr(d1) if want1 and d1.numel() else None,
+                                      _lib.ptr(d2) if want2 and d2.numel() else None, _lib.ptr(ws), ws.numel(), _lib.stream())
+        _lib.check(rc, "reart_infonce_backward")
+    return d1, d2
+
+
+class _InfoNCEFn(torch.autograd.Function):
+    """The forward keeps the operands, lse and count; the backward is one native call that recomputes the logits, for the
+    operands that need a gradient only."""
+
+    @staticmethod
+    def forward(ctx, f1, f2, pos, mask, tau, sink):
+        ctx.set_materialize_grads(False)
+        f1c, f2c = f1.detach().contiguous(), f2.detach().contiguous()
+        loss, row_loss, lse, top, count = _infonce_forward_call(f1c, f2c, pos, mask, tau)
+        if sink is not None:
+            sink._last = (row_loss, top, count, pos)
+        ctx.tau, ctx.has_mask = tau, mask is not None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            ctx.save_for_backward(*((f1c, f2c, pos, lse, count) + ((mask,) if mask is not None else ())))
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        if g is None:
+            return None, None, None, None, None, None
+        f1c, f2c, pos, lse, count = ctx.saved_tensors[:5]
+        mask = ctx.saved_tensors[5] if ctx.has_mask else None
+        d1, d2 = _infonce_backward_call(f1c, f2c, pos, mask, lse, count, g.detach().to(torch.float32).contiguous(), ctx.tau,
+                                        ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return d1, d2, None, None, None, None
+
+
+class DescriptorInfoNCE(torch.nn.Module):
+    """``forward(f1 [B,N1,C], f2 [B,N2,C], pos [B,N1] int64, col_mask=None) -> scalar``: the contrastive descriptor loss
+    (PointInfoNCE) on two descriptor sets.  With s_ij = <f1_i, f2_j> / tau the loss is the mean over the used rows of
+
+        log sum_j exp(s_ij) - s_i,pos(i)        (``F.cross_entropy(f1 @ f2.T / tau, pos)`` with masked columns at -inf)
+
+    as one native operator (``reart_infonce_forward`` / ``reart_infonce_backward``): the logits are formed tile by tile on
+    the fp32 matrix cores and never stored, the backward recomputes them, every sum has a fixed order (the same bits on
+    every run), nothing synchronises with the host.  ``pos[b, i]`` is the column of ``f2`` that is the positive of row i; an
+    entry outside [0, N2), the conventional -1 included, means the row is not used.  ``col_mask`` [B,N2] bool / uint8: a
+    false column takes part in no row's sum, and a row whose positive is masked out is not used.  With no used row the
+    loss is exactly 0.  First-order gradients reach ``f1`` and ``f2``, whichever require them; nothing is computed for one
+    that does not.
+
+    The descriptors are used as given: for cosine logits apply ``F.normalize`` to them first, autograd carries it.
+
+    ``symmetric=True`` adds the loss of the transposed problem (``f2`` against ``f1``) and halves the sum: there the
+    positive of column j is the lowest row i with ``pos(i) = j`` among the used rows, columns no used row names (masked
+    ones among them) are unused and no column of ``f1`` is masked; two native calls, the inverse map built on the device.
+
+    ``.last`` holds ``(row_loss [B,N1], top [B,N1], count)`` of the latest call (of ``f1`` against ``f2``): ``top`` is the
+    lowest live column attaining the row's maximum, -1 on unused rows; ``accuracy()`` is the share of used rows with
+    ``top == pos``, a 0-d device tensor.
+
+    Limits: float32 descriptors, int64 ``pos``, bool / uint8 mask (``TypeError`` otherwise); 1 <= C <= 256, N1 and
+    N2 <= 65 536, B <= 1024 (``NotImplementedError``); shape mismatches and ``tau <= 0`` raise ``ValueError``; host tensors
+    raise ``RuntimeError: ... no CPU fallback``."""
+
+    def __init__(self, tau=0.07, symmetric=False):
+        super().__init__()
+        if not float(tau) > 0.0:
+            raise ValueError(f"DescriptorInfoNCE: tau = {tau} must be positive")
+        self.tau, self.symmetric = float(tau), bool(symmetric)
+        self._last = None
+
+    @property
+    def last(self):
+        return None if self._last is None else self._last[:3]
+
+    def accuracy(self):
+        if self._last is None:
+            raise RuntimeError("DescriptorInfoNCE: accuracy() follows a forward call")
+        _, top, count, pos = self._last
+        hit = ((top == pos) & (top >= 0)).sum()
+        return hit.to(torch.float32) / count.clamp(min=1).to(torch.float32)
+
+    @staticmethod
+    def _check(f1, f2, pos, col_mask):
+        if f1.dtype != torch.float32 or f2.dtype != torch.float32:
+            raise TypeError(f"DescriptorInfoNCE: float32 descriptors, not {f1.dtype} and {f2.dtype}")
+        if pos.dtype != torch.int64:
+            raise TypeError(f"DescriptorInfoNCE: int64 positives, not {pos.dtype}")
+        if col_mask is not None and col_mask.dtype not in (torch.bool, torch.uint8):
+            raise TypeError(f"DescriptorInfoNCE: a bool or uint8 column mask, not {col_mask.dtype}")
+        if f1.dim() != 3 or f2.dim() != 3 or f1.shape[0] != f2.shape[0] or f1.shape[2] != f2.shape[2] or f1.shape[2] < 1:
+            raise ValueError(f"DescriptorInfoNCE: f1 [B,N1,C] and f2 [B,N2,C], not {tuple(f1.shape)} and {tuple(f2.shape)}")
+        if tuple(pos.shape) != tuple(f1.shape[:2]):
+            raise ValueError(f"DescriptorInfoNCE: pos {tuple(f1.shape[:2])}, not {tuple(pos.shape)}")
+        if col_mask is not None and tuple(col_mask.shape) != tuple(f2.shape[:2]):
+            raise ValueError(f"DescriptorInfoNCE: col_mask {tuple(f2.shape[:2])}, not {tuple(col_mask.shape)}")
+        B, N1, C = f1.shape
+        if C > _lib.MAX_D:
+            raise NotImplementedError(f"DescriptorInfoNCE: C = {C} above REART_MAX_D = {_lib.MAX_D}")
+        if max(N1, f2.shape[1]) > _lib.NCE_MAX_N:
+            raise NotImplementedError(f"DescriptorInfoNCE: N1 = {N1}, N2 = {f2.shape[1]} above {_lib.NCE_MAX_N}")
+        if B > _lib.NCE_MAX_B:
+            raise NotImplementedError(f"DescriptorInfoNCE: B = {B} above {_lib.NCE_MAX_B}")
+        _lib.require_gpu(f1, f2, pos, col_mask)
+
+    @staticmethod
+    def _transposed_positives(pos, mask, N2):
+        """[B,N2]: the lowest used row naming each column, -1 where none does."""
+        B, N1 = pos.shape
+        if N2 == 0 or N1 == 0:
+            return torch.full((B, N2), -1, dtype=torch.int64, device=pos.device)
+        used = (pos >= 0) & (pos < N2)
+        col = torch.where(used, pos, torch.zeros_like(pos))
+        if mask is not None:
+            used = used & (mask.gather(1, col) != 0)
+            col = torch.where(used, col, torch.zeros_like(pos))
+        row = torch.arange(N1, dtype=torch.int64, device=pos.device).expand(B, N1)
+        row = torch.where(used, row, torch.full_like(row, N1))
+        inv = torch.full((B, N2), N1, dtype=torch.int64, device=pos.device)
+        inv.scatter_reduce_(1, col, row, "amin", include_self=True)           # a minimum of integers: any order, one result
+        return torch.where(inv >= N1, torch.full_like(inv, -1), inv)
+
+    def forward(self, f1, f2, pos, col_mask=None):
+        if not self.tau > 0.0:
+            raise ValueError(f"DescriptorInfoNCE: tau = {self.tau} must be positive")
+        self._check(f1, f2, pos, col_mask)
+        pos = pos.detach().contiguous()
+        mask = None if col_mask is None else col_mask.detach().to(torch.uint8).contiguous()
+        loss = _InfoNCEFn.apply(f1, f2, pos, mask, self.tau, self)
+        if self.symmetric:
+            pos_t = self._transposed_positives(pos, mask, f2.shape[1])
+            loss = 0.5 * (loss + _InfoNCEFn.apply(f2, f1, pos_t, None, self.tau, None))
+        return loss

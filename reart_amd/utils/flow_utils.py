@@ -320,3 +320,22 @@ def compute_corr_list_filter(norm_pc_list, feature_extractor, knn=None, matching
         src_list.append(src)
         tgt_list.append(tgt[e][src])
     return src_list, tgt_list
+
+
+@torch.no_grad()
+def correspondence_targets(pred, obs, max_dist):
+    """Positives for ``networks.loss.DescriptorInfoNCE`` from a fitted model: ``pred`` [B,N,3] is where the model puts the
+    canonical points in every frame (``pc_trans_list``), ``obs`` [B,M,3] the observed frames -> ``pos`` [B,N] int64, the
+    index of the observed point nearest to each predicted one (``knn_points``, K = 1: the lowest index on a tie), or -1
+    where their squared distance exceeds ``max_dist`` ** 2.  A composition of what exists; no gradient."""
+    if pred.dim() != 3 or obs.dim() != 3 or pred.shape[0] != obs.shape[0] or pred.shape[2] != 3 or obs.shape[2] != 3:
+        raise ValueError(f"correspondence_targets: pred [B,N,3] and obs [B,M,3], not {tuple(pred.shape)} and {tuple(obs.shape)}")
+    if not float(max_dist) >= 0.0:
+        raise ValueError(f"correspondence_targets: max_dist = {max_dist} is not a distance")
+    _lib.require_gpu(pred, obs)
+    from .chamfer import knn_points
+    if pred.shape[1] == 0 or obs.shape[1] == 0 or pred.shape[0] == 0:
+        return torch.full(tuple(pred.shape[:2]), -1, dtype=torch.int64, device=pred.device)
+    nn = knn_points(pred.detach(), obs.detach(), K=1)
+    far = nn.dists[..., 0] > float(max_dist) ** 2
+    return torch.where(far, torch.full_like(nn.idx[..., 0], -1), nn.idx[..., 0])
