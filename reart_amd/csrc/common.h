@@ -67,6 +67,40 @@ __device__ __forceinline__ double reart_wave_sum_d(double v) {
     return v;
 }
 
+// Sum of `term` over a workgroup of BS threads in a fixed order: the butterfly inside every wave, then thread 0 adds the waves
+// in ascending order.  Thread 0 returns the total (the other threads their wave's).  s_red: BS / REART_WAVE doubles of LDS;
+// contains one barrier and none in front: two sums in a row take two arrays.  The tree starts from 0.0, which differs from
+// starting at the first wave's partial only where every partial is -0.0 (DESIGN.md says why none is).
+template <int BS>
+__device__ __forceinline__ double reart_block_sum_d(double term, double *s_red) {
+    term = reart_wave_sum_d(term);
+    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = term;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        term = 0.0;
+        for (int w = 0; w < BS / REART_WAVE; ++w) term += s_red[w];
+    }
+    return term;
+}
+// *loss = weight * (cost_d[0] + ... + cost_d[E - 1]) by a workgroup of BS threads: strided sums in double, the block sum, one
+// rounding.  The loss of the structure and the connection term, from a kernel of its own or as the tail of the gradient's.
+template <int BS>
+__device__ __forceinline__ void reart_loss_sum_d(const double *cost_d, int E, float weight, float *loss, double *s_red) {
+    double v = 0.0;
+    for (int e = threadIdx.x; e < E; e += BS) v += cost_d[e];
+    v = reart_block_sum_d<BS>(v, s_red);
+    if (threadIdx.x == 0) *loss = (float)((double)weight * v);
+}
+
+// The wave's LDS accesses before this point are complete, and the compiler moves none across it.
+__device__ __forceinline__ void reart_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// the ballot bits of the lanes below `lane`
+__device__ __forceinline__ unsigned long long reart_lanes_below(int lane) { return (1ull << lane) - 1ull; }
+
 // Minimum / maximum over each group of 16 consecutive lanes (a DPP row), every lane receives the result.
 // Four DPP steps (quad xor 1, quad xor 2, half-row mirror, row mirror): one VALU instruction each, where
 // __shfl_xor lowers to ds_bpermute_b32 (an LDS crossbar round trip per step).

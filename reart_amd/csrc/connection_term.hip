@@ -13,14 +13,16 @@
 //                      in LDS (knn_keys.h), wave 0 merges the four lists and writes the workgroup's partial list.
 //   cs_merge_kernel    one wave per edge merges the partial lists of the slots that had sources and writes the tables.
 // reart_connection_term, three launches with a gradient, two without:
-//   ct_index_kernel    the records 2 (e k + r) + role (0 = source, 1 = target) of the valid edges, grouped by the point they
-//                      name and ascending inside a group: a workgroup per 512 points reads all records twice (count per
-//                      (wave, point), then place), every wave a contiguous run of records.
-//   ct_cost_kernel     one workgroup per edge: the T k squared pair distances added in double, a fixed tree.
+//   reart_invlist_kernel<512, 16, CtRecords> (invlist_dev.h, shared with pointnet_grad.hip)
+//                      the records 2 (e k + r) + role (0 = source, 1 = target) of the valid edges, grouped by the point they
+//                      name and ascending inside a group: a workgroup of 1024 threads per 512 points, one cloud.
+//   ct_cost_kernel     one workgroup per edge: the T k squared pair distances added in double (reart_block_sum_d, common.h).
 //   ct_grad_kernel     a thread per (frame, point) adds the point's records in ascending record number; workgroup (0, 0)
-//                      also adds the edge costs.  ct_loss_kernel does that alone when no gradient is asked for.
+//                      also adds the edge costs (reart_loss_sum_d, common.h, the structure term's as well).  ct_loss_kernel
+//                      does that alone when no gradient is asked for.
 // No floating-point atomics, no host synchronisation, no allocation; every output entry has one writer.
 #include "common.h"
+#include "invlist_dev.h"
 #include "knn_keys.h"
 
 #define CS_MAX_N REART_CONN_MAX_N    // 65 536: two indices in the low 32 bits of a key
@@ -61,7 +63,6 @@ static size_t ct_ws_layout(int N, int E, int k, void *workspace, CtWs *w) {
 
 // items per wave when CT_WAVES waves share n items in contiguous runs, whole steps of 64
 __device__ __forceinline__ int cs_run(int n) { return (n + CT_WAVES * 64 - 1) / (CT_WAVES * 64) * 64; }
-__device__ __forceinline__ u64 cs_lanes_below(int lane) { return (1ull << lane) - 1ull; }
 
 // ---------------------------------------------------------------------------------------------------------- select
 __global__ __launch_bounds__(1024) void cs_members_kernel(const int64_t *__restrict__ seg, int N, int P, int *__restrict__ members,
@@ -90,7 +91,7 @@ __global__ __launch_bounds__(1024) void cs_members_kernel(const int64_t *__restr
         const int i = i0 + lane;
         const bool mine = i < hi && seg[i] == p;
         const u64 m = __ballot(mine);
-        if (mine) members[off + __popcll(m & cs_lanes_below(lane))] = i;
+        if (mine) members[off + __popcll(m & reart_lanes_below(lane))] = i;
         off += __popcll(m);
     }
     if (tid == 0) { count[p] = total; base[p] = first; }
@@ -119,7 +120,7 @@ __global__ __launch_bounds__(CS_SRC) void cs_search_kernel(const float *__restri
     if (g * CS_SRC >= na) return;                       // cs_merge_kernel skips this slot
     const int *ma = members + base[a], *mb = members + base[b];
     s_lst[w][lane] = kl_none<u64>();
-    kl_wave_sync();
+    reart_wave_sync();
     u64 thr = kl_none<u64>();
     for (int c = g; c * CS_SRC < na; c += G) {
         const int sp = c * CS_SRC + tid;
@@ -176,7 +177,7 @@ __global__ __launch_bounds__(64) void cs_merge_kernel(const int32_t *__restrict_
     if (ok) {
         const int ng = min(G, (count[a] + CS_SRC - 1) / CS_SRC);
         s_lst[lane] = lane < k ? partial[((size_t)e * G) * k + lane] : kl_none<u64>();
-        kl_wave_sync();
+        reart_wave_sync();
         for (int g = 1; g < ng; ++g) {
             const u64 v = lane < k ? partial[((size_t)e * G + g) * k + lane] : kl_none<u64>();
             const int c = __popcll(__ballot(v != kl_none<u64>()));
@@ -206,84 +207,18 @@ __device__ __forceinline__ bool ct_live(const CtTables &c, int rec, int &s, int 
     return c.valid[rec / c.k] != 0 && (unsigned)s < (unsigned)c.N && (unsigned)g < (unsigned)c.N;
 }
 
-__global__ __launch_bounds__(CT_WAVES * 64) void ct_index_kernel(CtTables c, int *__restrict__ start, int *__restrict__ list) {
-    __shared__ int s_cnt[CT_WAVES][CT_TILE];
-    __shared__ int s_start[CT_TILE];
-    __shared__ int s_below[CT_WAVES], s_wsum[CT_WAVES];
-    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-    const int lo = blockIdx.x * CT_TILE, hi = min(c.N, lo + CT_TILE);
-    const int R = 2 * c.E * c.k;
-    const int run = cs_run(R);
-    const int q_lo = min(R, w * run), q_hi = min(R, q_lo + run);
-    for (int u = tid; u < CT_WAVES * CT_TILE; u += CT_WAVES * 64) (&s_cnt[0][0])[u] = 0;
-    __syncthreads();
-    int below = 0;
-    for (int q0 = q_lo; q0 < q_hi; q0 += 64) {
-        const int q = q0 + lane;
-        int s = 0, g = 0;
-        const bool live = q < q_hi && ct_live(c, q >> 1, s, g);
-        const int pt = (q & 1) ? g : s;
-        below += __popcll(__ballot(live && pt < lo));
-        if (live && pt >= lo && pt < hi) atomicAdd(&s_cnt[w][pt - lo], 1);     // an integer count: any order, one result
+// the records of reart_invlist_kernel: q = 2 (e k + r) + role names the pair's source (role 0) or target (role 1)
+struct CtRecords {
+    CtTables c;
+    __device__ int count() const { return 2 * c.E * c.k; }
+    __device__ int points() const { return c.N; }
+    __device__ bool point(int, int q, int &pt) const {
+        int s, g;
+        const bool live = ct_live(c, q >> 1, s, g);
+        pt = (q & 1) ? g : s;
+        return live;
     }
-    if (lane == 0) s_below[w] = below;
-    __syncthreads();
-    // a point's list: the waves' runs behind each other; the tile's lists behind each other; the tile behind the points below
-    int tot = 0;
-    if (tid < CT_TILE)
-        for (int v = 0; v < CT_WAVES; ++v) {
-            const int n = s_cnt[v][tid];
-            s_cnt[v][tid] = tot;
-            tot += n;
-        }
-    int inc = tot;
-    for (int o = 1; o < 64; o <<= 1) {
-        const int u = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += u;
-    }
-    if (lane == 63) s_wsum[w] = inc;
-    __syncthreads();
-    int first = 0, all = 0;
-    for (int v = 0; v < CT_WAVES; ++v) {
-        first += s_below[v];
-        all += s_wsum[v];
-        if (v < w) first += s_wsum[v];
-    }
-    if (tid < CT_TILE) {
-        s_start[tid] = first + inc - tot;
-        if (lo + tid < hi) start[lo + tid] = first + inc - tot;
-    }
-    if (tid == 0 && hi == c.N) start[c.N] = first + all;           // wave 0: first = the records below the tile
-    __syncthreads();
-    for (int q0 = q_lo; q0 < q_hi; q0 += 64) {
-        const int q = q0 + lane;
-        int s = 0, g = 0;
-        const bool live = q < q_hi && ct_live(c, q >> 1, s, g);
-        const int pt = (q & 1) ? g : s;
-        bool todo = live && pt >= lo && pt < hi;
-        u64 m;
-        while ((m = __ballot(todo)) != 0) {             // one point per turn: its records of this step, in lane order
-            const int lp = __shfl(pt, __ffsll((long long)m) - 1, 64) - lo;
-            const bool mine = todo && pt - lo == lp;
-            const u64 same = __ballot(mine);
-            const int at = s_cnt[w][lp];
-            if (mine) list[s_start[lp] + at + __popcll(same & cs_lanes_below(lane))] = q;
-            kl_wave_sync();
-            if (lane == 0) s_cnt[w][lp] = at + __popcll(same);
-            kl_wave_sync();
-            todo = todo && !mine;
-        }
-    }
-}
-
-// sum over the workgroup (256 threads) in a fixed tree; thread 0 gets the total
-__device__ __forceinline__ double ct_block_sum(double v, double *s_w) {
-    const int tid = threadIdx.x;
-    v = reart_wave_sum_d(v);
-    if ((tid & 63) == 0) s_w[tid >> 6] = v;
-    __syncthreads();
-    return ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
-}
+};
 
 __global__ __launch_bounds__(256) void ct_cost_kernel(const float *__restrict__ pc, CtTables c, int T, double *__restrict__ cost_d,
                                                       float *__restrict__ edge_cost) {
@@ -297,24 +232,16 @@ __global__ __launch_bounds__(256) void ct_cost_kernel(const float *__restrict__ 
         const float *ps = pc + ((size_t)t * c.N + s) * 3, *pg = pc + ((size_t)t * c.N + g) * 3;
         acc += (double)reart_sqdist3(ps[0], ps[1], ps[2], pg[0], pg[1], pg[2]);
     }
-    const double tot = ct_block_sum(acc, s_w) / (double)c.k;
+    const double tot = reart_block_sum_d<256>(acc, s_w) / (double)c.k;
     if (tid == 0) {
         cost_d[e] = tot;
         if (edge_cost) edge_cost[e] = (float)tot;
     }
 }
 
-// loss = weight * sum_e cost_d[e]: 256 threads, strided, then the fixed tree; one rounding
-__device__ __forceinline__ void ct_loss_sum(const double *cost_d, int E, float weight, float *loss, double *s_w) {
-    double v = 0.0;
-    for (int e = threadIdx.x; e < E; e += 256) v += cost_d[e];
-    const double tot = ct_block_sum(v, s_w);
-    if (threadIdx.x == 0) *loss = (float)((double)weight * tot);
-}
-
 __global__ __launch_bounds__(256) void ct_loss_kernel(const double *cost_d, int E, float weight, float *loss) {
     __shared__ double s_w[4];
-    ct_loss_sum(cost_d, E, weight, loss, s_w);
+    reart_loss_sum_d<256>(cost_d, E, weight, loss, s_w);
 }
 
 // grad[t,n] = sum over the records naming n, ascending record number, of +-(2 weight / k)(p[t,src] - p[t,tgt])
@@ -337,7 +264,7 @@ __global__ __launch_bounds__(256) void ct_grad_kernel(const float *__restrict__ 
         float *o = grad + ((size_t)t * c.N + n) * 3;
         o[0] = gx; o[1] = gy; o[2] = gz;
     }
-    if (blockIdx.x == 0 && blockIdx.y == 0) ct_loss_sum(cost_d, c.E, weight, loss, s_w);
+    if (blockIdx.x == 0 && blockIdx.y == 0) reart_loss_sum_d<256>(cost_d, c.E, weight, loss, s_w);
 }
 
 // ------------------------------------------------------------------------------------------------------------ host
@@ -382,7 +309,8 @@ extern "C" int reart_connection_term(const float *pc_trans, const int32_t *src_i
     const CtTables c{src_idx, tgt_idx, valid, N, E, k};
     if (E > 0) hipLaunchKernelGGL(ct_cost_kernel, dim3(E), dim3(256), 0, st, pc_trans, c, T, w.cost_d, edge_cost);
     if (grad) {     // E == 0: every list is empty, the gradient is written as zeros
-        hipLaunchKernelGGL(ct_index_kernel, dim3(reart_div_up(N, CT_TILE)), dim3(CT_WAVES * 64), 0, st, c, w.start, w.list);
+        hipLaunchKernelGGL((reart_invlist_kernel<CT_TILE, CT_WAVES, CtRecords>), dim3(reart_div_up(N, CT_TILE)), dim3(CT_WAVES * 64), 0, st,
+                           CtRecords{c}, w.start, w.list);
         hipLaunchKernelGGL(ct_grad_kernel, dim3(reart_div_up(N, 256), T), dim3(256), 0, st, pc_trans, c, 2.0f * weight / (float)k,
                            w.start, w.list, grad, w.cost_d, weight, loss);
     } else {

@@ -28,21 +28,6 @@ __device__ __forceinline__ int reart_fx_bits(int Pmax, float m) {
     return b > 39 ? 39 : (b < 0 ? 0 : b);
 }
 
-// Sum of `term` over a workgroup of BS threads in a fixed order: the butterfly inside every wave, then thread 0 adds the waves
-// in ascending order.  Thread 0 returns the total (the other threads their wave's).  s_red: BS / REART_WAVE doubles of LDS;
-// contains one barrier.
-template <int BS>
-__device__ __forceinline__ double reart_block_sum_d(double term, double *s_red) {
-    term = reart_wave_sum_d(term);
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = term;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        term = 0.0;
-        for (int w = 0; w < BS / REART_WAVE; ++w) term += s_red[w];
-    }
-    return term;
-}
-
 // Sum of `total` partials left by other workgroups of the launch, by ONE wave in a fixed order: lane l adds the partials
 // l, l + 64, ... in double, then the butterfly.  Agent-scope loads: the partials meet in L2 whichever XCD wrote them.
 __device__ __forceinline__ double reart_partials_sum_d(const double *part, int total) {

@@ -12,8 +12,8 @@
 //   MODE 0  forward, rows stationary: per lane a running maximum, the sum of exp(s - maximum) rescaled when the maximum rises,
 //           the lowest column attaining the maximum, and the positive's logit when it comes by.  The two lanes of a row meet
 //           once, at the end.  The columns may be split over up to 16 workgroups (small B); nce_rows_kernel merges the
-//           splits in ascending order, writes lse, row_loss and top, and a block's sum of row_loss in double;
-//           nce_loss_kernel adds the blocks' sums in a fixed order: three launches.
+//           splits in ascending order, writes lse, row_loss and top, and a block's sum of row_loss in double
+//           (reart_block_sum_d, common.h); nce_loss_kernel adds the blocks' sums in a fixed order: three launches.
 //   MODE 1  dF1, rows stationary; MODE 2 dF2, columns stationary.  p'_ij = exp(s_ij - lse_i) - [j = pos(i)] is formed in the
 //           accumulator registers, which ARE the A operand of the second product (row x, k = the streamed descriptor of this
 //           lane's half), against the streamed tile that is already in LDS as B operand: out[x][c] += sum_y p'[x][y] F[y][c],
@@ -287,20 +287,10 @@ __global__ __launch_bounds__(256) void nce_tile_kernel(NceArgs a) {
     }
 }
 
-// sum over the workgroup (256 threads) in a fixed tree; thread 0 gets the total
-__device__ __forceinline__ double nce_block_sum(double v, double *s_w) {
-    const int tid = threadIdx.x;
-    v = reart_wave_sum_d(v);
-    __syncthreads();
-    if ((tid & 63) == 0) s_w[tid >> 6] = v;
-    __syncthreads();
-    return ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
-}
-
 // a thread per row: the splits merged in ascending order, lse = maximum + log(sum) (in double, rounded once), row_loss, top
 __global__ __launch_bounds__(256) void nce_rows_kernel(NceArgs a, int S, size_t R, float *__restrict__ row_loss, float *__restrict__ lse,
                                                        int64_t *__restrict__ top, double *__restrict__ bsum, long long *__restrict__ bcnt) {
-    __shared__ double s_w[4];
+    __shared__ double s_w[4], s_c[4];          // an array per sum: reart_block_sum_d has no barrier in front
     const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
     float rl = 0.f;
     int used = 0;
@@ -323,19 +313,19 @@ __global__ __launch_bounds__(256) void nce_rows_kernel(NceArgs a, int S, size_t 
         lse[e] = l;
         top[e] = tp;
     }
-    const double tot = nce_block_sum((double)rl, s_w);
-    const double cnt = nce_block_sum((double)used, s_w);
+    const double tot = reart_block_sum_d<256>((double)rl, s_w);
+    const double cnt = reart_block_sum_d<256>((double)used, s_c);
     if (threadIdx.x == 0) { bsum[blockIdx.x] = tot; bcnt[blockIdx.x] = (long long)cnt; }
 }
 
 // loss = (sum of the blocks' sums, 256 strided threads then the fixed tree) / count, rounded once; 0 where no row is used
 __global__ __launch_bounds__(256) void nce_loss_kernel(const double *__restrict__ bsum, const long long *__restrict__ bcnt, size_t nblk,
                                                        float *__restrict__ loss, long long *__restrict__ count) {
-    __shared__ double s_w[4];
+    __shared__ double s_w[4], s_c[4];
     double v = 0.0, c = 0.0;
     for (size_t q = threadIdx.x; q < nblk; q += 256) { v += bsum[q]; c += (double)bcnt[q]; }
-    const double tot = nce_block_sum(v, s_w);
-    const double cnt = nce_block_sum(c, s_w);                  // at most 2^26 rows: exact
+    const double tot = reart_block_sum_d<256>(v, s_w);
+    const double cnt = reart_block_sum_d<256>(c, s_c);                // at most 2^26 rows: exact
     if (threadIdx.x == 0) {
         *count = (long long)cnt;
         *loss = cnt > 0.0 ? (float)(tot / cnt) : 0.f;

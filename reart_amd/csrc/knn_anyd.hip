@@ -141,7 +141,7 @@ __global__ __launch_bounds__(64) void knn_anyd_kernel(const T *__restrict__ qimg
     const int nv = n1 - i0 < 0 ? 0 : (n1 - i0 < Q ? n1 - i0 : Q);     // queries of the group with a list
     Key *cand = s_keys + (size_t)Q * K;
     for (int e = lane; e < Q * K; e += 64) s_keys[e] = kl_none<Key>();
-    kl_wave_sync();
+    reart_wave_sync();
 
     Key thr[Q];                       // each list's K-th key (all-ones while it is not full)
 #pragma unroll

@@ -44,13 +44,6 @@ __device__ __forceinline__ u64 kl_none<u64>() { return ~0ull; }
 template <>
 __device__ __forceinline__ KeyF64 kl_none<KeyF64>() { return KeyF64{~0ull, ~0u, 0u}; }
 
-// the wave's LDS accesses before this point are complete, and the compiler moves none across it
-__device__ __forceinline__ void kl_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 __device__ __forceinline__ u64 kl_shfl_xor(u64 v, int m) {
     const int lo = __shfl_xor((int)(unsigned)v, m, 64), hi = __shfl_xor((int)(unsigned)(v >> 32), m, 64);
     return ((u64)(unsigned)hi << 32) | (unsigned)lo;
@@ -95,17 +88,17 @@ __device__ __forceinline__ Key kl_merge(Key *lst, Key *cand, int K, Key v, int c
     Key old[NE];
 #pragma unroll
     for (int u = 0; u < NE; ++u) old[u] = (lane + 64 * u < K) ? lst[lane + 64 * u] : kl_none<Key>();
-    kl_wave_sync();
+    reart_wave_sync();
     // new slots: a candidate moves up by the list entries below it, an entry by the candidates below it
     const int cpos = lane < c ? lane + kl_count_below(lst, K, v) : K;
     int npos[NE];
 #pragma unroll
     for (int u = 0; u < NE; ++u) npos[u] = lane + 64 * u + kl_count_below(cand, c, old[u]);
-    kl_wave_sync();
+    reart_wave_sync();
 #pragma unroll
     for (int u = 0; u < NE; ++u)
         if (lane + 64 * u < K && npos[u] < K) lst[npos[u]] = old[u];
     if (cpos < K) lst[cpos] = v;
-    kl_wave_sync();
+    reart_wave_sync();
     return lst[K - 1];
 }

@@ -52,7 +52,7 @@ __global__ __launch_bounds__(KL_BS) void knn_list_kernel(KnnListArgs a) {
 #pragma unroll
     for (int u = 0; u < NE; ++u)
         if (lane + 64 * u < K) lst[lane + 64 * u] = ~0ull;
-    kl_wave_sync();
+    reart_wave_sync();
 
     const float *qp = a.q + (size_t)w * 3;
     const float qx = qp[0], qy = qp[1], qz = qp[2];

@@ -17,105 +17,40 @@
 //   dX = dZ Wt^T      is reart_mlp_layer on dZ with the transposed weight (pg_transpose_kernel), no bias, no ReLU.  For a gathered
 //                     input only the FEATURE columns are computed (the weight rows of the xyz columns are left out of the
 //                     transposed image), into the workspace; then
-//   pgi_index_kernel  builds, per cloud, the list of rows that name each point (a stable counting sort: the rows of a point in
-//                     ascending order; indices outside [0, Npts) are left out), and
+//   reart_invlist_kernel<256, 4, PgRecords> (invlist_dev.h, shared with connection_term.hip) builds, per cloud, the list of
+//                     rows that name each point (the rows of a point in ascending order; indices outside [0, Npts) are left
+//                     out), and
 //   pg_scatter_kernel sums a point's rows in that order into dF.  A point no row names gets exactly 0.
 // The interpolation backward uses the same lists over the (fine point, neighbour) pairs.
 #include "common.h"
 #include "internal.h"
+#include "invlist_dev.h"
 #include <math.h>
 
 typedef float pg_f16v __attribute__((ext_vector_type(16)));
-typedef unsigned long long pg_u64;
 
 // ---------------------------------------------------------------------------------------------------------------------
-// inverse lists: which records name point p of cloud b?   rec [B][Rb] (i64 point indices), start [B][Npts + 1], list [B * Rb]
-// (absolute record numbers b * Rb + q, the records of a point in ascending order, the points of a cloud behind each other from
-// b * Rb on; records with an index outside [0, Npts) take no place).  One workgroup per 256 points of a cloud; its four waves
-// walk the cloud's records in four contiguous runs (the counting sort of connection_term.hip's ct_index_kernel).
+// inverse lists (invlist_dev.h): rec [B][Rb] (i64 point indices; one outside [0, Npts) takes no place), start [B][Npts + 1],
+// list [B * Rb].  One workgroup per 256 points of a cloud; its four waves walk the cloud's records in four contiguous runs.
 // ---------------------------------------------------------------------------------------------------------------------
 #define PGI_TILE 256
 #define PGI_WAVES 4
 
-__device__ __forceinline__ void pg_wave_sync() {       // the wave's LDS accesses before this point are complete
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ pg_u64 pg_lanes_below(int lane) { return (1ull << lane) - 1ull; }
-
-__global__ __launch_bounds__(PGI_WAVES * 64) void pgi_index_kernel(const int64_t *__restrict__ rec_all, int Rb, int Npts,
-                                                                   int *__restrict__ start, int *__restrict__ list) {
-    __shared__ int s_cnt[PGI_WAVES][PGI_TILE];
-    __shared__ int s_start[PGI_TILE];
-    __shared__ int s_below[PGI_WAVES], s_wsum[PGI_WAVES];
-    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-    const int b = blockIdx.y;
-    const int lo = blockIdx.x * PGI_TILE, hi = min(Npts, lo + PGI_TILE);
-    const int64_t *__restrict__ rec = rec_all + (size_t)b * Rb;
-    const int base = b * Rb;
-    const int run = (Rb + PGI_WAVES * 64 - 1) / (PGI_WAVES * 64) * 64;
-    const int q_lo = min(Rb, w * run), q_hi = min(Rb, q_lo + run);
-    for (int u = tid; u < PGI_WAVES * PGI_TILE; u += PGI_WAVES * 64) (&s_cnt[0][0])[u] = 0;
-    __syncthreads();
-    int below = 0;
-    for (int q0 = q_lo; q0 < q_hi; q0 += 64) {
-        const int q = q0 + lane;
-        const int64_t p = q < q_hi ? rec[q] : -1;
-        const bool live = p >= 0 && p < Npts;
-        const int pt = live ? (int)p : 0;
-        below += __popcll(__ballot(live && pt < lo));
-        if (live && pt >= lo && pt < hi) atomicAdd(&s_cnt[w][pt - lo], 1);      // an integer count: any order, one result
+struct PgRecords {
+    const int64_t *rec;
+    int Rb, Npts;
+    __device__ int count() const { return Rb; }
+    __device__ int points() const { return Npts; }
+    __device__ bool point(int b, int q, int &pt) const {
+        const int64_t p = rec[(size_t)b * Rb + q];
+        pt = (int)p;
+        return p >= 0 && p < Npts;
     }
-    if (lane == 0) s_below[w] = below;
-    __syncthreads();
-    // a point's list: the waves' runs behind each other; the tile's lists behind each other; the tile behind the points below
-    int tot = 0;
-    for (int v = 0; v < PGI_WAVES; ++v) {
-        const int n = s_cnt[v][tid];
-        s_cnt[v][tid] = tot;
-        tot += n;
-    }
-    int inc = tot;
-    for (int o = 1; o < 64; o <<= 1) {
-        const int u = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += u;
-    }
-    if (lane == 63) s_wsum[w] = inc;
-    __syncthreads();
-    int first = 0, all = 0;
-    for (int v = 0; v < PGI_WAVES; ++v) {
-        first += s_below[v];
-        all += s_wsum[v];
-        if (v < w) first += s_wsum[v];
-    }
-    s_start[tid] = first + inc - tot;
-    if (lo + tid < hi) start[(size_t)b * (Npts + 1) + lo + tid] = base + first + inc - tot;
-    if (tid == 0 && hi == Npts) start[(size_t)b * (Npts + 1) + Npts] = base + first + all;   // wave 0: first = the records below the tile
-    __syncthreads();
-    for (int q0 = q_lo; q0 < q_hi; q0 += 64) {
-        const int q = q0 + lane;
-        const int64_t p = q < q_hi ? rec[q] : -1;
-        const bool live = p >= 0 && p < Npts;
-        const int pt = live ? (int)p : 0;
-        bool todo = live && pt >= lo && pt < hi;
-        pg_u64 m;
-        while ((m = __ballot(todo)) != 0) {               // one point per turn: its records of this step, in lane order
-            const int lp = __shfl(pt, __ffsll((long long)m) - 1, 64) - lo;
-            const bool mine = todo && pt - lo == lp;
-            const pg_u64 same = __ballot(mine);
-            const int at = s_cnt[w][lp];
-            if (mine) list[base + s_start[lp] + at + __popcll(same & pg_lanes_below(lane))] = base + q;
-            pg_wave_sync();
-            if (lane == 0) s_cnt[w][lp] = at + __popcll(same);
-            pg_wave_sync();
-            todo = todo && !mine;
-        }
-    }
-}
+};
 
 static void pgi_launch(const int64_t *rec, int B, int Rb, int Npts, int *start, int *list, hipStream_t st) {
-    hipLaunchKernelGGL(pgi_index_kernel, dim3(reart_div_up(Npts, PGI_TILE), B), dim3(PGI_WAVES * 64), 0, st, rec, Rb, Npts, start, list);
+    hipLaunchKernelGGL((reart_invlist_kernel<PGI_TILE, PGI_WAVES, PgRecords>), dim3(reart_div_up(Npts, PGI_TILE), B), dim3(PGI_WAVES * 64), 0, st,
+                       PgRecords{rec, Rb, Npts}, start, list);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -6,13 +6,13 @@
 // handful of sums over the frames, and a gradient that every part collects from its incident edges:
 //   st_edge_kernel     one workgroup per edge, its lanes striding the frames (one wave up to T = 64, four beyond).  Pass 1
 //                      decomposes every frame and reduces the masked sums of axis / moment, |theta| and |d| inside the
-//                      workgroup (wave shuffles, then LDS); pass 2 builds the constant target of every frame, its cost and
+//                      workgroup (reart_wave_sum_d, then LDS); pass 2 builds the constant target of every frame, its cost and
 //                      dL/dM, and -- with `pairs` -- carries dL/dM to the two ends of the edge, written per (frame, edge,
 //                      end) into the workspace.
 //   st_gather_kernel   one workgroup per (part, run of 16 frames): the part's incidence list (edge, end) is compacted from
 //                      `pairs` into LDS in ascending edge order, then a thread owns one entry of one 4x4 and adds the
-//                      list's contributions in that order.  Workgroup (0, 0) also adds the edge costs, in double and in a
-//                      fixed tree, and rounds the loss once.
+//                      list's contributions in that order.  Workgroup (0, 0) also adds the edge costs (reart_loss_sum_d,
+//                      common.h, the connection term's as well: in double, a fixed order, one rounding).
 // No atomics, no host synchronisation, no allocation, no memset: every output entry has one writer.  Two launches with
 // `pairs`, two without (edge kernel + the loss sum).
 #include "common.h"
@@ -115,8 +115,7 @@ template <int BS, int N>
 __device__ __forceinline__ void st_block_sum(double *v, double (*s_part)[ST_NRED], double *s_out) {
     const int tid = threadIdx.x;
 #pragma unroll
-    for (int i = 0; i < N; ++i)
-        for (int o = 32; o >= 1; o >>= 1) v[i] += __shfl_xor(v[i], o, 64);
+    for (int i = 0; i < N; ++i) v[i] = reart_wave_sum_d(v[i]);
     __syncthreads();                      // s_part / s_out of an earlier sum have been read
     if ((tid & 63) == 0)
 #pragma unroll
@@ -221,20 +220,9 @@ __global__ __launch_bounds__(BS) void st_edge_kernel(StArgs a) {
     }
 }
 
-// loss = weight * sum_e cost_d[e]: 256 threads, strided, then a fixed tree; one rounding
-__device__ __forceinline__ void st_loss_sum(const double *cost_d, int E, float weight, float *loss, double *s_w) {
-    const int tid = threadIdx.x;
-    double v = 0.0;
-    for (int e = tid; e < E; e += 256) v += cost_d[e];
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    if ((tid & 63) == 0) s_w[tid >> 6] = v;
-    __syncthreads();
-    if (tid == 0) *loss = (float)((double)weight * (((s_w[0] + s_w[1]) + s_w[2]) + s_w[3]));
-}
-
 __global__ __launch_bounds__(256) void st_loss_kernel(const double *cost_d, int E, float weight, float *loss) {
     __shared__ double s_w[4];
-    st_loss_sum(cost_d, E, weight, loss, s_w);
+    reart_loss_sum_d<256>(cost_d, E, weight, loss, s_w);
 }
 
 // grad[t,p] = sum over the edges that end in p, ascending edge number, src end before tgt end; row 3 = 0.
@@ -270,7 +258,7 @@ __global__ __launch_bounds__(256) void st_gather_kernel(const float *__restrict_
         }
         grad[((size_t)t * P + p) * 16 + ent] = sum;
     }
-    if (loss && blockIdx.x == 0 && blockIdx.y == 0) st_loss_sum(cost_d, E, weight, loss, s_w);
+    if (loss && blockIdx.x == 0 && blockIdx.y == 0) reart_loss_sum_d<256>(cost_d, E, weight, loss, s_w);
 }
 
 // grad_rel [T,E,4,4] -> the two ends' rows per (frame, edge); rows 0..2 of the upstream only
