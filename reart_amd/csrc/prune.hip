@@ -53,6 +53,20 @@
 //     order array as a vector load + v_readfirstlane, for the flow job qmap[b] the same way behind it, the count as a
 //     flat_load, and the K = 3 seed targets in three dependent groups (2 + 4 + 3 loads) -- six round trips for a flow item.
 //     Launches without item words (SearchArgs::item == NULL, the stand-alone warm operators) keep border[pos] -> qmap[b].
+//   * The filter loop of a search wave (knn_pruned_wave; read off the emitted gfx950 code as well, counts in
+//     profiles/filter_stream_isa_counts.txt).  The launch is bound by what a SIMD can issue, and most of what it issues is the
+//     filter: coarse rounds, precise steps, queue appends.  In the group form (BOXL) a precise step of two boxes is 20 VALU
+//     instructions, 18 of arithmetic and one v_mov_b32 per box for the LDS address: the coarse round parks a box's bounds as
+//     (lo0, lo1) | (hi0, hi1) | (lo2, -hi2), the three register pairs the step works on.  The wave index is a scalar
+//     (readfirstlane at the kernel's entry), so box addresses, the box number of an enqueue and the statistics counter are
+//     SALU work.  The loop that judges boxes only enqueues; a dense scan or a drain is done outside it, so the candidates
+//     are loop-invariant where most boxes pass, and it has ONE exit on one scalar (the survivor mask): a box no lane needs
+//     costs 1 VALU, an enqueued one 5.  Before: 31 per step (nine register shuffles, two 64-bit multiply-adds for the
+//     addresses), a v_add per counter event, and 14 copies of the candidates per enqueued box of a K = 3 item.  Per launch
+//     of the headline shape 12.7 M -> 9.5 M VALU instructions, 32.5 -> 29.1 us.  The cloud-resident form (BOXL = false: bounds in the lanes of the coarse
+//     round, read with v_readlane) keeps the per-box pairing it had -- it sits at 80 VGPRs and the axis form cost it a
+//     resident wave -- and takes the same loop structure and the one-block coarse round.  Every form evaluates the same
+//     operations in the same order: the filter's decisions, and with them the executed pairs, are bit for bit the same.
 //   * Neighbour seeds (round 3).  A lane's own seed is a poor bound exactly when it matters: every iteration a fifth of
 //     the points re-sample their part label and jump (queries of the x -> y search, targets of the y -> x search), their
 //     old neighbour is then far away, and those lanes -- 23 % of them -- used to produce 78 % of all (query, box)
@@ -94,8 +108,9 @@ __device__ __forceinline__ int pr_uniform_word(const void *p) { return *(const _
 // instructions, loads for the 60 % of the boxes the precise test rejects, no gain; DESIGN_HISTORY.md)
 #define PR_QCAP 640     // words of a wave's queue space: the first 384 hold box bounds, 256 (query, box) entries (768: one
                         // workgroup less per compute unit, 32.9 vs 32.3 us; 512: drains too small and too many, 33.7 us)
-#define PR_WPE 6         // waves per SIMD the compiler must allow for (register budget: 85 -> 80 VGPRs; the kernel sits at the
-                         // edge -- 78 under this bound, 82 without it, no spills either way -- and the sixth wave is worth 7 %)
+#define PR_WPE 6         // waves per SIMD the compiler must allow for (register budget: 85 -> 80 VGPRs; the kernel sat at the
+                         // edge -- 78 under this bound, 82 without it, no spills either way -- and the sixth wave is worth 7 %;
+                         // with the wave index in a scalar register it needs 70 and the bound is also its maximum, see below)
 // LDS per wave: staged box of a dense scan [64 floats] | the wave's queries [64][4] | result slots [3][64] u64 | queue
 // The precise filter reads a surviving box's bounds back from LDS (broadcast ds_read, the LDS pipe is idle) instead of twelve
 // v_readlane per box pair on the VALU, which bounds this kernel: 45.0 -> 43.6 us per launch.  The 1.5 KB come out of the
@@ -110,8 +125,19 @@ extern "C" int reart_debug_prune_stats(unsigned long long *out, int reset) {
     return REART_OK;
 }
 #define PRUNE_STAT(k, v) do { if ((threadIdx.x & 63) == 0) atomicAdd(&g_prune_stats[k], (unsigned long long)(v)); } while (0)
+// events of the filter loop per kind of item (row 0: K = 1, row 1: K = 3), summed over waves (tools/filter_events.py): 0 coarse
+// rounds, 1 boxes passing the coarse filter, 2 precise steps (two boxes each, the last of a round may hold one), 3 boxes some
+// lane needs, 4 of them enqueued, 5 densely scanned, 6 drain steps, 7 waves
+__device__ unsigned long long g_prune_events[2][8];
+extern "C" int reart_debug_prune_events(unsigned long long *out, int reset) {
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_prune_events), sizeof(g_prune_events)) != hipSuccess) return REART_ERR_LAUNCH;
+    if (reset) { unsigned long long z[16] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_prune_events), z, sizeof(z)); }
+    return REART_OK;
+}
+#define PRUNE_EVENT(k, v) do { if ((threadIdx.x & 63) == 0) atomicAdd(&g_prune_events[KK == 1 ? 0 : 1][k], (unsigned long long)(v)); } while (0)
 #else
 #define PRUNE_STAT(k, v) do { } while (0)
+#define PRUNE_EVENT(k, v) do { } while (0)
 #endif
 #ifdef REART_PRUNE_PHASE   // diagnostic build only (tools/phase_prof.py; make -C reart_amd/csrc phase)
 // phase clocks of the search waves (s_memtime ticks summed over waves): 0 prologue (seeds, group summaries), 1 coarse
@@ -222,6 +248,7 @@ __device__ __forceinline__ void knn_pruned_wave(const float *qcloud, const int *
     const float qx = qp[0], qy = qp[1], qz = qp[2];
     PH_STAMP(0, "v"(qx), "v"(qy), "v"(qz));
     const f2 qx2 = {qx, qx}, qy2 = {qy, qy}, qz2 = {qz, qz};
+    const f2 qxy = {qx, qy}, qzn = {-qz, qz};             // the precise filter's operands (paired by axis)
 
     const float *tx = cloud;
     const float *ty = tx + cstride;
@@ -349,6 +376,7 @@ __device__ __forceinline__ void knn_pruned_wave(const float *qcloud, const int *
     auto drain_queue = [&]() {
         for (int e0 = 0; e0 < qcnt; e0 += 64) {
             wp += PR_WORK(6);
+            PRUNE_EVENT(6, 1);
             const int e = e0 + lane;
             const bool valid = e < qcnt;
             const unsigned ent = s_q[valid ? e : e0];
@@ -435,11 +463,16 @@ __device__ __forceinline__ void knn_pruned_wave(const float *qcloud, const int *
             const float4 A = *(const float4 *)(bx + (size_t)bid * 8);
             const float4 Bv = *(const float4 *)(bx + (size_t)bid * 8 + 4);
             lo0 = A.x; lo1 = A.y; lo2 = A.z; hi0 = A.w; hi1 = Bv.x; hi2 = Bv.y;
-            if (BOXL) {        // the precise filter reads a surviving box's bounds back as LDS broadcasts (not VALU readlanes)
+            if (BOXL) {        // the precise filter reads a surviving box's bounds back as LDS broadcasts (not VALU readlanes),
+                // in the pairs it works on: (lo0, lo1) | (hi0, hi1) | (lo2, -hi2).  hi2 is parked NEGATED: the filter forms
+                // {lo2 - qz, qz - hi2} as {lo2, -hi2} + {-qz, qz}, one packed add without a modifier to build
                 float *o = s_bb + 6 * lane;
-                o[0] = lo0; o[1] = lo1; o[2] = lo2; o[3] = hi0; o[4] = hi1; o[5] = hi2;
+                o[0] = lo0; o[1] = lo1; o[2] = hi0; o[3] = hi1; o[4] = lo2; o[5] = -hi2;
             }
-            // two query sub-groups per packed instruction (same operation order per sub-group as box_lb)
+            // two query sub-groups per packed instruction (same operation order per sub-group as box_lb).  Both halves in ONE
+            // basic block ('|', not '||'): the lane's bound is then broadcast by the op_sel of the packed add in both -- behind
+            // a branch the second half assembled its operands with eight v_mov_b32 (the branch was taken only when all 64
+            // boxes of a round passed in the first half)
             const f2 bl0 = {lo0, lo0}, bl1 = {lo1, lo1}, bl2 = {lo2, lo2}, bh0 = {hi0, hi0}, bh1 = {hi1, hi1}, bh2 = {hi2, hi2};
 #pragma unroll
             for (int q = 0; q < 4; q += 2) {
@@ -450,18 +483,21 @@ __device__ __forceinline__ void knn_pruned_wave(const float *qcloud, const int *
                 const f2 e1 = {fmaxf(fmaxf(a1.x, c1.x), 0.f), fmaxf(fmaxf(a1.y, c1.y), 0.f)};
                 const f2 e2 = {fmaxf(fmaxf(a2.x, c2.x), 0.f), fmaxf(fmaxf(a2.y, c2.y), 0.f)};
                 const f2 lb = (e0 * e0 + e1 * e1) + e2 * e2;
-                pass = pass || (lb.x <= G[q][6]) || (lb.y <= G[q + 1][6]);
+                pass = pass | (lb.x <= G[q][6]) | (lb.y <= G[q + 1][6]);
             }
         }
         unsigned long long mask = __ballot(pass);
         PH(1);
         PRUNE_STAT(KK == 1 ? 0 : 3, 0);                                  // coarse rounds (K = 1)
+        PRUNE_EVENT(0, 1);
+        PRUNE_EVENT(1, __builtin_popcountll(mask));
         if (KK == 1) PRUNE_STAT(1, __builtin_popcountll(mask));          // boxes passing the coarse filter
         if (KK == 1) PRUNE_STAT(3, __builtin_popcountll(__ballot(thr == INFINITY)));  // lanes without a bound
         // scan of one box: the brute-force inner loop of knn.hip on its 16 targets
         auto scan_box = [&](const int bit) {
             wp += PR_WORK(5) | (64u * NN_BOX);                           // a scan costs about five tests
             if (KK == 1) PRUNE_STAT(2, 1);                               // boxes scanned
+            PRUNE_EVENT(5, 1);
             const int j0 = (base + bit * a.S + s) * NN_BOX;
             // the box's 16 targets are staged in the wave's LDS slot (x[16] | y[16] | z[16]); all lanes read
             // the same addresses (broadcast) -- the operands of the packed ops are VGPR pairs
@@ -523,67 +559,112 @@ __device__ __forceinline__ void knn_pruned_wave(const float *qcloud, const int *
         auto enqueue_box = [&](const int bit, const unsigned long long need, const bool nd, const int nneed) {
             wp += PR_WORK(1);
             if (KK == 1) PRUNE_STAT(2, 1);
+            PRUNE_EVENT(4, 1);
             const int bid = base + bit * a.S + s;
             const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(need >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)need, 0u));
             if (nd) s_q[qcnt + rank] = ((unsigned)bid << 6) | (unsigned)lane;
             qcnt += nneed;
         };
-        while (mask) {
-            // (Targets used to come through scalar loads, s_load_dwordx16 x 3 per scanned box: one dependent scalar-cache
-            // miss chain per scan; measured 95 -> 80 us for the launch with the vector path of scan_box alone.)
-            unsigned long long cm = mask;                                // every surviving box of the round
-            mask = 0ull;
-            // ---- precise filter with the lane's current bound, two boxes per step in packed fp32 (same
-            // operation order per box as box_lb; the second box is judged after the first one's scan)
-            while (cm) {
-            const int bA = __builtin_ctzll(cm);
-            cm &= cm - 1;
-            const bool hasB = cm != 0;
-            const int bB = hasB ? __builtin_ctzll(cm) : bA;
-            if (hasB) cm &= cm - 1;
-            f2 L0, L1, L2, H0, H1, H2;
-            if (BOXL) {
-                const float *pA = s_bb + 6 * bA, *pB = s_bb + 6 * bB;
-                L0 = f2{pA[0], pB[0]}; L1 = f2{pA[1], pB[1]}; L2 = f2{pA[2], pB[2]};
-                H0 = f2{pA[3], pB[3]}; H1 = f2{pA[4], pB[4]}; H2 = f2{pA[5], pB[5]};
-            } else {
-                L0 = f2{rl(lo0, bA), rl(lo0, bB)}; L1 = f2{rl(lo1, bA), rl(lo1, bB)}; L2 = f2{rl(lo2, bA), rl(lo2, bB)};
-                H0 = f2{rl(hi0, bA), rl(hi0, bB)}; H1 = f2{rl(hi1, bA), rl(hi1, bB)}; H2 = f2{rl(hi2, bA), rl(hi2, bB)};
-            }
-            const f2 a0 = L0 - qx2, c0 = qx2 - H0, a1 = L1 - qy2, c1 = qy2 - H1, a2 = L2 - qz2, c2 = qz2 - H2;
-            const f2 e0 = {fmaxf(fmaxf(a0.x, c0.x), 0.f), fmaxf(fmaxf(a0.y, c0.y), 0.f)};
-            const f2 e1 = {fmaxf(fmaxf(a1.x, c1.x), 0.f), fmaxf(fmaxf(a1.y, c1.y), 0.f)};
-            const f2 e2 = {fmaxf(fmaxf(a2.x, c2.x), 0.f), fmaxf(fmaxf(a2.y, c2.y), 0.f)};
-            const f2 lb = (e0 * e0 + e1 * e1) + e2 * e2;
-            wp += PR_WORK(2);
-            PH(2);
-#pragma unroll 1   // one copy of the scan code (two copies cost 30 VGPRs of occupancy)
-            for (int h = 0; h < (hasB ? 2 : 1); ++h) {
-                const float lbh = h ? lb.y : lb.x;
+        // (Targets used to come through scalar loads, s_load_dwordx16 x 3 per scanned box: one dependent scalar-cache
+        // miss chain per scan; measured 95 -> 80 us for the launch with the vector path of scan_box alone.)
+        // ---- precise filter with the lane's current bound, two boxes per step in packed fp32 (same operation order per box
+        // as box_lb; the second box is judged after the first one's scan).
+        // The candidates (bm, bb, thr) pass three kinds of box: not needed and enqueued (the common ones: neither touches them)
+        // and densely scanned / drained (rare: new candidates are computed beside the old ones).  With all three in one loop
+        // body the compiler merged them in a block of copies that the common paths ran too: 14 v_mov_b32 per enqueued box of
+        // a K = 3 item (7 + 7; 3 + 4 for K = 1).  So the loop is split: the INNER loop takes steps, judges both boxes and
+        // enqueues, and the candidates are loop-invariant in it (it only reads thr); a box to scan or a full queue leaves it
+        // with the box's number in `rare`, and the outer loop does the rare work at its ONE site (a second copy of the scan
+        // costs registers).  When that happens at a step's first box the second one stays in the mask and leads the next
+        // step: it is judged against the bound the rare work may just have lowered, as before, from the same lower bound
+        // (evaluated again: the rare path pays).  The order of the evaluations is what it was.
+        // The work count: two tests per step, and a round of n survivors takes (n + 1) / 2 steps when none is re-done --
+        // counted once per round, so that the sum is the one this loop always reported whatever steps are re-done.
+        wp += PR_WORK(2 * ((__builtin_popcountll(mask) + 1) >> 1));
+        // a box some lane needs: enqueued, or `rare` says what the outer loop has to do (>= 0 scan this box, -2 drain the queue)
+#define PR_NEEDED_BOX(BIT, NEED, ND)                                                                              \
+        PRUNE_EVENT(3, 1);                                                                                        \
+        const int nneed = __builtin_popcountll(NEED);                                                             \
+        if (nneed > queue_max) { rare = (BIT); left = cm; cm = 0ull; }                                            \
+        else { enqueue_box((BIT), (NEED), (ND), nneed); PH(4);                                                    \
+               if (qcnt > QCAP - 64) { rare = -2; left = cm; cm = 0ull; } }   /* uniform: qcnt is a wave-wide count */
+        unsigned long long cm = mask;                                    // every surviving box of the round
+        for (;;) {
+            int rare = -1;
+            unsigned long long left = 0ull;                              // the boxes still to judge when the loop is left for rare work
+            // ONE exit, at the head, on ONE scalar: every `break` out of a loop is a flag the compiler sets, merges and tests on
+            // all paths; the rare paths empty the mask instead and park the rest of it in `left`
+            while (cm != 0) {
+                const int bA = __builtin_ctzll(cm);
+                const unsigned long long restA = cm & (cm - 1);          // without box A
+                const bool hasB = restA != 0;
+                const int bB = hasB ? __builtin_ctzll(restA) : bA;
+                f2 lb;
+                if constexpr (BOXL) {
+                    // Paired by AXIS, not by box: per box (lo0, lo1), (hi0, hi1) and (lo2, -hi2) are three aligned register pairs as
+                    // the LDS reads deliver them (the coarse round parks them in this order), so no operand of a packed
+                    // instruction is assembled from two boxes' registers (that took nine v_mov_b32 per step).  Per box the
+                    // operations of box_lb in its order: {lo0, lo1} - {qx, qy}; {qx, qy} - {hi0, hi1}; {lo2, -hi2} + {-qz, qz}
+                    // (negation is exact and addition commutes: the bits of lo2 - qz and qz - hi2); max3 per axis; {ex, ey}^2
+                    // packed; (ex^2 + ey^2) + ez^2.  The two boxes are independent chains that share the packed square of
+                    // {ezA, ezB} and the last packed add.  s_bb is wave-uniform for the compiler too (the caller's wave index
+                    // is a scalar), so 24 * bA is SALU work.
+                    const f2 *pA = (const f2 *)(s_bb + 6 * bA), *pB = (const f2 *)(s_bb + 6 * bB);
+                    const f2 LA = pA[0], HA = pA[1], ZA = pA[2];
+                    const f2 LB = pB[0], HB = pB[1], ZB = pB[2];
+                    const f2 aA = LA - qxy, cA = qxy - HA, zA = ZA + qzn;
+                    const f2 aB = LB - qxy, cB = qxy - HB, zB = ZB + qzn;
+                    const f2 eA = {fmaxf(fmaxf(aA.x, cA.x), 0.f), fmaxf(fmaxf(aA.y, cA.y), 0.f)};
+                    const f2 eB = {fmaxf(fmaxf(aB.x, cB.x), 0.f), fmaxf(fmaxf(aB.y, cB.y), 0.f)};
+                    const f2 ez = {fmaxf(fmaxf(zA.x, zA.y), 0.f), fmaxf(fmaxf(zB.x, zB.y), 0.f)};
+                    const f2 sA = eA * eA, sB = eB * eB;
+                    float tA = sA.x + sA.y, tB = sB.x + sB.y;
+                    asm("" : "+v"(tA), "+v"(tB));     // two scalar adds: packed across the boxes they cost three v_mov_b32 to pair up
+                    lb = f2{tA, tB} + ez * ez;
+                } else {
+                    // the cloud-resident form keeps the bounds in the lanes of the coarse round and pairs box A with box B per axis
+                    // (twelve v_readlane per step): the form this filter had before, unchanged
+                    const f2 L0 = f2{rl(lo0, bA), rl(lo0, bB)}, L1 = f2{rl(lo1, bA), rl(lo1, bB)}, L2 = f2{rl(lo2, bA), rl(lo2, bB)};
+                    const f2 H0 = f2{rl(hi0, bA), rl(hi0, bB)}, H1 = f2{rl(hi1, bA), rl(hi1, bB)}, H2 = f2{rl(hi2, bA), rl(hi2, bB)};
+                    const f2 a0 = L0 - qx2, c0 = qx2 - H0, a1 = L1 - qy2, c1 = qy2 - H1, a2 = L2 - qz2, c2 = qz2 - H2;
+                    const f2 e0 = {fmaxf(fmaxf(a0.x, c0.x), 0.f), fmaxf(fmaxf(a0.y, c0.y), 0.f)};
+                    const f2 e1 = {fmaxf(fmaxf(a1.x, c1.x), 0.f), fmaxf(fmaxf(a1.y, c1.y), 0.f)};
+                    const f2 e2 = {fmaxf(fmaxf(a2.x, c2.x), 0.f), fmaxf(fmaxf(a2.y, c2.y), 0.f)};
+                    lb = (e0 * e0 + e1 * e1) + e2 * e2;
+                }
+                PRUNE_EVENT(2, 1);
+                PH(2);
 #ifdef REART_PRUNE_STATS   // how many of the 64 queries need a scanned box: 1 | 2-3 | 4-7 | 8+  (K = 1 only)
                 if (KK == 1) {
-                    const int nl = __builtin_popcountll(__ballot(lbh <= thr));
+                    const int nl = __builtin_popcountll(__ballot(lb.x <= thr));
                     if (nl) PRUNE_STAT(nl == 1 ? 4 : (nl < 4 ? 5 : (nl < 8 ? 6 : 7)), 1);
                 }
 #endif
-                const bool nd = lbh <= thr;
-                const unsigned long long need = __ballot(nd);
-                if (need) {
-                    const int nneed = __builtin_popcountll(need);
-                    if (nneed <= queue_max) {
-                        enqueue_box(h ? bB : bA, need, nd, nneed);
-                        PH(4);
-                        if (qcnt > QCAP - 64) { drain_queue(); PH(5); }   // uniform: qcnt is a wave-wide count
-                    } else {
-                        scan_box(h ? bB : bA);
-                        PH(3);
-                    }
+                cm = restA;
+                const bool ndA = lb.x <= thr;
+                const unsigned long long needA = __ballot(ndA);
+                if (needA) { PR_NEEDED_BOX(bA, needA, ndA) }
+                if (cm == 0) continue;                                   // the round's last box; or rare work first (box B is in `left`)
+                cm = restA & (restA - 1);
+#ifdef REART_PRUNE_STATS
+                if (KK == 1) {
+                    const int nl = __builtin_popcountll(__ballot(lb.y <= thr));
+                    if (nl) PRUNE_STAT(nl == 1 ? 4 : (nl < 4 ? 5 : (nl < 8 ? 6 : 7)), 1);
                 }
+#endif
+                const bool ndB = lb.y <= thr;
+                const unsigned long long needB = __ballot(ndB);
+                if (needB) { PR_NEEDED_BOX(bB, needB, ndB) }
             }
-            }
+            if (rare == -1) break;
+            if (rare >= 0) { scan_box(rare); PH(3); }
+            else { drain_queue(); PH(5); }
+            cm = left;
         }
+#undef PR_NEEDED_BOX
     }
 
+    PRUNE_EVENT(7, 1);
     PH(2);
     if (qcnt > 0) drain_queue();
     PH(5);
@@ -597,8 +678,11 @@ __device__ __forceinline__ void knn_pruned_wave(const float *qcloud, const int *
 // ------------------------------------------------------------------------------------------------------------
 // The search launch: up to two K = 1 jobs (the Chamfer directions) and one K = 3 job (the flow search);
 // SearchArgs is declared in internal.h.
+// Exactly PR_WPE waves per SIMD, as a minimum AND a maximum: with the wave index in a scalar register the kernel needs 70
+// VGPRs, which the hardware would run at seven -- a ninth resident workgroup per compute unit by LDS, a residency this kernel was not
+// tuned at (the seventh wave was measured to buy nothing, DESIGN_HISTORY.md).  The maximum makes the allocation 73..80.
 template <bool BATCH>
-__global__ __launch_bounds__(64 * PR_SMAX, PR_WPE) void knn_group_kernel(Batched<SearchArgs> ab) {
+__global__ __launch_bounds__(64 * PR_SMAX) __attribute__((amdgpu_waves_per_eu(PR_WPE, PR_WPE))) void knn_group_kernel(Batched<SearchArgs> ab) {
     // instance of a batch (gridDim.x is a multiple of 8: blockIdx.x & 7 is still the XCD); a single one reads at a fixed offset
     PH_ENTRY;
     const SearchArgs &a_ = ab.a[BATCH ? blockIdx.y : 0];
@@ -618,7 +702,10 @@ __global__ __launch_bounds__(64 * PR_SMAX, PR_WPE) void knn_group_kernel(Batched
     const int share = a_.share;
     asm volatile("" :: "s"(a.n1), "s"(a.n3), "s"(a.G), "s"(a.per), "s"(a.S1), "s"(a.S3), "s"(a.interleave), "s"(a.sparse), "s"(items), "s"(prof), "s"(share));
     const int L = blockIdx.x, x = L & 7, r = L >> 3;
-    const int s = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    // the wave index as a SCALAR: threadIdx.x >> 6 is the same in all lanes of a wave, but divergent as far as the compiler can
+    // tell -- and with it the wave's LDS base (every box address of the precise filter was a 64-bit VALU multiply-add), the
+    // statistics counter (a v_add per event) and the box number of an enqueue
+    const int s = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     // XCD-local item r: two K = 1 items alternate with one K = 3 item while both kinds last
     const int items1 = a.n1 * a.per, items3 = a.n3 * a.per;
     const int mixed = (a.n1 == 2 && a.n3) ? 3 * a.per : 0;
@@ -674,7 +761,12 @@ __global__ __launch_bounds__(64 * PR_SMAX, PR_WPE) void knn_group_kernel(Batched
         float *s_tg = (float *)wl;
         float *s_qc = (float *)(wl + 64 * 4);
         unsigned long long *s_key = (unsigned long long *)(wl + 64 * 4 + 64 * 16);
-        unsigned int *s_q = (unsigned int *)(wl + 64 * 4 + 64 * 16 + 3 * 64 * 8);
+        // the queue space's offset as ONE scalar the compiler cannot take apart: a box's three pairs are then read through one
+        // address register (s_bb + 24 * box, offsets 0 / 8 / 16); as base + 2816 the constant did not fit ds_read2_b64's
+        // offset field and every box took a second v_mov_b32
+        int q_off = s * PR_LDS_WAVE_BYTES + (64 * 4 + 64 * 16 + 3 * 64 * 8);
+        asm("" : "+s"(q_off));
+        unsigned int *s_q = (unsigned int *)(s_dyn + q_off);
         static_assert(384 + PR_QCAP >= 3 * 3 * 64, "neighbour seeds of a K = 3 item: 9 x 64 floats in the result slots + the queue's space");
         static_assert(PR_QCAP >= 384 + 128, "box bounds of a coarse round + at least two drain steps of queue");
         float *s_bb = (float *)s_q;          // the bounds of a coarse round's 64 boxes take the first 384 entries of the queue's space
