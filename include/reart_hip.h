@@ -394,7 +394,11 @@ typedef struct reart_relax_config {
     /* Tuning and measurement switches.  0 = the library default everywhere.  The library reads NO environment
      * variable in any call path: the caller decides once per instance (reart_amd/relax.py maps REART_* variables
      * to these fields when an engine is built), so the ranks of a job cannot diverge mid-run. */
-    int search_mode;         /* 0: exact box-pruned warm-started search (default); 1: cold brute force (same results) */
+    int search_mode;         /* 0: exact box-pruned warm-started search (default); 1: cold brute force (same results); */
+                             /* 2 | 3 | 4: the pruned search in the forms only very large shapes take by themselves,   */
+                             /* for tests (same results): 2 frame offsets as 64-bit products (arrays of 2^31 bytes and  */
+                             /* more), 3 launch positions through the order array and the query map instead of item    */
+                             /* words (more than 2^21 - 1 pairs), 4 both                                                */
     int tune_slices;         /* waves (box slices) per search workgroup, 1..4 (default 3)  */
     int tune_slices_flow;    /* the same for the K = 3 flow search (default: tune_slices)  */
     int tune_sparse;         /* boxes needed by <= n queries of a wave go through the (query, box) queue instead of a  */

@@ -162,9 +162,11 @@ struct KnnJob {
     int nqg;               // ceil(P1/64)
     int P2;
     const int *tlen;       // nullable per-batch target count (ragged SoA rows, stride Ppad)
+    unsigned int nqg_rcp;  // pruned search only: reart_div_magic(nqg), set by the search launcher (the wave splits its pair
+                           // b * nqg + g with one multiply-high, reart_div_by_magic below)
+    int L;
     // ---- not read by a search wave whose launch has item words (SearchArgs::item)
     const int *qmap;       // nullable per-batch query frame index into q
-    int L;
     const int64_t *lenq;   // nullable, rows >= lenq[n] produce zeros
     const int64_t *lent;   // nullable, number of valid targets
     const int *border;     // pruned search only, nullable: [N * nqg] (batch, query group) pair = b * nqg + g handled at
@@ -214,6 +216,24 @@ REART_HD static inline bool reart_search_items_fit(long pairs, int frames) {   /
     return pairs <= (long)SEARCH_ITEM_PAIR_MASK && frames + 1 < (1 << (32 - SEARCH_ITEM_PAIR_BITS));
 }
 REART_HD static inline unsigned int reart_search_item(int pair, int qb) { return (unsigned int)pair | ((unsigned int)(qb + 1) << SEARCH_ITEM_PAIR_BITS); }
+// n / d without a division where d is known in front of the launch: m = floor((2^32 - 1) / d) (the host, once), then
+// q' = high word of n * m and ONE correction.  m >= (2^32 - d) / d, so n * m / 2^32 >= n / d - n / 2^32 > n / d - 1 for every
+// n < 2^32, and m <= 2^32 / d, so q' <= n / d: q' is the quotient or one below it, whatever d >= 1 -- exact for every query-group
+// count and every pair an item word or an order array can hold (tests/test_search_item_div_cpu.py walks them).  A software
+// division is ~ 45 instructions with a v_rcp_iflag_f32 and a v_readfirstlane on a search wave's dependent chain.
+REART_HD static inline unsigned int reart_div_magic(unsigned int d) { return 0xFFFFFFFFu / d; }
+REART_HD static inline unsigned int reart_div_by_magic(unsigned int n, unsigned int d, unsigned int m) {
+    const unsigned int q = (unsigned int)(((unsigned long long)n * m) >> 32);
+    return q + (n - q * d >= d ? 1u : 0u);
+}
+// Frame offsets of a search job in 32 bits: true when the largest BYTE offset a search wave forms from a frame's base --
+// queries [frames][P1][3], seeds and records [B][P1][K] (4 bytes each), targets [B][3][Ppad], boxes [B][Ppad / NN_BOX][8] --
+// stays below 2^31 for the job (a frame's index times its stride is then an s_mul_i32 and one 64-bit add to the base).
+// B: batches; q holds one query cloud per batch (qmap and the item words permute them: a query frame is < B).
+REART_HD static inline bool reart_search_off32(long long B, long long P1, long long Ppad, int K) {
+    const long long lim = 1ll << 31;
+    return B * P1 * 3 * 4 < lim && B * P1 * K * 4 < lim && B * 3 * Ppad * 4 < lim && B * (Ppad / NN_BOX) * 8 * 4 < lim;
+}
 // exact search with box pruning + warm start (prune.hip): ONE launch for up to two K = 1 jobs (the Chamfer
 // directions) and one K = 3 job (the flow search); one workgroup per (job, batch, query group), S waves each.
 // The words that pick a workgroup's item and its record come first (one scalar load), the jobs behind them.
@@ -234,6 +254,7 @@ struct SearchArgs {
                                    // query groups) with the cloud copied into LDS (knn_cloud_kernel); S1 / S3 then unused
     int cloud_slices;              // cloud-resident form: box slices per query group, 1 | 2 | 4 | 8 (0: the default, 4)
     int k_nqg;                     // query groups per batch (set by the launcher)
+    int wide;                      // 1: 64-bit frame offsets also where 32 bits would do (the form very large clouds take; tests)
     KnnJob k1[2];                  // K = 1 jobs; results pd / pi [B][P1] (pi int32: also the next seed)
     KnnJob k3;                     // K = 3 job; results pd / pi [B][P1][3]: the three best 8-target BLOCKS
                                    // (block minimum, first index), rescanned with the exact key by the consumer

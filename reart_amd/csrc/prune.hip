@@ -44,7 +44,7 @@
 //     arithmetic on blockIdx gives (job, launch position).  Then, still in front of the opening barrier, everything else is
 //     requested: the position's item word (a scalar load -- the previous launch wrote it, the longest wait of the head; it
 //     holds the (batch, query group) pair AND the batch's query frame, internal.h) and the job's members by value (KnnJob
-//     keeps them contiguous: s_load_dwordx16 + x4 + x2 at the job's offset).  One wait, at the barrier.  Behind it the
+//     keeps them contiguous: s_load_dwordx16 + x8 at the job's offset).  One wait, at the barrier.  Behind it the
 //     batch's target count (scalar load of tlen[b], only the flow job has one), the query (one global_load_dwordx3 through a
 //     uniform base + 32-bit lane offset) and the K seeds are requested together; the count is wanted when the seeds are in.
 //     All 3 K seed targets are gathered through the clamped index before the first LDS store (+inf is chosen at the store).
@@ -67,6 +67,20 @@
 //     round, read with v_readlane) keeps the per-box pairing it had -- it sits at 80 VGPRs and the axis form cost it a
 //     resident wave -- and takes the same loop structure and the one-block coarse round.  Every form evaluates the same
 //     operations in the same order: the filter's decisions, and with them the executed pairs, are bit for bit the same.
+//   * The fixed part of a search wave (everything outside the filter loop; counts per region in
+//     profiles/search_fixed_isa_counts.txt, tools/isa_regions.py).  Nearly half of the ~ 1 560 instructions a wave issues are set-up
+//     and wrap-up that every wave repeats in the same form.  Cut where the result does not need them: the (batch, query group)
+//     pair is split by a reciprocal of nqg the launcher puts beside it in the job (reart_div_by_magic, internal.h: one
+//     s_mul_hi_u32 and one correction where a software division took ~ 45 instructions with a v_rcp_iflag_f32 and a
+//     v_readfirstlane_b32 on the wave's chain); the frame bases are s_mul_i32 products where the launcher finds every offset
+//     below 2^31 bytes (template parameter OFF32, reart_search_off32; the 64-bit form stays for larger clouds); the order array
+//     and the query map of launches without item words are scalar loads (as vector loads they made the query frame a vector
+//     value for every launch: two v_mul_lo_u32 and two v_readfirstlane_b32 in front of the query load); the counter's seed term
+//     is counted in the bound loop (it was a second software division); the partial bounds of the workgroup's waves are
+//     exchanged by four reads at fixed offsets, two selects on S and a v_min3_f32 + v_min_f32 (the loop over S was ~ 76
+//     instructions, two canonicalising v_max per fminf); the six coordinate summaries of the rows are ONE block of 24 DPP
+//     steps taken across the values (1 s_nop for 24).  Per wave ~ 120 of ~ 650 fixed instructions; every operation that
+//     decides anything is the same in the same order.
 //   * Neighbour seeds (round 3).  A lane's own seed is a poor bound exactly when it matters: every iteration a fifth of
 //     the points re-sample their part label and jump (queries of the x -> y search, targets of the y -> x search), their
 //     old neighbour is then far away, and those lanes -- 23 % of them -- used to produce 78 % of all (query, box)
@@ -92,8 +106,11 @@ struct SearchHot {
     unsigned int *cost;
     int P1, Ppad, nqg, P2;
     const int *tlen;
+    unsigned int nqg_rcp;
+    int L;                 // not used: fills the run to 24 words (s_load_dwordx16 + x8)
 };
-static_assert(sizeof(SearchHot) == 88 && offsetof(KnnJob, tlen) == offsetof(SearchHot, tlen) && offsetof(KnnJob, q) == 0 && offsetof(KnnJob, q_alt) == offsetof(SearchHot, q_alt) &&
+static_assert(sizeof(SearchHot) == 96 && offsetof(KnnJob, tlen) == offsetof(SearchHot, tlen) && offsetof(KnnJob, q) == 0 && offsetof(KnnJob, q_alt) == offsetof(SearchHot, q_alt) &&
+              offsetof(KnnJob, nqg_rcp) == offsetof(SearchHot, nqg_rcp) &&
               offsetof(KnnJob, tsoa) == offsetof(SearchHot, tsoa) && offsetof(KnnJob, boxes) == offsetof(SearchHot, boxes) &&
               offsetof(KnnJob, seed) == offsetof(SearchHot, seed) && offsetof(KnnJob, pd) == offsetof(SearchHot, pd) &&
               offsetof(KnnJob, pi) == offsetof(SearchHot, pi) && offsetof(KnnJob, cost) == offsetof(SearchHot, cost) &&
@@ -183,6 +200,14 @@ extern "C" int reart_debug_prune_head(unsigned long long *out, int reset) {
 #define PH_ENTRY_FLUSH(row) do { } while (0)
 #endif
 
+// -DREART_PRUNE_MARKS (tools/isa_regions.py): a comment line in the emitted code where a region of a search wave's fixed part
+// begins -- no instruction, but the scheduler may move arithmetic across it, so region counts are good to a few instructions
+#ifdef REART_PRUNE_MARKS
+#define PR_MARK(name) asm volatile("; PRMARK " name)
+#else
+#define PR_MARK(name) do { } while (0)
+#endif
+
 #define PR_WORK(w) ((unsigned)(w) << 20)   // the work count lives in bits 20..31 of a wave's statistics counter, the pairs below
 
 // min / max of a lane's value with a DPP-permuted copy in ONE instruction (v_min_f32_dpp).  Written through the compiler
@@ -206,6 +231,46 @@ PR_DPP_OP(pr_max_hm, "v_max_f32_dpp", "row_half_mirror")
 PR_DPP_OP(pr_max_rm, "v_max_f32_dpp", "row_mirror")
 __device__ __forceinline__ float pr_row16_min(float v) { return pr_min_rm(pr_min_hm(pr_min_q2(pr_min_q1(v)))); }
 __device__ __forceinline__ float pr_row16_max(float v) { return pr_max_rm(pr_max_hm(pr_max_q2(pr_max_q1(v)))); }
+// The six row summaries of the query's coordinates (minimum and maximum per axis) in ONE block: the four steps are taken
+// across the six values, so five instructions stand between a write and the DPP read of it and the block needs one s_nop
+// (for whatever wrote the inputs) where six chains of pr_row16_* issue 24.  Outputs are early-clobber: the inputs are read
+// by steps behind the first writes.  Same instructions, same operands per value: the same bits.
+#define PR_ROW6_STEP(A, B, C, CTRLTXT)                                                                            \
+    "v_min_f32_dpp %0, " A ", " A " " CTRLTXT " row_mask:0xf bank_mask:0xf\n\t"                                   \
+    "v_min_f32_dpp %1, " B ", " B " " CTRLTXT " row_mask:0xf bank_mask:0xf\n\t"                                   \
+    "v_min_f32_dpp %2, " C ", " C " " CTRLTXT " row_mask:0xf bank_mask:0xf\n\t"
+#define PR_ROW6_STEPX(A, B, C, CTRLTXT)                                                                           \
+    "v_max_f32_dpp %3, " A ", " A " " CTRLTXT " row_mask:0xf bank_mask:0xf\n\t"                                   \
+    "v_max_f32_dpp %4, " B ", " B " " CTRLTXT " row_mask:0xf bank_mask:0xf\n\t"                                   \
+    "v_max_f32_dpp %5, " C ", " C " " CTRLTXT " row_mask:0xf bank_mask:0xf\n\t"
+__device__ __forceinline__ void pr_row16_box(float x, float y, float z, float &l0, float &l1, float &l2, float &h0, float &h1, float &h2) {
+    asm("s_nop 1\n\t"
+        PR_ROW6_STEP("%6", "%7", "%8", "quad_perm:[1,0,3,2]") PR_ROW6_STEPX("%6", "%7", "%8", "quad_perm:[1,0,3,2]")
+        PR_ROW6_STEP("%0", "%1", "%2", "quad_perm:[2,3,0,1]") PR_ROW6_STEPX("%3", "%4", "%5", "quad_perm:[2,3,0,1]")
+        PR_ROW6_STEP("%0", "%1", "%2", "row_half_mirror") PR_ROW6_STEPX("%3", "%4", "%5", "row_half_mirror")
+        PR_ROW6_STEP("%0", "%1", "%2", "row_mirror") PR_ROW6_STEPX("%3", "%4", "%5", "row_mirror")
+        : "=&v"(l0), "=&v"(l1), "=&v"(l2), "=&v"(h0), "=&v"(h1), "=&v"(h2) : "v"(x), "v"(y), "v"(z));
+}
+// minimum of three / two floats that are never NaN, in ONE instruction each: fminf of a value the compiler has not computed
+// itself (an LDS read) is wrapped in a canonicalising v_max x,x per operand
+__device__ __forceinline__ float pr_min3(float a, float b, float c) {
+    float r;
+    asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
+__device__ __forceinline__ float pr_min2(float a, float b) {
+    float r;
+    asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+// a frame's base inside an array of 4-byte elements, n1 * n2 elements per frame.  OFF32 (the launcher: reart_search_off32):
+// every such offset of the launch is below 2^31 bytes, so it is s_mul_i32 products and a 64-bit add; otherwise every
+// product is formed in 64 bits from the first factor on (s_mul_i32 + s_mul_hi_u32 + the cross terms per factor)
+template <bool OFF32>
+__device__ __forceinline__ const char *pr_frame(const void *base, int frame, int n1, int n2) {
+    if (OFF32) return (const char *)base + (size_t)(4u * (unsigned)frame * (unsigned)n1 * (unsigned)n2);
+    return (const char *)base + 4 * ((size_t)frame * (size_t)n1 * (size_t)n2);
+}
 
 __device__ __forceinline__ float rl(float v, int lane) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
@@ -229,7 +294,7 @@ __device__ __forceinline__ float box_lb(float lo0, float lo1, float lo2, float h
 // s_q otherwise; skipped when that space is too small for KK x 3 x 64 floats).
 // The caller has resolved what depends on the batch: `qcloud` the query cloud [P1][3] of batch b (q + qmap[b] * P1 * 3, or
 // q_alt), `seed_p` the job's seeds, `n2` the batch's target count -- nothing here waits for a per-batch word.
-template <int KK, bool LDSV, int QCAP, bool BOXL>
+template <int KK, bool LDSV, int QCAP, bool BOXL, bool OFF32>
 __device__ __forceinline__ void knn_pruned_wave(const float *qcloud, const int *seed_p, const int P1, const int n2,
                                                 const int S, const int sparse, const int b, const int g,
                                                 const int s, const float *cloud, const int cstride, const float *boxes_p,
@@ -246,6 +311,7 @@ __device__ __forceinline__ void knn_pruned_wave(const float *qcloud, const int *
     // (wave-uniform base) + (32-bit lane offset in bytes), as in the drain: no 64-bit lane address to build or keep
     const float *qp = (const float *)((const char *)qcloud + 12u * (unsigned)ic);
     const float qx = qp[0], qy = qp[1], qz = qp[2];
+    PR_MARK("seeds");
     PH_STAMP(0, "v"(qx), "v"(qy), "v"(qz));
     const f2 qx2 = {qx, qx}, qy2 = {qy, qy}, qz2 = {qz, qz};
     const f2 qxy = {qx, qy}, qzn = {-qz, qz};             // the precise filter's operands (paired by axis)
@@ -260,7 +326,7 @@ __device__ __forceinline__ void knn_pruned_wave(const float *qcloud, const int *
     float thr = 0.f;
     unsigned int wp = 0u;             // statistics counter, see PR_WORK below
     {
-        const int *sd = (const int *)((const char *)(seed_p + (size_t)b * P1 * KK) + 4u * KK * (unsigned)ic);
+        const int *sd = (const int *)(pr_frame<OFF32>(seed_p, b, P1, KK) + 4u * KK * (unsigned)ic);
         int sj[KK];
         bool ok = true;
 #pragma unroll
@@ -286,8 +352,10 @@ __device__ __forceinline__ void knn_pruned_wave(const float *qcloud, const int *
             float sx[KK], sy[KK], sz[KK];
 #pragma unroll
             for (int k = 0; k < KK; ++k) {
-                const int j = ok ? sj[k] : 0;
-                sx[k] = tx[j]; sy[k] = ty[j]; sz[k] = tz[j];
+                // (wave-uniform row) + (32-bit lane offset in bytes), as the query's load: no 64-bit lane address per row
+                const unsigned jo = 4u * (unsigned)(ok ? sj[k] : 0);
+                sx[k] = *(const float *)((const char *)tx + jo); sy[k] = *(const float *)((const char *)ty + jo);
+                sz[k] = *(const float *)((const char *)tz + jo);
             }
             if (!LDSV) __builtin_amdgcn_sched_barrier(0);      // the scheduler must not sink a gather below a store
 #pragma unroll
@@ -297,6 +365,7 @@ __device__ __forceinline__ void knn_pruned_wave(const float *qcloud, const int *
                 s_scr[(3 * k + 2) * 64 + lane] = ok ? sz[k] : INFINITY;
             }
             PH_STAMP(2, "v"(lane));
+            PR_MARK("bound");
             thr = INFINITY;
             const float *row = s_scr + (lane & 48);
             // s_xthr (the workgroup's exchange array [S][64]): the S waves of the workgroup hold the same 64 queries, so each
@@ -304,7 +373,6 @@ __device__ __forceinline__ void knn_pruned_wave(const float *qcloud, const int *
             // lives, where they still run side by side); without it every wave evaluates all 16 candidates
             const bool split = s_xthr != nullptr && a.S > 1;
             const int c0 = split ? 2 * s : 0, cstep = split ? 2 * a.S : 2;
-            wp = 64u * KK * 2u * (unsigned)((16 - c0 + cstep - 1) / cstep);   // the seed candidates this wave evaluates
 #pragma unroll 1      // rolled: unrolled, the 72 LDS loads of a K = 3 item in flight cost 25 VGPRs, i.e. two resident waves per SIMD
             for (int c = c0; c < 16; c += cstep) {
                 f2 far = {0.f, 0.f};
@@ -317,11 +385,23 @@ __device__ __forceinline__ void knn_pruned_wave(const float *qcloud, const int *
                     far = f2{fmaxf(far.x, d.x), fmaxf(far.y, d.y)};
                 }
                 thr = fminf(thr, fminf(far.x, far.y));
+                wp += 64u * KK * 2u;                 // the seed candidates this wave evaluates: counted where they are, one s_add a
+                                                     // trip (as (16 - c0 + cstep - 1) / cstep in front of the loop: a software division)
             }
+            PR_MARK("exchange");
             if (split) {
                 s_xthr[64 * s + lane] = thr;
                 __syncthreads();                     // every live wave of the workgroup runs this prologue (waves >= S have left)
-                for (int t = 0; t < a.S; ++t) thr = fminf(thr, s_xthr[64 * t + lane]);
+                // The minimum over the S live waves' slots, the wave's own among them: four reads at fixed offsets, the slots of
+                // waves that do not exist (never written: any bits) replaced by +inf on a uniform condition, two instructions of
+                // minima.  (As `for (t < a.S) thr = fminf(thr, s_xthr[..])` the loop was unrolled by two with exit flags and every
+                // fminf canonicalised both operands: ~ 76 instructions.)  No operand is ever NaN: a partial bound is a
+                // fminf / fmaxf of squared distances, and fmaxf(0, NaN) = 0 drops the NaN a NaN or infinite query produces --
+                // that query is dealt with below, by the test on the query itself.  The minimum of a set of non-NaN floats
+                // does not depend on the order they are taken in, and +0 / -0 cannot both occur (distances are >= +0): the
+                // same bits as the loop's.
+                const float x0 = s_xthr[lane], x1 = s_xthr[64 + lane], x2 = s_xthr[128 + lane], x3 = s_xthr[192 + lane];
+                thr = pr_min2(pr_min3(x0, x1, a.S > 2 ? x2 : INFINITY), a.S > 3 ? x3 : INFINITY);
             }
             // a NaN query: fmaxf / fminf drop the NaN distances (fmaxf(0, NaN) = 0), so the bound would come out 0, not NaN --
             // test the query itself and prune nothing for it (its lower bounds are NaN and fail every compare: index -1)
@@ -338,8 +418,9 @@ __device__ __forceinline__ void knn_pruned_wave(const float *qcloud, const int *
     }
 
     // ---- group summaries: 4 groups of 16 lanes
-    const float gl0 = pr_row16_min(qx), gl1 = pr_row16_min(qy), gl2 = pr_row16_min(qz);
-    const float gh0 = pr_row16_max(qx), gh1 = pr_row16_max(qy), gh2 = pr_row16_max(qz);
+    PR_MARK("rows");
+    float gl0, gl1, gl2, gh0, gh1, gh2;
+    pr_row16_box(qx, qy, qz, gl0, gl1, gl2, gh0, gh1, gh2);
     const float gt = pr_row16_max(thr);
     float G[4][7];
 #pragma unroll
@@ -454,6 +535,7 @@ __device__ __forceinline__ void knn_pruned_wave(const float *qcloud, const int *
     };
     const int per = 64 * a.S;
     PH(0);
+    PR_MARK("filter");
     for (int base = 0; base < nbox; base += per) {
         // ---- coarse filter: lane l looks at box base + l*S + s
         const int bid = base + lane * a.S + s;
@@ -670,6 +752,7 @@ __device__ __forceinline__ void knn_pruned_wave(const float *qcloud, const int *
     PH(5);
     PH_FLUSH(0, 5);
     PH_HEAD_FLUSH(KK == 1 ? 0 : 1);
+    PR_MARK("park");
     qx_o = qx; qy_o = qy; qz_o = qz;
     work_o = (int)(wp >> 20); pairs_o = wp & 0xFFFFFu;
 }
@@ -681,7 +764,7 @@ __device__ __forceinline__ void knn_pruned_wave(const float *qcloud, const int *
 // Exactly PR_WPE waves per SIMD, as a minimum AND a maximum: with the wave index in a scalar register the kernel needs 70
 // VGPRs, which the hardware would run at seven -- a ninth resident workgroup per compute unit by LDS, a residency this kernel was not
 // tuned at (the seventh wave was measured to buy nothing, DESIGN_HISTORY.md).  The maximum makes the allocation 73..80.
-template <bool BATCH>
+template <bool BATCH, bool OFF32>
 __global__ __launch_bounds__(64 * PR_SMAX) __attribute__((amdgpu_waves_per_eu(PR_WPE, PR_WPE))) void knn_group_kernel(Batched<SearchArgs> ab) {
     // instance of a batch (gridDim.x is a multiple of 8: blockIdx.x & 7 is still the XCD); a single one reads at a fixed offset
     PH_ENTRY;
@@ -720,8 +803,13 @@ __global__ __launch_bounds__(64 * PR_SMAX) __attribute__((amdgpu_waves_per_eu(PR
         kind = v < left1 ? 1 : 3;
         idx = v < left1 ? d1 + v : d3 + (v - left1);
     }
-    const int j = kind == 1 ? (a.n1 == 2 ? (idx & 1) : 0) : 0;
-    const int p = kind == 1 ? (a.n1 == 2 ? (idx >> 1) : idx) : idx;
+    // two K = 1 jobs share the K = 1 items: job idx & 1, position idx >> 1.  The shift count in integer arithmetic on `kind` as
+    // a WORD (1 or 3) and n1 (0, 1 or 2): as the 1-bit value the compiler makes of (kind == 1 && n1 == 2) each use of it as a
+    // number went v_cndmask_b32 + v_readfirstlane_b32
+    asm("" : "+s"(kind));
+    const int sh = (a.n1 >> 1) & ((3 - kind) >> 1);
+    const int j = idx & sh;
+    const int p = idx >> sh;
     const int pos = a.interleave ? p * 8 + x : x * a.per + p;   // launch position: XCD x owns a contiguous chunk, or every 8th
     const bool live = p < a.per && pos < a.G && (kind == 1 ? idx < items1 : idx < items3);
     // ---- everything the workgroup needs to know is requested HERE, in front of the opening barrier: the item word (one
@@ -735,9 +823,10 @@ __global__ __launch_bounds__(64 * PR_SMAX) __attribute__((amdgpu_waves_per_eu(PR
     __builtin_memcpy(&h, jp, sizeof(SearchHot));
     if (threadIdx.x == 0) { s_ticket = 0u; s_t0 = prof ? wall_clock64() : 0ull; }
     __syncthreads();                        // at the start, where all waves of the workgroup arrive together
+    PR_MARK("query");
     // the values are wanted in registers at this point: keeps the compiler from moving a load down to its first use
     asm volatile("" :: "s"(rec), "s"(h.tlen), "s"(h.q), "s"(h.q_alt), "s"(h.tsoa), "s"(h.boxes), "s"(h.seed), "s"(h.pd),
-                 "s"(h.pi), "s"(h.cost), "s"(h.P1), "s"(h.Ppad), "s"(h.nqg), "s"(h.P2));
+                 "s"(h.pi), "s"(h.cost), "s"(h.P1), "s"(h.Ppad), "s"(h.nqg), "s"(h.P2), "s"(h.nqg_rcp), "s"(h.L));
     const unsigned long long t0 = s_t0;
     if (!live) {                                                        // padding of the last chunk (uniform per workgroup)
         if (prof && threadIdx.x == 0) { prof[2 * (size_t)L] = t0; prof[2 * (size_t)L + 1] = t0; a_.prof_pairs[L] = 0u; }
@@ -746,11 +835,15 @@ __global__ __launch_bounds__(64 * PR_SMAX) __attribute__((amdgpu_waves_per_eu(PR
     const int S = kind == 1 ? a.S1 : a.S3;
     if (s >= S) return;                                                 // the other kind of item uses more waves
     // without item words (the stand-alone warm operators): the order array, then the query map
-    const int grp = items ? (int)((unsigned)rec & SEARCH_ITEM_PAIR_MASK) : (jp->border ? jp->border[pos] : pos);
-    const int b = grp / h.nqg, g = grp - b * h.nqg;
-    const int qb = items ? (int)((unsigned)rec >> SEARCH_ITEM_PAIR_BITS) - 1 : (jp->qmap ? jp->qmap[b] : b);
+    // (both as scalar loads: as plain loads they were global_load + v_readfirstlane, and the query frame -- a phi of a scalar and
+    // a vector value -- took the frame's base through two v_mul_lo_u32 and two v_readfirstlane for launches WITH item words too)
+    const int grp = items ? (int)((unsigned)rec & SEARCH_ITEM_PAIR_MASK) : (jp->border ? pr_uniform_word(jp->border + pos) : pos);
+    // the pair -> (batch, query group) without a division: the job carries the reciprocal of nqg beside it (internal.h)
+    const int b = (int)reart_div_by_magic((unsigned)grp, (unsigned)h.nqg, h.nqg_rcp), g = grp - b * h.nqg;
+    const int qb = items ? (int)((unsigned)rec >> SEARCH_ITEM_PAIR_BITS) - 1 : (jp->qmap ? pr_uniform_word(jp->qmap + b) : b);
     const int n2 = h.tlen ? pr_uniform_word(h.tlen + b) : h.P2;       // beside the query and the seeds; wanted when the seeds are in
-    const float *qcloud = qb < 0 ? h.q_alt : h.q + (size_t)qb * h.P1 * 3;
+    const float *qcloud = qb < 0 ? h.q_alt : (const float *)pr_frame<OFF32>(h.q, qb, h.P1, 3);
+    const float *cloud = (const float *)pr_frame<OFF32>(h.tsoa, b, 3, h.Ppad);
     float qx = 0.f, qy = 0.f, qz = 0.f;
     float bm[3] = {INFINITY, INFINITY, INFINITY};
     int bb[3] = {-1, -1, -1};
@@ -772,16 +865,15 @@ __global__ __launch_bounds__(64 * PR_SMAX) __attribute__((amdgpu_waves_per_eu(PR
         float *s_bb = (float *)s_q;          // the bounds of a coarse round's 64 boxes take the first 384 entries of the queue's space
         s_q += 384;
         constexpr int QC = PR_QCAP - 384;
-        const float *cloud = h.tsoa + (size_t)b * 3 * h.Ppad;
-        const float *boxes_p = h.boxes + (size_t)b * (h.Ppad / NN_BOX) * 8;
+        const float *boxes_p = (const float *)pr_frame<OFF32>(h.boxes, b, (int)((unsigned)h.Ppad / NN_BOX), 8);
         PH_HEAD_END;
         if (kind == 1) {
             float m1[1]; int b1[1];
-            knn_pruned_wave<1, false, QC, true>(qcloud, h.seed, h.P1, n2, S, a.sparse, b, g, s, cloud, h.Ppad, boxes_p, s_tg, s_qc, s_q, s_bb, share, share > 1 ? &s_xthr[0][0] : nullptr, s_key,
+            knn_pruned_wave<1, false, QC, true, OFF32>(qcloud, h.seed, h.P1, n2, S, a.sparse, b, g, s, cloud, h.Ppad, boxes_p, s_tg, s_qc, s_q, s_bb, share, share > 1 ? &s_xthr[0][0] : nullptr, s_key,
                                                qx, qy, qz, m1, b1, work, pairs);
             bm[0] = m1[0]; bb[0] = b1[0];
         } else {
-            knn_pruned_wave<3, false, QC, true>(qcloud, h.seed, h.P1, n2, S, a.sparse, b, g, s, cloud, h.Ppad, boxes_p, s_tg, s_qc, s_q, s_bb, share, share > 1 ? &s_xthr[0][0] : nullptr, s_key,
+            knn_pruned_wave<3, false, QC, true, OFF32>(qcloud, h.seed, h.P1, n2, S, a.sparse, b, g, s, cloud, h.Ppad, boxes_p, s_tg, s_qc, s_q, s_bb, share, share > 1 ? &s_xthr[0][0] : nullptr, s_key,
                                                qx, qy, qz, bm, bb, work, pairs);
         }
         PH_ENTRY_FLUSH(kind == 1 ? 0 : 1);
@@ -807,10 +899,11 @@ __global__ __launch_bounds__(64 * PR_SMAX) __attribute__((amdgpu_waves_per_eu(PR
 #pragma unroll
         for (int k = 0; k < 3; ++k) { bm[k] = PARK_M(0)[k * 64 + lane]; bb[k] = PARK_B(0)[k * 64 + lane]; }
     }
+    PR_MARK("merge");
     // ---- merge the slices' candidates by (minimum, first index): distinct slices hold distinct boxes, so the lower block
     // start is the lower index
     const int i = g * NN_BS + lane;
-    const float *tx = h.tsoa + (size_t)b * 3 * h.Ppad, *ty = tx + h.Ppad, *tz = ty + h.Ppad;
+    const float *tx = cloud, *ty = tx + h.Ppad, *tz = ty + h.Ppad;
     if (kind == 1) {
         float m = bm[0];
         int blk = bb[0];
@@ -831,8 +924,9 @@ __global__ __launch_bounds__(64 * PR_SMAX) __attribute__((amdgpu_waves_per_eu(PR
         }
         pairs += 64u * (NN_BOX / 2);
         if (i < h.P1) {
-            const size_t o = (size_t)b * h.P1 + i;
-            h.pd[o] = m; h.pi[o] = bi;
+            // (wave-uniform frame base) + (32-bit lane offset), as the loads of the prologue
+            *(float *)(pr_frame<OFF32>(h.pd, b, h.P1, 1) + 4u * (unsigned)i) = m;
+            *(int *)(pr_frame<OFF32>(h.pi, b, h.P1, 1) + 4u * (unsigned)i) = bi;
         }
     } else {
         float kd[3] = {INFINITY, INFINITY, INFINITY};
@@ -847,9 +941,10 @@ __global__ __launch_bounds__(64 * PR_SMAX) __attribute__((amdgpu_waves_per_eu(PR
             }
         }
         if (i < h.P1) {
-            const size_t o = ((size_t)b * h.P1 + i) * 3;
+            float *od = (float *)(pr_frame<OFF32>(h.pd, b, h.P1, 3) + 12u * (unsigned)i);
+            int *oi = (int *)(pr_frame<OFF32>(h.pi, b, h.P1, 3) + 12u * (unsigned)i);
 #pragma unroll
-            for (int k = 0; k < 3; ++k) { h.pd[o + k] = kd[k]; h.pi[o + k] = kd[k] < INFINITY ? ki[k] : -1; }
+            for (int k = 0; k < 3; ++k) { od[k] = kd[k]; oi[k] = kd[k] < INFINITY ? ki[k] : -1; }
         }
     }
     if (lane == 0) {
@@ -919,11 +1014,11 @@ __global__ __launch_bounds__(64 * PC_WAVES) void knn_cloud_kernel(SearchArgs a) 
         const int n2 = jb.tlen ? jb.tlen[b] : jb.P2;
         if (kind == 1) {
             float m1[1]; int b1[1];
-            knn_pruned_wave<1, true, PC_QCAP, false>(qcloud, jb.seed, jb.P1, n2, S, a.sparse, b, g, sl, cl, Ppad, bxs, nullptr, s_qc, s_q, nullptr, a.share, nullptr, s_key, qx, qy, qz,
+            knn_pruned_wave<1, true, PC_QCAP, false, false>(qcloud, jb.seed, jb.P1, n2, S, a.sparse, b, g, sl, cl, Ppad, bxs, nullptr, s_qc, s_q, nullptr, a.share, nullptr, s_key, qx, qy, qz,
                                               m1, b1, work, pairs);
             bm[0] = m1[0]; bb[0] = b1[0];
         } else {
-            knn_pruned_wave<3, true, PC_QCAP, false>(qcloud, jb.seed, jb.P1, n2, S, a.sparse, b, g, sl, cl, Ppad, bxs, nullptr, s_qc, s_q, nullptr, a.share, nullptr, s_key, qx, qy, qz,
+            knn_pruned_wave<3, true, PC_QCAP, false, false>(qcloud, jb.seed, jb.P1, n2, S, a.sparse, b, g, sl, cl, Ppad, bxs, nullptr, s_qc, s_q, nullptr, a.share, nullptr, s_key, qx, qy, qz,
                                               bm, bb, work, pairs);
         }
         if (S > 1 && sl > 0) {
@@ -1015,7 +1110,25 @@ static int search_check(SearchArgs &a) {
     if (a.n3 && (!a.k3.boxes || !a.k3.seed || !a.k3.pd || !a.k3.pi)) return REART_ERR_INVALID_ARG;
     a.per = reart_div_up(a.G, 8);
     a.k_nqg = a.n1 ? a.k1[0].nqg : a.k3.nqg;
+    for (int j = 0; j < a.n1; ++j) {
+        if (a.k1[j].nqg < 1) return REART_ERR_INVALID_ARG;
+        a.k1[j].nqg_rcp = reart_div_magic((unsigned)a.k1[j].nqg);
+    }
+    if (a.n3) {
+        if (a.k3.nqg < 1) return REART_ERR_INVALID_ARG;
+        a.k3.nqg_rcp = reart_div_magic((unsigned)a.k3.nqg);
+    }
     return REART_OK;
+}
+// every frame offset of every job of the launch in 32 bits (reart_search_off32): picks the kernel's instantiation.
+// The batch count is G / nqg: every caller lays out G = B * nqg pairs (SearchArgs::G), which is checked here.
+static bool search_off32(const SearchArgs &a) {
+    bool ok = !a.wide;
+    for (int j = 0; j < a.n1; ++j) ok = ok && a.G % a.k1[j].nqg == 0;
+    if (a.n3) ok = ok && a.G % a.k3.nqg == 0;
+    for (int j = 0; j < a.n1; ++j) ok = ok && reart_search_off32(a.G / a.k1[j].nqg, a.k1[j].P1, a.k1[j].Ppad, 1);
+    if (a.n3) ok = ok && reart_search_off32(a.G / a.k3.nqg, a.k3.P1, a.k3.Ppad, 3);
+    return ok;
 }
 
 int reart_search_launch(const SearchArgs &a_in, hipStream_t st) {
@@ -1048,8 +1161,13 @@ int reart_search_launch_batch(const SearchArgs *ak, int K, hipStream_t st) {
     const SearchArgs &a = ab.a[0];
     const int S = (a.n1 ? a.S1 : 0) > (a.n3 ? a.S3 : 0) ? a.S1 : a.S3;
     const size_t lds = (size_t)S * PR_LDS_WAVE_BYTES;
-    if (K == 1) hipLaunchKernelGGL(knn_group_kernel<false>, dim3(reart_search_grid(a.n1, a.n3, a.G)), dim3(64 * S), lds, st, ab);
-    else hipLaunchKernelGGL(knn_group_kernel<true>, dim3(reart_search_grid(a.n1, a.n3, a.G), K), dim3(64 * S), lds, st, ab);
+    bool off32 = true;
+    for (int k = 0; k < K; ++k) off32 = off32 && search_off32(ab.a[k]);
+    const dim3 grid1(reart_search_grid(a.n1, a.n3, a.G)), gridK(reart_search_grid(a.n1, a.n3, a.G), K);
+    if (K == 1 && off32) hipLaunchKernelGGL((knn_group_kernel<false, true>), grid1, dim3(64 * S), lds, st, ab);
+    else if (K == 1) hipLaunchKernelGGL((knn_group_kernel<false, false>), grid1, dim3(64 * S), lds, st, ab);
+    else if (off32) hipLaunchKernelGGL((knn_group_kernel<true, true>), gridK, dim3(64 * S), lds, st, ab);
+    else hipLaunchKernelGGL((knn_group_kernel<true, false>), gridK, dim3(64 * S), lds, st, ab);
     REART_CHECK_LAUNCH();
     return REART_OK;
 }

@@ -130,6 +130,11 @@ extern "C" size_t reart_relax_workspace_bytes(const reart_relax_config *cfg) {
     return p.total;
 }
 
+// item words (internal.h) or plain pairs + the query map: one decision for relax_init_kernel, which writes them, and the
+// step, which hands them to the search.  search_mode 3 | 4 take the second form where the first would fit (tests)
+REART_HD static inline bool relax_item_words(const reart_relax_config &c, long pairs) {
+    return reart_search_items_fit(pairs, c.B) && c.search_mode != 3 && c.search_mode != 4;
+}
 // ------------------------------------------------------------------------------ prepare
 __global__ void relax_init_kernel(reart_relax_config c, const int *__restrict__ ref_off,
                                   int *__restrict__ rlen, int *__restrict__ qmap,
@@ -173,7 +178,7 @@ __global__ void relax_init_kernel(reart_relax_config c, const int *__restrict__ 
         // flow job qmap[t]).  Shapes whose pairs or frames do not fit the word keep plain pairs (KnnJob::border).
         {
             const int nqg = (c.N + NN_BS - 1) / NN_BS, ng = c.B * nqg;
-            const bool words = reart_search_items_fit((long)ng, c.B);
+            const bool words = relax_item_words(c, (long)ng);
             for (int g = 0; g < nqg; ++g)
                 for (int j = 0; j < 3; ++j)
                     item[j * ng + t * nqg + g] = words ? reart_search_item(t * nqg + g, j < 2 ? t : qm) : (unsigned int)(t * nqg + g);
@@ -780,7 +785,7 @@ static int step_describe(const reart_relax_config *cfg, const reart_relax_buffer
 
     const int nqg = reart_div_up(N, NN_BS);
     const int *qmap = (const int *)(ws + p.o_qmap);
-    const bool item_words = reart_search_items_fit((long)B * nqg, B);       // as relax_init_kernel decides
+    const bool item_words = relax_item_words(c, (long)B * nqg);             // as relax_init_kernel decides
     // job descriptions: K = 1 x -> y (0), y -> x (1); K = 3 flow
     KnnArgs &ka = L.ka, &k3 = L.k3;
     ka.N = B; ka.S = p.S1; ka.K = 1; ka.euclidean = 0;
@@ -826,6 +831,7 @@ static int step_describe(const reart_relax_config *cfg, const reart_relax_buffer
         SearchArgs &sa = L.sa;
         sa.item = item_words ? (const unsigned int *)(ws + p.o_item) : nullptr;
         sa.G = B * nqg; sa.S1 = p.W1; sa.S3 = p.W3; sa.sparse = p.sparse; sa.share = c.tune_share < 0 ? 0 : (c.tune_share == 1 ? 1 : 2); sa.interleave = c.tune_xcd > 0 ? 0 : 1;
+        sa.wide = (c.search_mode == 2 || c.search_mode == 4) ? 1 : 0;
         sa.cloud_resident = c.tune_cloud > 0 ? 1 : 0; sa.cloud_slices = c.tune_cloud > 0 ? c.tune_cloud : 0;
         if (chamfer) { sa.k1[0] = ka.job[0]; sa.k1[1] = ka.job[1]; sa.n1 = 2; }
         if (c.use_flow) { sa.k3 = k3.job[0]; sa.n3 = 1; }
